@@ -10,11 +10,19 @@ rank stops the rest and fails the run). Each rank is one notebook pod's GPU runn
 the K1 readiness op: a bf16 GEMM C = A @ B^T (8192^3 by default) on the hand-written gfx950 MFMA
 kernel. A "step" = one such GEMM on every GPU. ``--prewarm-s`` (default 1 s) of untimed GEMMs settle
 the GPU clock, then W untimed warmup steps, then exactly K timed steps bracketed by barrier + device
-sync on both sides; the slowest rank's time is used. After the timed region rank 0 times
-torch.matmul (hipBLASLt) on the same operands (``torch_matmul_tflops_per_gpu``, never the value). ``value`` is
-the whole-job aggregate TFLOPS (N x per-GEMM FLOPs / max-rank time). Weak scaling: per-GPU work
+sync on both sides; the slowest rank's time is used. ``value`` is
+the whole-job aggregate TFLOPS (N x per-GEMM FLOPs / max-rank time), ``ms_per_step`` the milliseconds
+one timed step took. Weak scaling: per-GPU work
 is fixed as N grows. Data: synthetic uniform [-1, 1) bf16 operands (random data, not zeros:
-zero operands inflate MFMA clocks — cdna_hip_programming.md §5.4 rule 25).
+zero operands inflate MFMA clocks — cdna_hip_programming.md §5.4 rule 25), seeded by the rank alone.
+
+A plain run stops there: it sets up, warms up, times the K steps, writes the last step's result when
+``--dump-outputs DIR`` is given (``DIR/c.npy``, float32; a fixed seeded sample of rows when C is
+large) and prints the result line. Everything below runs only with ``--full``.
+
+``--full``: the GEMM is first checked against a fp32 reference (``correct``, ``max_abs_err_vs_fp32``;
+a wrong result fails the run), and after the timed region rank 0 times torch.matmul (hipBLASLt) on
+the same operands (``torch_matmul_tflops_per_gpu``, never the value).
 
 Cold start (rank 0, after the timed region, while the other ranks wait on a CPU-side barrier with
 their GPU memory released): ``--coldstart-runs`` (default 10) Notebook CREATE -> Ready runs of ONE
@@ -51,6 +59,18 @@ def parse_args():
                         "sustained clock rather than on the DVFS ramp from idle (0 disables)")
     # --gemm-m/-n/-k: the spellings to use behind torch.distributed.run, whose parser rejects "--m"
     # as an ambiguous prefix of its own options even after the script name
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything that is not the headline figure: the fp32 "
+                        "spot check of the GEMM, the A/B against torch.matmul (hipBLASLt), the RCCL / peer "
+                        "all-reduce sweeps and the xGMI probe (N > 1 or --force-dist), the notebook cold starts "
+                        "and the control-plane latencies. Off by default: a plain run sets up, warms up, times "
+                        "the K steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                        "(float32): c.npy, the GEMM result C (c_rank<r>.npy per rank when N > 1). A result "
+                        "larger than the per-rank share of 32 MiB is written as a fixed sample of whole rows "
+                        "(sorted indices drawn by numpy.random.default_rng(0)). The operands depend only on "
+                        "the arguments and the rank, so two builds can be compared output for output")
     p.add_argument("--m", "--gemm-m", dest="m", type=int, default=8192)
     p.add_argument("--n", "--gemm-n", dest="n", type=int, default=8192)
     p.add_argument("--k", "--gemm-k", dest="k", type=int, default=8192)
@@ -74,7 +94,28 @@ def parse_args():
     p.add_argument("--budget-s", type=float, default=float(os.environ.get("KFAMD_BENCH_BUDGET_S", "450")),
                    help="wall-clock budget from process start for everything after the timed region: extras "
                         "that do not fit are reported as skipped, one that hangs as timeout (bench_extras.py)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: float32 bytes written over all ranks (well inside 64 MB)
+
+
+def dump_outputs(out_dir: str, c, rank: int, world: int) -> None:
+    """--dump-outputs: the result of the last timed step as float32 .npy, whole when it fits this
+    rank's share of DUMP_BYTES, else the same seeded sample of whole rows in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    m, n = c.shape
+    keep = max(1, DUMP_BYTES // world // (4 * n))
+    if keep < m:
+        rows = np.sort(np.random.default_rng(0).choice(m, size=keep, replace=False))
+        c = c.index_select(0, torch.from_numpy(rows).to(c.device))
+    name = "c.npy" if world == 1 else f"c_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), c.float().cpu().numpy())
 
 
 COLD_START_NOTE = ("process pods (no container runtime). cold_start_* = the product's default path: the "
@@ -197,14 +238,16 @@ def main() -> int:
     b = (torch.rand(N, K, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
     c = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
 
-    # correctness check of this very configuration against a fp32 reference: one row in every
+    # --full: correctness check of this very configuration against a fp32 reference: one row in every
     # 256-row macro-tile (a different row offset in each) against ALL N columns, so every output tile
     # of the XCD-remapped grid — and every wave's row range within the tiles — is compared
-    ops.gemm_nt(a, b, out=c)
-    rows = torch.tensor([t * 256 + (t * 37) % min(256, M - t * 256) for t in range((M + 255) // 256)], device=dev)
-    ref = a.index_select(0, rows).float() @ b.float().t()
-    err = (c.index_select(0, rows).float() - ref).abs().max().item()
-    ok = err <= 1e-2 * ref.abs().max().item() + 1e-2
+    ok = True
+    if args.full:
+        ops.gemm_nt(a, b, out=c)
+        rows = torch.tensor([t * 256 + (t * 37) % min(256, M - t * 256) for t in range((M + 255) // 256)], device=dev)
+        ref = a.index_select(0, rows).float() @ b.float().t()
+        err = (c.index_select(0, rows).float() - ref).abs().max().item()
+        ok = err <= 1e-2 * ref.abs().max().item() + 1e-2
 
     def step():
         ops.gemm_nt(a, b, out=c)
@@ -264,14 +307,25 @@ def main() -> int:
         "dist_path": "rccl" if distributed else "none",
         "per_gpu_tflops": round(per_gpu_tflops, 2),
         "kernel": "kfamd gemm_w4 (4 waves x 128x128, one wave/SIMD, asm MFMA 16x16x32 bf16 with AGPR accumulators, buffer_load..lds into a 5-slot LDS ring with the K loop unrolled over its 5-tile period, XCD remap, in-kernel edge tiles)",
-        "check_rows": int(rows.numel()),
-        "correct": bool(ok),
-        "max_abs_err_vs_fp32": err,
     }
+
+    if args.dump_outputs:
+        # before any extra: the A/B below writes torch.matmul's result into the same buffer
+        dump_outputs(args.dump_outputs, c, rank, world)
+
+    from kubeflow_rm_amd.bench_extras import Extras, print_line
+    if not args.full:
+        # a plain run ends here: set up, warmed up, K steps timed, outputs written, the line
+        if rank == 0:
+            print_line(line)
+        if distributed:
+            dist.destroy_process_group()
+        return 0
+
+    line.update({"check_rows": int(rows.numel()), "correct": bool(ok), "max_abs_err_vs_fp32": err})
 
     # everything after the timed region is an extra: own try, own deadline, overall budget, and a
     # watchdog that prints the line with what was measured if one of them hangs (bench_extras.py)
-    from kubeflow_rm_amd.bench_extras import Extras, print_line
     import datetime
     # the CPU group's own timeout bounds every wait on it (ranks != 0 park on it during rank 0's
     # cold starts): past the budget a barrier raises instead of waiting for the 30-minute default

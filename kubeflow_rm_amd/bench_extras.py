@@ -1,6 +1,6 @@
 """Budgeted post-measurement extras for ``bench.py``.
 
-After the timed GEMM region ``bench.py`` runs optional extras: the RCCL sweep, the hand-written
+After the timed GEMM region ``bench.py --full`` runs optional extras: the RCCL sweep, the hand-written
 one-/two-shot all-reduces, the xGMI probe, four cold-start variants and the control-plane
 latencies. Any of them can be slow or, in the worst case, hang (a collective whose peer died, a
 notebook pod that never becomes Ready). None of them may cost the headline JSON line, so:

@@ -7,6 +7,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import pytest
+
 ROOT = Path(__file__).resolve().parent.parent
 
 _STUB = r"""
@@ -69,6 +71,70 @@ def test_control_plane_latencies_measured():
     r = measure_control_plane(runs=2)
     for k in ("profile_ready_p50_s", "tensorboard_ready_p50_s", "pvcviewer_ready_p50_s"):
         assert r[k] is not None and 0 < r[k] < 30, r
+
+
+def test_dump_outputs_whole_and_seeded_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small result is written whole as float32; one over the byte budget as the
+    same sorted sample of whole rows every time, split between the ranks when there are several."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    c = torch.arange(40 * 8, dtype=torch.float32).reshape(40, 8).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "whole"), c, 0, 1)
+    whole = np.load(tmp_path / "whole" / "c.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, c.float().numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * 8 * 4)  # room for 10 rows
+    bench.dump_outputs(str(tmp_path / "s1"), c, 0, 1)
+    bench.dump_outputs(str(tmp_path / "s2"), c, 0, 1)
+    s1, s2 = np.load(tmp_path / "s1" / "c.npy"), np.load(tmp_path / "s2" / "c.npy")
+    assert s1.shape == (10, 8) and np.array_equal(s1, s2)
+    rows = (s1[:, 0] / 8).astype(int)  # row r starts with 8 r: exact in bf16 up to 256
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, c.float().numpy()[rows])
+    bench.dump_outputs(str(tmp_path / "s1"), c, 1, 2)
+    assert np.load(tmp_path / "s1" / "c_rank1.npy").shape == (5, 8)
+
+
+def _bench_gpu(*argv):
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--prewarm-s", "0", "--gemm-m", "520", "--gemm-n", "392", "--gemm-k", "264", *argv],
+                       cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_gpu_plain_run_times_the_steps_and_dumps_the_last_result(tmp_path):
+    """A plain run: the K timed steps and the result line, nothing after them; --dump-outputs writes
+    the GEMM result of the operands that the arguments determine (an odd shape with edge tiles)."""
+    import numpy as np
+    import torch
+    d = _bench_gpu("--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["unit"].startswith("TFLOPS")
+    assert "extras_status" not in d and "correct" not in d and "cold_start_p50_s" not in d
+    got = np.load(tmp_path / "out" / "c.npy")
+    assert got.dtype == np.float32 and got.shape == (520, 392)
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    a = (torch.rand(520, 264, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+    b = (torch.rand(392, 264, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+    ref = (a.double() @ b.double().t()).cpu().numpy()
+    # fp32 accumulation of 264 bf16 products (2^-24 each, relative to sum |a||b| <= 264), then one
+    # rounding of the result to bf16 (8 significand bits: unit roundoff 2^-8)
+    tol = 2.0 ** -8 * np.abs(ref) + 264 * 264 * 2.0 ** -24
+    assert np.all(np.abs(got - ref) <= tol), float(np.abs(got - ref).max())
+
+
+@pytest.mark.gpu
+def test_gpu_full_run_keeps_the_check_and_the_extras():
+    d = _bench_gpu("--full", "--coldstart-runs", "0", "--ab-blocks", "1", "--budget-s", "120")
+    assert d["correct"] is True and d["check_rows"] == 3 and d["ms_per_step"] > 0
+    assert d["extras_status"]["gemm_ab_vs_hipblaslt"]["status"] == "ok" and d["ab_ours_tflops_median"] > 0
 
 
 _HANG_STUB = r"""

@@ -170,14 +170,14 @@ def test_readiness_rccl_single_stage():
 
 
 def test_bench_force_dist_runs_the_multi_gpu_path_under_torchrun(tmp_path):
-    """``torchrun --nproc-per-node 1 bench.py --force-dist``: the nccl init, the gloo CPU group, the
+    """``torchrun --nproc-per-node 1 bench.py --full --force-dist``: the nccl init, the gloo CPU group, the
     agree barrier, the RCCL sweep, the peer all-reduces, the xGMI probe and the cold-start parking
     all run, and the one JSON line carries their keys."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT",
                                                              "KFAMD_FORCE_DIST")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), str(ROOT / "bench.py"),
-           "--gpus", "1", "--steps", "5", "--warmup", "2", "--prewarm-s", "0.2", "--gemm-m", "2048", "--gemm-n",
+           "--full", "--gpus", "1", "--steps", "5", "--warmup", "2", "--prewarm-s", "0.2", "--gemm-m", "2048", "--gemm-n",
            "2048", "--gemm-k", "2048", "--force-dist", "--coldstart-runs", "1", "--coldstart-torch-runs", "0", "--ab-blocks", "2",
            "--budget-s", "240"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)

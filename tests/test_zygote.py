@@ -8,7 +8,9 @@ kills the process; and a zygote that is gone falls back to a fresh interpreter.
 """
 import json
 import os
+import shutil
 import signal
+import tempfile
 import time
 import urllib.error
 import urllib.request
@@ -37,6 +39,23 @@ def zc():
         cl.wait_zygotes(timeout=300)
         cl.client.create({"apiVersion": "v1", "kind": "Namespace", "metadata": {"name": "zy"}})
         yield cl
+
+
+@pytest.fixture
+def zsock(tmp_path):
+    """Path for a zygote's socket. An AF_UNIX address holds at most 107 bytes and the zygote binds
+    ``<path>.tmp`` first: under a deep temporary root pytest's tmp_path is too long for it, and the
+    socket gets a short directory of its own."""
+    path = str(tmp_path / "z.sock")
+    if len(os.fsencode(path + ".tmp")) <= 100:
+        yield path
+        return
+    base = tempfile.gettempdir()
+    d = tempfile.mkdtemp(prefix="zy-", dir=base if len(os.fsencode(base)) <= 70 else "/tmp")
+    try:
+        yield os.path.join(d, "z.sock")
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def _get(url):
@@ -178,14 +197,14 @@ def test_gpu_torch_ready_notebook_fresh_interpreter_is_reliable():
         assert run["cold_start_s"] <= 4.0, [x["cold_start_s"] for x in r["runs"]]
 
 
-def test_zygote_protocol_thread_pool_env_argv_exit(tmp_path):
+def test_zygote_protocol_thread_pool_env_argv_exit(tmp_path, zsock):
     """The protocol directly: a forked container gets its own CPU mask with a torch/OpenMP pool sized
     to it (not the zygote's), its env, argv and cwd; the exit status comes back on the connection."""
     import socket
     import subprocess
     import sys
     root = Path(__file__).resolve().parents[1]
-    sock = str(tmp_path / "z.sock")
+    sock = zsock
     env = dict(os.environ, PYTHONPATH=str(root))
     env.pop("OMP_NUM_THREADS", None)
     env.pop("OPENBLAS_NUM_THREADS", None)
@@ -263,12 +282,12 @@ def test_zygote_refuses_a_multithreaded_preload(tmp_path):
     assert not os.path.exists(sock)
 
 
-def test_zygote_rejects_malformed_requests(tmp_path):
+def test_zygote_rejects_malformed_requests(tmp_path, zsock):
     import socket
     import subprocess
     import sys
     root = Path(__file__).resolve().parents[1]
-    sock = str(tmp_path / "z.sock")
+    sock = zsock
     z = subprocess.Popen([sys.executable, "-m", "kubeflow_rm_amd.images.zygote", "--socket", sock],
                          env=dict(os.environ, PYTHONPATH=str(root)), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     try:
@@ -338,14 +357,14 @@ def test_gpu_warm_child_takes_the_one_gpu_notebook():
     assert sum(x["readiness_stages"].get("warm_op", 0) for x in r["runs"]) >= 2, [x["readiness_stages"] for x in r["runs"]]
 
 
-def test_warm_children_fail_soft_without_a_gpu(tmp_path):
+def test_warm_children_fail_soft_without_a_gpu(tmp_path, zsock):
     """On a host without a GPU a zygote asked for warm children reports each failure (at most 3 in a
     row per device) and keeps serving plain forks."""
     import socket
     import subprocess
     import sys
     root = Path(__file__).resolve().parents[1]
-    sock = str(tmp_path / "z.sock")
+    sock = zsock
     log = tmp_path / "z.log"
     env = dict(os.environ, PYTHONPATH=str(root), HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
     with open(log, "w") as lf:

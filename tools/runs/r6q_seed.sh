@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest -m gpu -q --timeout 240 --timeout-method t
 rc=$?; tail -3 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
 ls -la ${XDG_CACHE_HOME:-$HOME/.cache}/kfamd/ > $OUT/seed_ls.txt 2>&1; du -sh ${XDG_CACHE_HOME:-$HOME/.cache}/kfamd/* >> $OUT/seed_ls.txt 2>&1
 cat $OUT/seed_ls.txt
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || exit $?
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit $?
 python3 -c "
 import json
 d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
