@@ -211,6 +211,37 @@ int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, const void*
                         const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int T,
                         int D, float scale, int causal, const long long* strides, void* stream);
 
+// ---- decode (KV-cache generation) ------------------------------------------------------------
+// Single-query attention over a KV cache (attn_decode_bf16.hip), bf16 I/O, fp32 softmax, D = 64 / 128.
+//   q [B][H][D] (element strides b, h), k_cache / v_cache [B][H][Tcap][D] (strides b, h, t),
+//   o [B][H][D] (strides b, h); head dim contiguous. strides = {qb, qh, kb, kh, kt, vb, vh, vt, ob, oh}.
+//   lens: DEVICE int32 [B]; row b attends keys 0 .. lens[b]-1 (clamped to t_bound). t_bound: host upper
+//   bound of every lens[b] (<= Tcap); it sizes the grid: ceil(t_bound / split_keys) splits per (b, h).
+//   lse: optional f32 [B][H]. ws: kfamd_attn_decode_workspace bytes (unused with one split).
+// KFAMD_EINVAL: D not 64 / 128, t_bound < 1, a (b, h) slice of 2^31 bytes or more; KFAMD_EALIGN: rows
+// not 16-B aligned.
+int kfamd_attn_decode_split_keys(void);
+long long kfamd_attn_decode_workspace(int B, int H, int D, int t_bound);
+int kfamd_attn_decode_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                           float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
+                           const long long* strides, void* stream);
+// K and V rows of a fused QKV activation [B][T][3][H][D] (element strides qb, qt; [3][H][D] dense) into
+// the caches at rows pos[b] .. pos[b]+T-1 (pos: device int32 [B], not advanced). cache_strides = {kb, kh,
+// kt, vb, vh, vt}. Rows at or beyond Tcap are dropped.
+int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int H, int D,
+                         int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream);
+
+// Weight-streaming NT GEMM for 1 <= M <= 16 (gemm_skinny_bf16.hip): C[M][N] = act(alpha * A[M][K] .
+// W[N][K]^T + bias[N]) (+ R[M][N]); K % 8 == 0, A / W rows 16-B aligned, any N, epilogue semantics of
+// kfamd_gemm_nt_bf16. KFAMD_EINVAL: M outside 1..16 (or K % 8); KFAMD_EALIGN: alignment.
+int kfamd_gemm_nt_skinny_bf16(const void* A, const void* W, void* C, const void* bias, const void* R, int M, int N,
+                              int K, long long lda, long long ldw, long long ldc, long long ldr, float alpha, int act,
+                              void* stream);
+// the same with the arithmetic pattern forced (tests / bench): 0 = by M, 1 = VALU (M <= 8), 2 = MFMA
+int kfamd_gemm_nt_skinny_bf16_path(int path, const void* A, const void* W, void* C, const void* bias, const void* R,
+                                   int M, int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
+                                   float alpha, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

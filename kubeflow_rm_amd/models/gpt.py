@@ -11,6 +11,10 @@ With a tensor-parallel group the attention heads and the MLP are split Megatron-
 (QKV / fc1 column-parallel, out-proj / fc2 row-parallel: one all-reduce per sub-block).
 
 On CPU tensors the same module runs torch's reference ops (used by the gloo tests).
+
+Sampling: ``GPT.generate`` (``prefill`` + ``decode_step`` over an ``ops.KVCache``) runs each new token
+on the decode kernels — the M <= 16 weight-streaming GEMM, the KV append and split-KV single-query
+attention — and can replay the step as one hipGraph (no tensor-parallel group; head dims 64 / 128).
 """
 from __future__ import annotations
 
@@ -152,6 +156,43 @@ class Block(torch.nn.Module):
         return self.mlp(h, r)
 
 
+def _sample_top_k(logits, temperature, top_k, generator):
+    """Multinomial over softmax(logits / temperature) restricted to exactly ``top_k`` candidates (the
+    largest logits; among equal logits at the cut, the ones ``torch.topk`` returns)."""
+    vals, ix = torch.topk(logits.float() / temperature, min(int(top_k), logits.shape[-1]), dim=-1)
+    pick = torch.multinomial(torch.softmax(vals, -1), 1, generator=generator)
+    return ix.gather(1, pick).squeeze(1)
+
+
+def _sample(logits, temperature, top_k, generator):
+    """Next token ``[B]`` from logits ``[B, vocab]``: argmax at temperature 0, else multinomial over
+    softmax(logits / temperature), optionally restricted to the top_k largest logits."""
+    # top_k == 1 leaves one candidate, the argmax. bf16 logits hold exact ties, which argmax and topk
+    # need not break the same way, so that case takes argmax itself and equals greedy on any dtype.
+    if temperature == 0 or top_k == 1:
+        return logits.argmax(-1)
+    if top_k is not None:
+        return _sample_top_k(logits, temperature, top_k, generator)
+    return torch.multinomial(torch.softmax(logits.float() / temperature, -1), 1, generator=generator).squeeze(1)
+
+
+class _GraphedDecodeStep:
+    """A captured ``decode_step``: the replay runs no Python of the step, so the capacity check and the
+    host-side bound of ``decode_step`` are kept here (``cache.lens`` may never pass the capacity: the
+    position embedding is gathered by it)."""
+
+    def __init__(self, graphed, cache):
+        self.graphed, self.cache = graphed, cache
+
+    def __call__(self, tok: torch.Tensor) -> torch.Tensor:
+        c = self.cache
+        if c._bound + 1 > c.capacity:
+            raise ValueError(f"cache capacity {c.capacity} exceeded")
+        out = self.graphed(tok)
+        c._bound += 1
+        return out
+
+
 class GPT(torch.nn.Module):
     def __init__(self, cfg: GPTConfig, tp_group=None, device=None):
         super().__init__()
@@ -174,6 +215,163 @@ class GPT(torch.nn.Module):
         if targets is None:
             return logits
         return logits, _cross_entropy(logits, targets)
+
+    # ---- KV-cache generation --------------------------------------------------------------------
+    # prefill() runs the prompt once and fills the cache; decode_step() runs ONE new token per batch
+    # row against it. On the GPU both run on the HIP kernels (prefill: the training forward's GEMMs +
+    # flash attention; decode: the M <= 16 weight-streaming GEMM with fused epilogues, ops.kv_append,
+    # ops.attention_decode); CPU tensors and ops.torch_reference() run the same methods on torch ops.
+    # Nothing in decode_step depends on a host-side position (the position embedding is gathered by
+    # the device-side cache.lens), so it can be captured once into a hipGraph and replayed.
+
+    def new_cache(self, B: int, capacity: int, device=None) -> "ops.KVCache":
+        c = self.cfg
+        if capacity > c.max_seq:
+            raise ValueError(f"cache capacity {capacity} exceeds max_seq {c.max_seq}")
+        return ops.KVCache(c.n_layers, B, self.blocks[0].local_heads, c.head_dim, capacity,
+                           device=device if device is not None else self.tok.device, dtype=c.dtype)
+
+    def _native_decode(self, x: torch.Tensor) -> bool:
+        # both paths read the sharded weights without the TP layers' all-reduces: refuse, on any device
+        if tpl._collective(self.blocks[0].tp_group):
+            raise NotImplementedError("KV-cache generation with a tensor-parallel group that issues collectives")
+        if not (x.is_cuda and ops.native_enabled()):
+            return False
+        if self.cfg.dtype != torch.bfloat16 or self.cfg.head_dim not in ops.decode.HEAD_DIMS:
+            raise ValueError(f"KV-cache generation on a GPU: bf16 and head dim in {ops.decode.HEAD_DIMS} expected, "
+                             f"got {self.cfg.dtype}, head dim {self.cfg.head_dim}")
+        return True
+
+    def _check_cache(self, cache, B: int, T: int) -> None:
+        if cache.B != B or cache.n_layers != len(self.blocks):
+            raise ValueError("cache does not match the batch / model")
+        if cache._bound + T > cache.capacity:
+            raise ValueError(f"cache capacity {cache.capacity} exceeded")
+
+    @torch.no_grad()
+    def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
+        """Run the prompt ``idx [B, T0]`` into an empty ``cache``; logits ``[B, vocab]`` of the last position."""
+        B, T = idx.shape
+        self._check_cache(cache, B, T)
+        if cache._bound != 0:
+            raise ValueError("prefill expects an empty cache (continuing a cache takes decode_step)")
+        native = self._native_decode(self.tok)
+        c = self.cfg
+        x = F.embedding(idx, self.tok) + self.pos[:T]
+        for li, blk in enumerate(self.blocks):
+            h, hd = blk.local_heads, c.head_dim
+            if native:
+                x2 = x.reshape(B * T, c.d_model)
+                y = ops.layer_norm_fwd(x2, blk.ln1.weight, blk.ln1.bias)[0]
+                qkv = ops.gemm_nt(y, blk.qkv.weight, bias=blk.qkv.bias).view(B, T, 3 * h * hd)
+                ops.kv_append(qkv, cache, li)
+                a = ops.attention_qkv(qkv, h, hd, causal=True).view(B * T, h * hd)
+                x2 = ops.gemm_nt(a, blk.proj.weight, bias=blk.proj.bias, residual=x2)
+                y = ops.layer_norm_fwd(x2, blk.ln2.weight, blk.ln2.bias)[0]
+                y = ops.gemm_nt(y, blk.fc1.weight, bias=blk.fc1.bias, act=blk.fc1.act)
+                x = ops.gemm_nt(y, blk.fc2.weight, bias=blk.fc2.bias, residual=x2).view(B, T, c.d_model)
+            else:
+                qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
+                ops.kv_append(qkv, cache, li)
+                q, k, v = qkv.view(B, T, 3, h, hd).permute(2, 0, 3, 1, 4)
+                a = F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
+                x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
+                y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
+                x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
+        cache.advance(T)
+        last = x[:, -1]  # the LM head of the last position only
+        if native:
+            last = ops.layer_norm_fwd(last.contiguous(), self.ln_f.weight, self.ln_f.bias)[0]
+            return ops.gemm_nt(last, self.tok)  # M = B rows: auto routes it as the parent commit did
+        return F.linear(self.ln_f(last), self.tok)
+
+    def _skinny(self, x, w, bias=None, act="none", residual=None):
+        # decode linears: the weight-streaming kernel wherever it beat the "auto" route in
+        # profiles/decode (every gpt-1b projection shape at M = 1, 2, 4, 8, 16: 2.8x to 28x)
+        return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual, variant="skinny")
+
+    @torch.no_grad()
+    def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
+        """One new token ``tok [B]`` per row against ``cache``; logits ``[B, vocab]``. Advances the cache."""
+        B = tok.shape[0]
+        self._check_cache(cache, B, 1)
+        native = self._native_decode(self.tok)
+        c = self.cfg
+        x = F.embedding(tok, self.tok) + F.embedding(cache.lens, self.pos)  # [B, d_model]
+        # the step's attention sees the row it appends: lens + 1, computed on the device
+        att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1)}
+        for li, blk in enumerate(self.blocks):
+            h, hd = blk.local_heads, c.head_dim
+            if native:
+                y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
+                qkv = self._skinny(y, blk.qkv.weight, blk.qkv.bias)  # [B, 3 * h * hd]
+                ops.kv_append(qkv.view(B, 1, 3 * h * hd), cache, li)
+                a = torch.empty(B, h * hd, device=x.device, dtype=x.dtype)
+                ops.attention_decode(qkv.view(B, 3, h, hd)[:, 0], cache, li, out=a.view(B, h, hd), **att)
+                x = self._skinny(a, blk.proj.weight, blk.proj.bias, residual=x)
+                y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
+                y = self._skinny(y, blk.fc1.weight, blk.fc1.bias, act=blk.fc1.act)
+                x = self._skinny(y, blk.fc2.weight, blk.fc2.bias, residual=x)
+            else:
+                qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
+                ops.kv_append(qkv.view(B, 1, -1), cache, li)  # torch ops: CPU tensors / torch_reference()
+                a = ops.attention_decode(qkv.view(B, 3, h, hd)[:, 0], cache, li, **att).reshape(B, h * hd)
+                x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
+                y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
+                x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
+        cache.advance(1)
+        if native:
+            return self._skinny(ops.layer_norm_fwd(x, self.ln_f.weight, self.ln_f.bias)[0], self.tok)
+        return F.linear(self.ln_f(x), self.tok)
+
+    @torch.no_grad()
+    def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
+                 generator: torch.Generator | None = None, graph: bool = False) -> torch.Tensor:
+        """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
+        ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
+        logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
+        captured once into a hipGraph and replayed per token."""
+        B, T0 = idx.shape
+        total = T0 + max_new_tokens
+        if max_new_tokens < 0 or T0 < 1 or total > self.cfg.max_seq:
+            raise ValueError(f"prompt {T0} + max_new_tokens {max_new_tokens} must fit max_seq {self.cfg.max_seq}")
+        if max_new_tokens == 0:
+            return idx.clone()
+        if graph and not idx.is_cuda:
+            raise ValueError("generate(graph=True) needs GPU tensors")
+        cache = self.new_cache(B, total, device=idx.device)
+        logits = self.prefill(idx, cache)
+        step = lambda t: self.decode_step(t, cache)  # noqa: E731
+        if graph and max_new_tokens > 1:
+            step = self.graphed_decode_step(cache)
+        out = [idx]
+        for i in range(max_new_tokens):
+            nxt = _sample(logits, temperature, top_k, generator)
+            out.append(nxt.view(B, 1))
+            if i + 1 < max_new_tokens:
+                logits = step(nxt)
+        return torch.cat(out, 1)
+
+    def graphed_decode_step(self, cache) -> "_GraphedDecodeStep":
+        """``decode_step`` on ``cache`` captured once into a hipGraph (its attention grid sized for the
+        whole capacity); each call replays it on a new token ``[B]`` and returns the logits, valid until
+        the next call. The position lives in the device-side ``cache.lens``, which the replay advances;
+        the host-side bound follows, and a call with no free cache row raises like ``decode_step``. The
+        cache needs one free row for the warm-up step, whose effect on ``lens`` is undone here."""
+        if cache._bound + 1 > cache.capacity:
+            raise ValueError("graphed_decode_step needs a free cache row")
+        cache.pin_bound()
+        saved, bound = cache.lens.clone(), cache._bound
+
+        def step(t):  # warm-up and capture both start from the same host bound
+            cache._bound = bound
+            return self.decode_step(t, cache)
+
+        g = ops.GraphedCallable(step, torch.zeros(cache.B, dtype=torch.long, device=cache.lens.device), warmup=1)
+        torch.cuda.current_stream().synchronize()
+        cache.lens.copy_(saved)
+        cache._bound = bound
+        return _GraphedDecodeStep(g, cache)
 
     def flops_per_token(self, seq: int) -> float:
         """Training FLOPs/token (fwd+bwd = 3x fwd): dense matmuls + attention scores."""

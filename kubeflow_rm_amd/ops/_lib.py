@@ -87,6 +87,16 @@ _SIGNATURES = {
     "kfamd_attn_bwd_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
     "kfamd_attn_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                     c_int, c_float, c_int, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_decode_split_keys": (c_int, []),
+    "kfamd_attn_decode_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
+    "kfamd_attn_decode_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float,
+                                       ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
+                                     ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_gemm_nt_skinny_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
+                                          c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_bf16_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,
+                                               c_ll, c_ll, c_float, c_int, c_vp]),
     "kfamd_build_info": (ctypes.c_char_p, []),
 }
 

@@ -1,0 +1,197 @@
+"""KV-cache decode: the cache, the append and single-query attention (``kernels/attn_decode_bf16.hip``).
+
+``KVCache`` holds the per-layer K / V tensors ``[B, H, capacity, D]`` and the device-side ``lens``
+(``int32 [B]``): every kernel reads positions from ``lens``, so a decode step captured into a hipGraph
+replays while the position advances (``lens.add_(1)`` is part of the step). ``t_bound`` is the host-side
+upper bound of ``lens`` that sizes the attention grid; a step meant for capture sets it to the capacity.
+
+``kv_append(qkv, cache, layer)`` copies the K and V rows of a fused QKV activation ``[B, T, 3*H*D]``
+to rows ``lens[b] .. lens[b]+T-1``; ``attention_decode(q, cache, layer)`` attends one query row per
+head over keys ``0 .. lens[b]-1`` (or an explicit ``lens`` / ``t_bound``). Neither advances ``lens``. A
+model step that appends T rows passes its attention ``lens=cache.lens_after(T)`` (a device tensor
+``lens + T``: the rows it just appended are attended too) with ``t_bound=cache.bound_after(T)``, and
+calls ``cache.advance(T)`` (``lens.add_(T)``) once, after the last layer. The cache keeps no record of
+a step in flight.
+
+On CPU tensors the same functions run plain torch (index copy, masked fp32 SDPA): the CPU model path
+and its tests. On a GPU there is no fallback: a shape the kernels reject raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+HEAD_DIMS = (64, 128)
+_split_keys: int | None = None
+
+
+def split_keys() -> int:
+    """Keys per split of the decode attention kernel (``SPLIT_KEYS``)."""
+    global _split_keys
+    if _split_keys is None:
+        _split_keys = int(_lib.lib().kfamd_attn_decode_split_keys())
+    return _split_keys
+
+
+def __getattr__(name):  # SPLIT_KEYS: read from the library on first use (importing needs no GPU)
+    if name == "SPLIT_KEYS":
+        return split_keys()
+    raise AttributeError(name)
+
+
+def _stream_ptr(t: torch.Tensor) -> int:
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _native(t: torch.Tensor) -> bool:
+    """GPU tensors run the HIP kernels unless ops.torch_reference() is active (the A/B baseline)."""
+    from . import native_enabled
+    return t.is_cuda and native_enabled()
+
+
+def _ll(*vals) -> "ctypes.Array":
+    return (ctypes.c_longlong * len(vals))(*(int(v) for v in vals))
+
+
+class KVCache:
+    """Per-layer K / V ``[B, H, capacity, D]``, device ``lens`` (int32 [B]), host ``t_bound``."""
+
+    def __init__(self, n_layers: int, B: int, H: int, D: int, capacity: int, device=None,
+                 dtype: torch.dtype = torch.bfloat16):
+        if min(n_layers, B, H, D, capacity) < 1:
+            raise ValueError("KVCache: positive sizes expected")
+        self.n_layers, self.B, self.H, self.D, self.capacity = n_layers, B, H, D, capacity
+        self.device, self.dtype = torch.device(device if device is not None else "cpu"), dtype
+        self.k = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+        self.v = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+        self.lens = torch.zeros(B, device=self.device, dtype=torch.int32)
+        self._lens_after = torch.zeros(B, device=self.device, dtype=torch.int32)  # lens_after()'s buffer
+        self._bound, self._pinned = 0, False
+        self.workspace = None
+        if self.device.type == "cuda" and dtype == torch.bfloat16 and D in HEAD_DIMS:  # the kernels' shapes
+            nbytes = _lib.lib().kfamd_attn_decode_workspace(B, H, D, capacity)
+            self.workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
+
+    @property
+    def t_bound(self) -> int:
+        """Host-side upper bound of every ``lens[b]`` (sizes the attention grid)."""
+        return self.capacity if self._pinned else self._bound
+
+    def lens_after(self, T: int = 1) -> torch.Tensor:
+        """``lens + T`` on the device (one buffer per cache, capturable): the lengths a step that
+        appends T rows per batch row hands to its attention."""
+        return torch.add(self.lens, T, out=self._lens_after)
+
+    def bound_after(self, T: int = 1) -> int:
+        """The host bound that goes with ``lens_after(T)``."""
+        return self.capacity if self._pinned else min(self._bound + T, self.capacity)
+
+    def advance(self, T: int = 1) -> None:
+        """``lens += T`` on the device (capturable); the host bound follows."""
+        self.lens.add_(T)
+        self._bound = min(self._bound + T, self.capacity)
+
+    def set_lens(self, lens) -> None:
+        """Set per-row lengths from the host (a sync: not for a captured step)."""
+        vals = [int(x) for x in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+        if len(vals) != self.B or min(vals) < 0 or max(vals) > self.capacity:
+            raise ValueError(f"set_lens: {self.B} lengths in 0..{self.capacity} expected")
+        self.lens.copy_(torch.tensor(vals, dtype=torch.int32))
+        self._bound = max(vals)
+
+    def pin_bound(self) -> None:
+        """Size the attention grid for the whole capacity: what a step captured once must use."""
+        self._pinned = True
+
+    def reset(self) -> None:
+        self.lens.zero_()
+        self._bound = 0
+
+
+def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
+    """K, V rows of the fused QKV activation ``[B, T, 3*H*D]`` -> cache rows ``lens[b] .. lens[b]+T-1``
+    (rows at or beyond the capacity are dropped). ``lens`` is not advanced."""
+    B, H, D = cache.B, cache.H, cache.D
+    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != 3 * H * D:
+        raise ValueError(f"kv_append: qkv [B={B}, T, {3 * H * D}] expected, got {tuple(qkv.shape)}")
+    T = qkv.shape[1]
+    k, v = cache.k[layer], cache.v[layer]
+    if not _native(qkv):
+        x = qkv.reshape(B, T, 3, H, D)
+        rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=qkv.device).unsqueeze(0)  # [B, T]
+        if cache._bound + T <= cache.capacity:  # no row can fall off the end: one index_put per tensor
+            bidx = torch.arange(B, device=qkv.device).unsqueeze(1).expand(B, T)
+            k[bidx, :, rows] = x[:, :, 1].to(k.dtype)
+            v[bidx, :, rows] = x[:, :, 2].to(v.dtype)
+            return
+        for b in range(B):
+            keep = rows[b] < cache.capacity
+            k[b].index_copy_(1, rows[b][keep], x[b, keep, 1].transpose(0, 1).to(k.dtype))
+            v[b].index_copy_(1, rows[b][keep], x[b, keep, 2].transpose(0, 1).to(v.dtype))
+        return
+    if qkv.dtype != torch.bfloat16 or qkv.stride(2) != 1:
+        raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
+    rc = _lib.lib().kfamd_kv_append_bf16(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), cache.lens.data_ptr(), B, T, H, D,
+                                         cache.capacity, qkv.stride(0), qkv.stride(1),
+                                         _ll(*k.stride()[:3], *v.stride()[:3]), _stream_ptr(qkv))
+    _lib.check(rc, f"kv_append[B={B} T={T} H={H} D={D}]")
+
+
+def _attention_decode_torch(q, k, v, lens, scale):
+    """Masked SDPA of one query row over keys 0 .. lens[b]-1: fp32 on the CPU, the tensors' own dtype on
+    a GPU (the torch_reference() baseline reads the cache as it is stored)."""
+    Tcap = k.shape[2]
+    mask = torch.arange(Tcap, device=q.device).view(1, 1, 1, Tcap) < lens.view(-1, 1, 1, 1)
+    if not q.is_cuda:
+        q, k, v = q.float(), k.float(), v.float()
+    return F.scaled_dot_product_attention(q.unsqueeze(2), k, v, attn_mask=mask, scale=scale).squeeze(2)
+
+
+def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
+                     out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
+                     t_bound: int | None = None, return_lse: bool = False):
+    """softmax(scale * q k^T) v for one query row per head: q ``[B, H, D]`` (any b / h strides, e.g. a
+    view of the fused QKV output), keys ``0 .. lens[b]-1`` of ``cache`` layer ``layer``. ``out``:
+    optional ``[B, H, D]`` view to write (e.g. of a ``[B, 1, H*D]`` buffer). ``lens`` / ``t_bound``
+    default to the cache's."""
+    B, H, D = cache.B, cache.H, cache.D
+    if tuple(q.shape) != (B, H, D):
+        raise ValueError(f"attention_decode: q [{B}, {H}, {D}] expected, got {tuple(q.shape)}")
+    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    lens = cache.lens if lens is None else lens
+    t_bound = cache.t_bound if t_bound is None else int(t_bound)
+    k, v = cache.k[layer], cache.v[layer]
+    if not _native(q):
+        o = _attention_decode_torch(q, k, v, lens, scale).to(q.dtype)
+        if out is not None:
+            out.copy_(o)
+            o = out
+        if return_lse:
+            s = (q.float().unsqueeze(2) @ k.float().transpose(-1, -2)).squeeze(2) * scale
+            dead = torch.arange(k.shape[2], device=q.device).view(1, 1, -1) >= lens.view(-1, 1, 1)
+            return o, torch.logsumexp(s.masked_fill(dead, float("-inf")), -1)
+        return o
+    if D not in HEAD_DIMS:
+        raise ValueError(f"attention_decode: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
+    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype != torch.bfloat16:
+        raise ValueError("attention_decode: bf16 q (contiguous head dim) and a bf16 cache expected")
+    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
+        raise ValueError("attention_decode: lens must be a device int32 [B] tensor")
+    if not 1 <= t_bound <= cache.capacity:
+        raise ValueError(f"attention_decode: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
+    if out is None:
+        out = torch.empty(B, H, D, device=q.device, dtype=q.dtype)
+    elif tuple(out.shape) != (B, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
+        raise ValueError(f"attention_decode: out must be a bf16 GPU [{B}, {H}, {D}] view with a contiguous head dim")
+    lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
+    rc = _lib.lib().kfamd_attn_decode_bf16(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), lens.data_ptr(), out.data_ptr(),
+        lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
+        _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1)), _stream_ptr(q))
+    _lib.check(rc, f"attention_decode[B={B} H={H} D={D} t_bound={t_bound}]")
+    return (out, lse) if return_lse else out

@@ -15,6 +15,9 @@ from . import _lib
 
 ACTS = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu": 2, "silu": 3}
 VARIANTS = {"auto": 0, "fast": 1, "generic": 2, "pipe": 3, "pipe_sched": 4, "w4": 6, "w4s": 9}
+# the M <= 16 weight-streaming kernel: "skinny" picks VALU / MFMA by M, the other two force one (bench)
+SKINNY_PATHS = {"skinny": 0, "skinny_valu": 1, "skinny_mfma": 2}
+SKINNY_MAX_M = 16
 
 
 def _stream_ptr(t: torch.Tensor) -> int:
@@ -144,6 +147,22 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias: torch.Tensor | None = Non
         _check_operand(bias, "bias")
         if bias.numel() != N or not bias.is_contiguous():
             raise ValueError("bias must be a contiguous [N] tensor")
+    if variant in SKINNY_PATHS:
+        # weight-streaming decode kernel (kernels/gemm_skinny_bf16.hip): outside its contract it raises
+        if batched or not 1 <= M <= SKINNY_MAX_M or K % 8:
+            raise ValueError(f"gemm_nt variant={variant!r}: non-batched, 1 <= M <= {SKINNY_MAX_M} and K % 8 == 0 "
+                             f"expected, got M={M} K={K} batched={batched}")
+        r_ptr, ldr = None, 0
+        if residual is not None:
+            _check_operand(residual, "residual")
+            r2 = residual.reshape(M, N)
+            r_ptr, ldr = r2.data_ptr(), r2.stride(0)
+        rc = _lib.lib().kfamd_gemm_nt_skinny_bf16_path(
+            SKINNY_PATHS[variant], a3.data_ptr(), b.data_ptr(), c3.data_ptr(),
+            bias.data_ptr() if bias is not None else None, r_ptr, M, N, K, lda, ldb, ldc, ldr, float(alpha),
+            ACTS[act], _stream_ptr(a))
+        _lib.check(rc, f"gemm_nt[skinny {M}x{N}x{K}]")
+        return out
     if (variant == "auto" and not _w4_nt_shape(M, N, K)
             and ((M >= 128 and N >= 128) or flops(M, N, K, batch) >= _PAD_MIN_FLOPS)):
         return _gemm_nt_padded(a3, b, bias, residual, alpha, act, out, batched, batch, M, N, K)

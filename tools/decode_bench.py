@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Decode benchmark: the M <= 16 weight-streaming GEMM, single-query attention and GPT.generate.
+
+    python tools/decode_bench.py [--out decode_bench.json] [--steps gemm,attn,e2e] [--quick]
+
+The parent process never touches the GPU: every step runs as a child process of its own under a time
+limit, and a step that fails or times out ends the run (nothing more is started on the GPU).
+
+  gemm  gemm_nt(variant="skinny") (and each arithmetic pattern forced) against variant="auto" — the
+        route these shapes took before — at M in {1, 2, 4, 8, 16} x the gpt-1b projection shapes. The two are
+        interleaved block by block; medians over the blocks; the weights rotate through copies that
+        together exceed the 256 MiB last-level cache, as a model's layers do.
+  attn  ops.attention_decode against torch SDPA (bf16, masked) on the same cache: B*H in {16, 128,
+        256}, D = 128, lens in {128, 2048, 4096}.
+  e2e   gpt-small and gpt-1b, B in {1, 8, 16}, prompt 2048 - 128, 128 new tokens: native eager, native
+        graphed and the torch-reference cached path of the same model, interleaved; ms/token and
+        (weights + KV bytes read per token) / time as a fraction of the 6.29 TB/s copy roof.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+ROOF = 6.29e12
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420}
+GEMM_MS = (1, 2, 4, 8, 16)  # 2 and 4: where the VALU / MFMA cut-over of the skinny kernel is decided
+GEMM_SHAPES = [(6144, 2048), (2048, 2048), (8192, 2048), (2048, 8192), (32000, 2048)]  # (N, K)
+
+
+def _time_blocks(fns: dict, blocks: int, iters: int):
+    """Interleaved blocks: for each block, each candidate runs `iters` calls between two events."""
+    import torch
+    for f in fns.values():  # warm-up
+        for i in range(3):
+            f(i)
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for b in range(blocks):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(iters):
+                f(b * iters + i)
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3 / iters)  # us per call
+    return {k: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for k, v in times.items()}
+
+
+def step_gemm(quick: bool):
+    import torch
+    from kubeflow_rm_amd.ops import gemm_nt
+    rows = []
+    for N, K in GEMM_SHAPES:
+        wbytes = N * K * 2
+        ncopy = max(2, -(-(512 << 20) // wbytes)) if not quick else 2
+        ws = [torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16) for _ in range(ncopy)]
+        bias = torch.randn(N, device="cuda").to(torch.bfloat16)
+        for M in GEMM_MS:
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            variants = ["auto", "skinny", "skinny_mfma"] + (["skinny_valu"] if M <= 8 else [])
+            fns = {v: (lambda i, v=v: gemm_nt(a, ws[i % ncopy], bias=bias, out=out, variant=v)) for v in variants}
+            r = _time_blocks(fns, blocks=5 if quick else 7, iters=ncopy)
+            row = {"M": M, "N": N, "K": K, "weight_copies": ncopy}
+            for v, t in r.items():
+                row[v] = {**t, "weight_GBps": wbytes / t["median_us"] / 1e3}
+            row["auto_over_skinny"] = r["auto"]["median_us"] / r["skinny"]["median_us"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def step_attn(quick: bool):
+    import torch
+    import torch.nn.functional as F
+    from kubeflow_rm_amd import ops
+    rows = []
+    D, cap = 128, 4096
+    for BH in (16, 128, 256):
+        B, H = BH // 16, 16
+        ncopy = 1 if quick else max(1, min(4, (512 << 20) // (2 * B * H * cap * D * 2)))
+        cache = ops.KVCache(ncopy, B, H, D, cap, device="cuda")
+        for t in (*cache.k, *cache.v):
+            t.normal_()
+        q = torch.randn(B, H, D, device="cuda").to(torch.bfloat16)
+        out = torch.empty(B, H, D, device="cuda", dtype=torch.bfloat16)
+        for n in (128, 2048, 4096):
+            cache.set_lens([n] * B)
+            mask = torch.arange(cap, device="cuda").view(1, 1, 1, cap) < n
+
+            def native(i):
+                ops.attention_decode(q, cache, i % ncopy, out=out, t_bound=n)
+
+            def sdpa_sliced(i):  # the best case for torch: the host knows the length and slices
+                F.scaled_dot_product_attention(q.unsqueeze(2), cache.k[i % ncopy][:, :, :n], cache.v[i % ncopy][:, :, :n])
+
+            def sdpa_masked(i):  # what a graph-capturable torch step has to do: mask the whole capacity
+                F.scaled_dot_product_attention(q.unsqueeze(2), cache.k[i % ncopy], cache.v[i % ncopy], attn_mask=mask)
+
+            r = _time_blocks({"native": native, "sdpa_sliced": sdpa_sliced, "sdpa_masked": sdpa_masked},
+                             blocks=5 if quick else 7, iters=20)
+            kv = 2 * B * H * n * D * 2
+            row = {"B": B, "H": H, "D": D, "len": n, "kv_bytes": kv, **r,
+                   "native_KV_GBps": kv / r["native"]["median_us"] / 1e3,
+                   "sdpa_sliced_over_native": r["sdpa_sliced"]["median_us"] / r["native"]["median_us"]}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def step_e2e(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.models import CONFIGS, GPT, num_params
+    rows = []
+    prompt, new = 2048 - 128, 128
+    for name in (("gpt-small",) if quick else ("gpt-small", "gpt-1b")):
+        cfg = CONFIGS[name]
+        model = GPT(cfg, device="cuda").eval()
+        wbytes = num_params(model) * 2 - cfg.max_seq * cfg.d_model * 2  # every weight once; pos: one row
+        for B in ((1, 8) if quick else (1, 8, 16)):
+            idx = torch.randint(0, cfg.vocab_size, (B, prompt), device="cuda")
+            toks = torch.randint(0, cfg.vocab_size, (new, B), device="cuda")
+
+            def run(mode):
+                cache = model.new_cache(B, prompt + new)
+                model.prefill(idx, cache)
+                step = (lambda t: model.decode_step(t, cache)) if mode != "graph" else model.graphed_decode_step(cache)
+                step(toks[0])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(1, new):
+                    step(toks[i])
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+            def run_ref():
+                with ops.torch_reference():
+                    return run("eager")
+
+            res = {"native_eager": [], "native_graph": [], "torch_reference": []}
+            for _ in range(3 if quick else 5):  # interleaved
+                res["native_eager"].append(run("eager"))
+                res["native_graph"].append(run("graph"))
+                res["torch_reference"].append(run_ref())
+            kv = 2 * cfg.n_layers * B * cfg.d_model * (prompt + new / 2) * 2
+            row = {"model": name, "B": B, "prompt": prompt, "new": new, "bytes_per_token": wbytes + kv}
+            for k, v in res.items():
+                med = statistics.median(v)
+                row[k] = {"ms_per_token": med, "min": min(v), "max": max(v),
+                          "roof_fraction": (wbytes + kv) / (med * 1e-3) / ROOF}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del model
+        torch.cuda.empty_cache()
+    return rows
+
+
+STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default="decode_bench.json")
+    ap.add_argument("--steps", default="gemm,attn,e2e")
+    ap.add_argument("--quick", action="store_true", help="fewer blocks / shapes (a smoke run of the tool)")
+    ap.add_argument("--child", choices=sorted(STEPS), help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:  # one step, in a process of its own
+        Path(args.out).write_text(json.dumps(STEPS[args.child](args.quick)))
+        return 0
+    result = {}
+    part = Path(args.out + ".part")
+    for name in args.steps.split(","):
+        cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S[name]), sys.executable, str(Path(__file__).resolve()),
+               "--child", name, "--out", str(part), *(["--quick"] if args.quick else [])]
+        rc = subprocess.run(cmd).returncode  # the child's rows stream to this process's stdout
+        if rc != 0:
+            print(f"step {name} ended with status {rc}: stopping", file=sys.stderr)
+            Path(args.out).write_text(json.dumps(result, indent=1))
+            return rc
+        result[name] = json.loads(part.read_text())
+        part.unlink()
+        Path(args.out).write_text(json.dumps(result, indent=1))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
