@@ -225,6 +225,20 @@ long long kfamd_attn_decode_workspace(int B, int H, int D, int t_bound);
 int kfamd_attn_decode_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
                            float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
                            const long long* strides, void* stream);
+// Multi-query attention over the KV cache (attn_extend_bf16.hip): Tq (1 .. 16) new rows per (b, h), already
+// appended to the cache; K / V are streamed once per (b, h, split) for up to 8 rows (two split launches
+// for Tq = 9 .. 16).
+//   q, o [B][Tq][H][D] (element strides b, t, h; head dim contiguous), caches as for decode.
+//   strides = {qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh}.
+//   lens: DEVICE int32 [B], the number of keys INCLUDING the Tq new rows (clamped to [0, t_bound]); query
+//   row i attends keys 0 .. lens[b] - Tq + i. A row whose limit is negative (lens[b] < Tq) writes zeros
+//   and lse = -inf. lse: optional f32 [B][Tq][H]. ws: kfamd_attn_extend_workspace bytes (Tq times
+//   decode's; unused with one split). Return codes as kfamd_attn_decode_bf16, plus KFAMD_EINVAL for Tq
+//   outside 1 .. 16 and for a missing workspace with more than one split.
+long long kfamd_attn_extend_workspace(int B, int H, int D, int Tq, int t_bound);
+int kfamd_attn_extend_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                           float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
+                           const long long* strides, void* stream);
 // K and V rows of a fused QKV activation [B][T][3][H][D] (element strides qb, qt; [3][H][D] dense) into
 // the caches at rows pos[b] .. pos[b]+T-1 (pos: device int32 [B], not advanced). cache_strides = {kb, kh,
 // kt, vb, vh, vt}. Rows at or beyond Tcap are dropped.

@@ -290,6 +290,10 @@ class GPT(torch.nn.Module):
         # profiles/decode (every gpt-1b projection shape at M = 1, 2, 4, 8, 16: 2.8x to 28x)
         return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual, variant="skinny")
 
+    def _auto(self, x, w, bias=None, act="none", residual=None):
+        # more than 16 rows (extend with B * T > 16): the "auto" route, as prefill
+        return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual)
+
     @torch.no_grad()
     def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
         """One new token ``tok [B]`` per row against ``cache``; logits ``[B, vocab]``. Advances the cache."""
@@ -325,16 +329,138 @@ class GPT(torch.nn.Module):
         return F.linear(self.ln_f(x), self.tok)
 
     @torch.no_grad()
+    def extend(self, idx: torch.Tensor, cache, last_only: bool = False) -> torch.Tensor:
+        """Append ``idx [B, T]`` (T >= 1 tokens per row) to ``cache`` in any state, empty included; logits
+        ``[B, T, vocab]`` of every new position (``[B, vocab]`` of the last one with ``last_only``).
+        Advances the cache by T. On the GPU a step of up to 16 tokens runs the decode kernels with
+        ``ops.attention_extend`` (K / V read once per 8 new rows; the weight-streaming GEMM while
+        B * T <= 16); longer inputs run in chunks of 16. Like ``decode_step`` it reads the position
+        from the device-side ``cache.lens`` only, so a fixed T <= 16 can be captured into a hipGraph."""
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise ValueError(f"extend: idx [B, T >= 1] expected, got {tuple(idx.shape)}")
+        B, T = idx.shape
+        self._check_cache(cache, B, T)
+        native = self._native_decode(self.tok)
+        R = ops.decode.MAX_EXTEND_ROWS
+        outs = []
+        for t0 in range(0, T, R):
+            final = t0 + R >= T
+            if last_only and not final:
+                self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none")
+            else:
+                outs.append(self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="last" if last_only else "all"))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+
+    def _extend_chunk(self, idx, cache, native: bool, head: str):
+        """One extend step of T <= 16 tokens per row; ``head``: LM head on "all" rows, the "last", or "none"."""
+        B, T = idx.shape
+        c = self.cfg
+        pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
+        x = F.embedding(idx, self.tok) + F.embedding(pos, self.pos)  # [B, T, d_model]
+        # the step's attention sees the rows it appends: lens + T, computed on the device
+        att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T)}
+        lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
+        if native:
+            x = x.reshape(B * T, c.d_model)
+        for li, blk in enumerate(self.blocks):
+            h, hd = blk.local_heads, c.head_dim
+            if native:
+                y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
+                qkv = lin(y, blk.qkv.weight, blk.qkv.bias).view(B, T, 3 * h * hd)
+                ops.kv_append(qkv, cache, li)
+                a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
+                ops.attention_extend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, out=a.view(B, T, h, hd), **att)
+                x = lin(a.view(B * T, h * hd), blk.proj.weight, blk.proj.bias, residual=x)
+                y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
+                y = lin(y, blk.fc1.weight, blk.fc1.bias, act=blk.fc1.act)
+                x = lin(y, blk.fc2.weight, blk.fc2.bias, residual=x)
+            else:
+                qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
+                ops.kv_append(qkv, cache, li)  # torch ops: CPU tensors / torch_reference()
+                a = ops.attention_extend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, **att).reshape(B, T, h * hd)
+                x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
+                y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
+                x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
+        cache.advance(T)
+        if head == "none":
+            return None
+        x = x.view(B, T, c.d_model)
+        if head == "last":
+            x = x[:, -1].contiguous()  # [B, d_model]
+        if not native:
+            return F.linear(self.ln_f(x), self.tok)
+        rows = x.reshape(-1, c.d_model)
+        head_lin = self._skinny if rows.shape[0] <= ops.gemm.SKINNY_MAX_M else self._auto
+        logits = head_lin(ops.layer_norm_fwd(rows, self.ln_f.weight, self.ln_f.bias)[0], self.tok)
+        return logits.view(*x.shape[:-1], c.vocab_size)
+
+    def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int):
+        """Greedy draft-and-verify for one sequence: per round the draft proposes up to ``lookahead``
+        tokens (``decode_step`` on its own cache), the target scores ``[last accepted, proposals...]`` in
+        ONE ``extend`` and keeps the longest prefix that equals its own argmax, plus its own next token
+        (the correction at the first mismatch, or the extra token after a full acceptance)."""
+        T0 = idx.shape[1]
+        total = T0 + max_new_tokens
+        tc = self.new_cache(1, total, device=idx.device)
+        dc = draft.new_cache(1, total, device=idx.device)
+        if T0 > 1:  # both caches hold the prompt but its last token: every new token comes from a round
+            self.prefill(idx[:, :-1], tc)
+            draft.prefill(idx[:, :-1], dc)
+        seq = idx[0].tolist()
+        stats = {"target_steps": 0, "proposed": 0, "accepted": 0}
+        while len(seq) < total:
+            K = min(lookahead, total - len(seq) - 1)  # a round emits at most K + 1 tokens
+            last = torch.tensor([seq[-1]], dtype=idx.dtype, device=idx.device)
+            props, tok = [], last
+            for _ in range(K):
+                tok = draft.decode_step(tok, dc).argmax(-1)
+                props.append(tok)
+            row = torch.cat([last, *props]).view(1, K + 1)
+            want = self.extend(row, tc).argmax(-1)[0].tolist()  # the target's token after each row
+            prop = row[0, 1:].tolist()
+            n = 0
+            while n < K and prop[n] == want[n]:
+                n += 1
+            seq += prop[:n] + [want[n]]
+            tc.rewind(K - n)  # the cache keeps [last, accepted proposals]
+            if K > 0 and n == K:
+                draft.decode_step(props[-1], dc)  # the draft has not seen its own last proposal yet
+            elif K > 0:
+                dc.rewind(K - 1 - n)  # the draft's cache holds [last, proposals but the final one]
+            stats["target_steps"] += 1
+            stats["proposed"] += K
+            stats["accepted"] += n
+        return torch.tensor([seq], dtype=idx.dtype, device=idx.device), stats
+
+    @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
-                 generator: torch.Generator | None = None, graph: bool = False) -> torch.Tensor:
+                 generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
+                 lookahead: int = 4, return_stats: bool = False):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
-        captured once into a hipGraph and replayed per token."""
+        captured once into a hipGraph and replayed per token.
+
+        ``draft`` (a ``GPT`` with the same vocabulary): greedy draft-and-verify decoding, ``lookahead``
+        proposals per target ``extend``; greedy only, B = 1, no ``graph``. ``return_stats`` then also
+        returns ``{"target_steps", "proposed", "accepted"}``."""
         B, T0 = idx.shape
         total = T0 + max_new_tokens
         if max_new_tokens < 0 or T0 < 1 or total > self.cfg.max_seq:
             raise ValueError(f"prompt {T0} + max_new_tokens {max_new_tokens} must fit max_seq {self.cfg.max_seq}")
+        if draft is not None:
+            if not (temperature == 0 or top_k == 1) or B != 1 or graph:
+                raise ValueError("generate(draft=...): greedy (temperature == 0 or top_k == 1), B = 1 and graph=False "
+                                 "expected")
+            if not isinstance(draft, GPT) or draft.cfg.vocab_size != self.cfg.vocab_size or lookahead < 1:
+                raise ValueError("generate(draft=...): a GPT with the same vocabulary and lookahead >= 1 expected")
+            if total > draft.cfg.max_seq:
+                raise ValueError(f"prompt + max_new_tokens must fit the draft's max_seq {draft.cfg.max_seq}")
+            out, stats = ((idx.clone(), {"target_steps": 0, "proposed": 0, "accepted": 0}) if max_new_tokens == 0
+                          else self._generate_draft(idx, max_new_tokens, draft, int(lookahead)))
+            return (out, stats) if return_stats else out
+        if return_stats:
+            raise ValueError("generate(return_stats=True) reports draft decoding: pass draft=")
         if max_new_tokens == 0:
             return idx.clone()
         if graph and not idx.is_cuda:

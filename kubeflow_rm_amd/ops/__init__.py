@@ -7,7 +7,7 @@ from .attention import attention_qkv, attn_block, flash_attention, split_heads  
 from .attention import supported as attention_supported  # noqa: F401
 from .allreduce import OneShotAllReduce  # noqa: F401
 from .graph import GraphedCallable  # noqa: F401
-from .decode import KVCache, attention_decode, kv_append  # noqa: F401
+from .decode import KVCache, attention_decode, attention_extend, kv_append  # noqa: F401
 from . import decode  # noqa: F401
 
 

@@ -91,6 +91,9 @@ _SIGNATURES = {
     "kfamd_attn_decode_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
     "kfamd_attn_decode_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float,
                                        ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_extend_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                       c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
                                      ctypes.POINTER(c_ll), c_vp]),
     "kfamd_gemm_nt_skinny_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,

@@ -13,6 +13,10 @@ model step that appends T rows passes its attention ``lens=cache.lens_after(T)``
 calls ``cache.advance(T)`` (``lens.add_(T)``) once, after the last layer. The cache keeps no record of
 a step in flight.
 
+``attention_extend(q, cache, layer)`` is the multi-token form (``kernels/attn_extend_bf16.hip``): T <= 16
+new query rows per head, already appended, each attending the cache up to its own row; with
+``KVCache.rewind(n)`` (drop the last n rows) it carries ``GPT.extend`` and draft-and-verify decoding.
+
 On CPU tensors the same functions run plain torch (index copy, masked fp32 SDPA): the CPU model path
 and its tests. On a GPU there is no fallback: a shape the kernels reject raises.
 """
@@ -27,6 +31,7 @@ import torch.nn.functional as F
 from . import _lib
 
 HEAD_DIMS = (64, 128)
+MAX_EXTEND_ROWS = 16  # query rows per attention_extend call
 _split_keys: int | None = None
 
 
@@ -73,6 +78,7 @@ class KVCache:
         self._lens_after = torch.zeros(B, device=self.device, dtype=torch.int32)  # lens_after()'s buffer
         self._bound, self._pinned = 0, False
         self.workspace = None
+        self.extend_workspace = None  # attention_extend's, allocated on its first use
         if self.device.type == "cuda" and dtype == torch.bfloat16 and D in HEAD_DIMS:  # the kernels' shapes
             nbytes = _lib.lib().kfamd_attn_decode_workspace(B, H, D, capacity)
             self.workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
@@ -108,9 +114,29 @@ class KVCache:
         """Size the attention grid for the whole capacity: what a step captured once must use."""
         self._pinned = True
 
+    def rewind(self, n: int) -> None:
+        """``lens -= n`` on the device, clamped at 0 (capturable); the host bound follows (a pinned bound
+        stays pinned). The rows beyond ``lens`` stay in memory: dead by the kernels' contract, overwritten
+        by the next append."""
+        if n < 0:
+            raise ValueError("rewind: n >= 0 expected")
+        self.lens.sub_(n).clamp_(min=0)
+        self._bound = max(self._bound - n, 0)
+
     def reset(self) -> None:
         self.lens.zero_()
         self._bound = 0
+
+    def _extend_ws(self) -> torch.Tensor:
+        """attention_extend's split workspace: MAX_EXTEND_ROWS times decode's, allocated on first use
+        (outside any capture) and kept."""
+        if self.extend_workspace is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("attention_extend: run one step before capturing (the workspace is allocated "
+                                   "on first use)")
+            nbytes = _lib.lib().kfamd_attn_extend_workspace(self.B, self.H, self.D, MAX_EXTEND_ROWS, self.capacity)
+            self.extend_workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
+        return self.extend_workspace
 
 
 def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
@@ -194,4 +220,69 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
         _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1)), _stream_ptr(q))
     _lib.check(rc, f"attention_decode[B={B} H={H} D={D} t_bound={t_bound}]")
+    return (out, lse) if return_lse else out
+
+
+def _attention_extend_torch(q, k, v, lens, scale):
+    """Masked fp32 SDPA of T query rows per head, row i over keys 0 .. lens[b]-T+i. A row with no key
+    gives zeros and lse = -inf. Returns (o [B, T, H, D] fp32, lse [B, T, H])."""
+    T, Tcap = q.shape[1], k.shape[2]
+    limit = lens.view(-1, 1).long() - T + torch.arange(T, device=q.device).view(1, T)  # last visible key
+    mask = torch.arange(Tcap, device=q.device).view(1, 1, 1, Tcap) <= limit.view(-1, 1, T, 1)  # [B, 1, T, Tcap]
+    s = (q.transpose(1, 2).float() @ k.float().transpose(-1, -2)) * scale  # [B, H, T, Tcap]
+    s = s.masked_fill(~mask, float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse.masked_fill(lse == float("-inf"), 0.0).unsqueeze(-1))  # a dead row: all zeros
+    seen = mask.any(2).view(-1, 1, Tcap, 1)  # the cache beyond lens may hold NaN: those V rows are zeroed
+    o = p @ torch.where(seen, v.float(), torch.zeros((), device=q.device))
+    return o.transpose(1, 2), lse.transpose(1, 2)
+
+
+def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
+                     out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
+                     t_bound: int | None = None, return_lse: bool = False):
+    """softmax(scale * q k^T) v for T new query rows per head (1 <= T <= 16 on a GPU): q ``[B, T, H, D]``
+    (any b / t / h strides, e.g. ``qkv.view(B, T, 3, H, D)[:, :, 0]``), already appended to ``cache``
+    layer ``layer``. ``lens[b]`` counts the keys INCLUDING the T new rows; row i attends keys
+    ``0 .. lens[b] - T + i`` (a row whose limit is negative gives zeros, lse = -inf). ``out``: optional
+    ``[B, T, H, D]`` view to write. ``lens`` / ``t_bound`` default to the cache's. K and V are read once
+    per 8 query rows (``kernels/attn_extend_bf16.hip``)."""
+    B, H, D = cache.B, cache.H, cache.D
+    if q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (H, D):
+        raise ValueError(f"attention_extend: q [{B}, T, {H}, {D}] expected, got {tuple(q.shape)}")
+    T = q.shape[1]
+    if T < 1:
+        raise ValueError("attention_extend: at least one query row expected")
+    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    lens = cache.lens if lens is None else lens
+    t_bound = cache.t_bound if t_bound is None else int(t_bound)
+    k, v = cache.k[layer], cache.v[layer]
+    if not _native(q):
+        o, lse = _attention_extend_torch(q, k, v, lens, scale)
+        o = o.to(q.dtype)
+        if out is not None:
+            out.copy_(o)
+            o = out
+        return (o, lse) if return_lse else o
+    if T > MAX_EXTEND_ROWS:
+        raise ValueError(f"attention_extend: 1 <= T <= {MAX_EXTEND_ROWS} query rows expected on a GPU, got {T}")
+    if D not in HEAD_DIMS:
+        raise ValueError(f"attention_extend: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
+    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype != torch.bfloat16:
+        raise ValueError("attention_extend: bf16 q (contiguous head dim) and a bf16 cache expected")
+    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
+        raise ValueError("attention_extend: lens must be a device int32 [B] tensor")
+    if not 1 <= t_bound <= cache.capacity:
+        raise ValueError(f"attention_extend: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
+    if out is None:
+        out = torch.empty(B, T, H, D, device=q.device, dtype=q.dtype)
+    elif tuple(out.shape) != (B, T, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
+        raise ValueError(f"attention_extend: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
+                         "head dim")
+    lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
+    rc = _lib.lib().kfamd_attn_extend_bf16(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), lens.data_ptr(), out.data_ptr(),
+        lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, H, D, T, t_bound, scale,
+        _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3]), _stream_ptr(q))
+    _lib.check(rc, f"attention_extend[B={B} T={T} H={H} D={D} t_bound={t_bound}]")
     return (out, lse) if return_lse else out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decode benchmark: the M <= 16 weight-streaming GEMM, single-query attention and GPT.generate.
 
-    python tools/decode_bench.py [--out decode_bench.json] [--steps gemm,attn,e2e] [--quick]
+    python tools/decode_bench.py [--out decode_bench.json] [--steps gemm,attn,e2e,extend] [--quick]
 
 The parent process never touches the GPU: every step runs as a child process of its own under a time
 limit, and a step that fails or times out ends the run (nothing more is started on the GPU).
@@ -15,6 +15,10 @@ limit, and a step that fails or times out ends the run (nothing more is started 
   e2e   gpt-small and gpt-1b, B in {1, 8, 16}, prompt 2048 - 128, 128 new tokens: native eager, native
         graphed and the torch-reference cached path of the same model, interleaved; ms/token and
         (weights + KV bytes read per token) / time as a fraction of the 6.29 TB/s copy roof.
+  extend  multi-token steps. Kernel: ops.attention_extend at Tq in {1, 2, 4, 8, 16} against Tq calls of
+        ops.attention_decode on the same cache (D = 128, capacity 4096, B*H in {16, 128}, lens in {128,
+        2048, 4096}; caches rotated as in attn). Model: gpt-small and gpt-1b, B = 1, position 1920:
+        one GPT.extend of T tokens against T decode_steps, each eager and as a hipGraph, interleaved.
 """
 from __future__ import annotations
 
@@ -31,7 +35,8 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 ROOF = 6.29e12
-STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420}
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600}
+EXTEND_TS = (1, 2, 4, 8, 16)
 GEMM_MS = (1, 2, 4, 8, 16)  # 2 and 4: where the VALU / MFMA cut-over of the skinny kernel is decided
 GEMM_SHAPES = [(6144, 2048), (2048, 2048), (8192, 2048), (2048, 8192), (32000, 2048)]  # (N, K)
 
@@ -166,13 +171,107 @@ def step_e2e(quick: bool):
     return rows
 
 
-STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e}
+def _extend_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    D, cap = 128, 4096
+    for BH in (16, 128):
+        B, H = BH // 16, 16
+        ncopy = 1 if quick else max(1, min(4, (512 << 20) // (2 * B * H * cap * D * 2)))
+        cache = ops.KVCache(ncopy, B, H, D, cap, device="cuda")
+        for t in (*cache.k, *cache.v):
+            t.normal_()
+        for n in (128, 2048, 4096):
+            cache.set_lens([n] * B)
+            for Tq in EXTEND_TS:
+                q = torch.randn(B, Tq, H, D, device="cuda").to(torch.bfloat16)
+                out = torch.empty(B, Tq, H, D, device="cuda", dtype=torch.bfloat16)
+
+                def extend(i):
+                    ops.attention_extend(q, cache, i % ncopy, out=out, t_bound=n)
+
+                def decode_x_tq(i):  # what a cache that grows one token at a time costs for the same rows
+                    for t in range(Tq):
+                        ops.attention_decode(q[:, t], cache, i % ncopy, out=out[:, t], t_bound=n)
+
+                r = _time_blocks({"extend": extend, "decode_x_tq": decode_x_tq}, blocks=5 if quick else 7, iters=20)
+                kv = 2 * B * H * n * D * 2
+                row = {"B": B, "H": H, "D": D, "len": n, "Tq": Tq, "kv_bytes": kv, "cache_copies": ncopy, **r,
+                       "extend_KV_GBps": kv / r["extend"]["median_us"] / 1e3,
+                       "decode_x_tq_over_extend": r["decode_x_tq"]["median_us"] / r["extend"]["median_us"]}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    return rows
+
+
+def _extend_model_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    rows = []
+    pos, cap, iters = 1920, 2048, 4  # iters * 16 rows fit between the position and the capacity
+    for name in (("gpt-small",) if quick else ("gpt-small", "gpt-1b")):
+        cfg = CONFIGS[name]
+        model = GPT(cfg, device="cuda").eval()
+        eager, pinned = model.new_cache(1, cap), model.new_cache(1, cap)  # a captured step pins the grid to the capacity
+        for c in (eager, pinned):
+            for t in (*c.k, *c.v):
+                t.normal_()
+            c.set_lens([pos])
+        dstep = model.graphed_decode_step(pinned)
+        for T in EXTEND_TS:
+            toks = torch.randint(0, cfg.vocab_size, (1, T), device="cuda")
+            pinned.set_lens([pos])
+            gstep = ops.GraphedCallable(lambda t: model.extend(t, pinned), toks.clone(), warmup=1)
+            torch.cuda.synchronize()
+
+            def decode_graph():
+                for t in range(T):
+                    dstep(toks[:, t])
+
+            def decode_eager():
+                for t in range(T):
+                    model.decode_step(toks[:, t], eager)
+
+            cands = {"extend_eager": (eager, lambda: model.extend(toks, eager)), "decode_eager": (eager, decode_eager),
+                     "extend_graph": (pinned, lambda: gstep(toks)), "decode_graph": (pinned, decode_graph)}
+            times = {k: [] for k in cands}
+            for b in range(-1, 5 if quick else 7):  # block -1: warm-up, not recorded
+                for k, (c, f) in cands.items():
+                    c.set_lens([pos])  # a sync, outside the timed region: every block starts at the same position
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(iters):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    if b >= 0:
+                        times[k].append(e0.elapsed_time(e1) / iters)  # ms per T tokens
+            row = {"model": name, "B": 1, "T": T, "position": pos, "capacity": cap}
+            for k, v in times.items():
+                row[k] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)}
+            row["decode_over_extend_eager"] = row["decode_eager"]["median_ms"] / row["extend_eager"]["median_ms"]
+            row["decode_over_extend_graph"] = row["decode_graph"]["median_ms"] / row["extend_graph"]["median_ms"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del gstep
+        del model, eager, pinned, dstep
+        torch.cuda.empty_cache()
+    return rows
+
+
+def step_extend(quick: bool):
+    return {"kernel": _extend_kernel_rows(quick), "model": _extend_model_rows(quick)}
+
+
+STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend}
 
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default="decode_bench.json")
-    ap.add_argument("--steps", default="gemm,attn,e2e")
+    ap.add_argument("--steps", default="gemm,attn,e2e,extend")
     ap.add_argument("--quick", action="store_true", help="fewer blocks / shapes (a smoke run of the tool)")
     ap.add_argument("--child", choices=sorted(STEPS), help=argparse.SUPPRESS)
     args = ap.parse_args()
