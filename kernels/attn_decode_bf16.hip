@@ -240,6 +240,22 @@ extern "C" long long kfamd_attn_decode_workspace(int B, int H, int D, int t_boun
   return (long long)B * H * nsplit * (D + 2) * (long long)sizeof(float);
 }
 
+// The merge of the splits' (m, l, o[D]) fp32 records into bf16 rows: reads only the workspace, so the
+// FP8-cache kernels (attn_kv_fp8.hip) launch it too. Arguments are the caller's, already checked.
+extern "C" int kfamd_attn_decode_combine(const float* ws, void* o, float* lse, int B, int H, int D, int nsplit,
+                                         long long ob, long long oh, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 cgrid((unsigned)H, (unsigned)B);
+  if (D == 64)
+    hipLaunchKernelGGL(attn_decode_combine<64>, cgrid, dim3(64), 0, s, ws, static_cast<__bf16*>(o), lse, H, nsplit, ob,
+                       oh);
+  else
+    hipLaunchKernelGGL(attn_decode_combine<128>, cgrid, dim3(128), 0, s, ws, static_cast<__bf16*>(o), lse, H, nsplit,
+                       ob, oh);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
 // strides (elements): q (b, h), k_cache (b, h, t), v_cache (b, h, t), o (b, h) — 10 values
 extern "C" int kfamd_attn_decode_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
                                       float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
@@ -275,15 +291,8 @@ extern "C" int kfamd_attn_decode_bf16(const void* q, const void* k_cache, const 
   else hipLaunchKernelGGL(attn_decode_split<128>, grid, dim3(kThreads), 0, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return static_cast<int>(e);
-  if (nsplit > 1) {
-    const dim3 cgrid((unsigned)H, (unsigned)B);
-    if (D == 64)
-      hipLaunchKernelGGL(attn_decode_combine<64>, cgrid, dim3(64), 0, s, a.ws, a.o, lse, H, nsplit, ob, oh);
-    else
-      hipLaunchKernelGGL(attn_decode_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, H, nsplit, ob, oh);
-    e = hipGetLastError();
-  }
-  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+  if (nsplit > 1) return kfamd_attn_decode_combine(a.ws, a.o, lse, B, H, D, nsplit, ob, oh, stream);
+  return KFAMD_OK;
 }
 
 // K and V rows of a fused QKV activation [B][T][3][H][D] (element strides qb, qt; [3][H][D] dense)

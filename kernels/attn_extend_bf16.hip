@@ -267,6 +267,22 @@ extern "C" long long kfamd_attn_extend_workspace(int B, int H, int D, int Tq, in
   return kfamd_attn_decode_workspace(B, H, D, t_bound) * Tq;
 }
 
+// The merge of the splits' per-row records: reads only the workspace, so the FP8-cache kernel
+// (attn_kv_fp8.hip) launches it too. Arguments are the caller's, already checked.
+extern "C" int kfamd_attn_extend_combine(const float* ws, void* o, float* lse, int B, int H, int D, int Tq, int nsplit,
+                                         long long ob, long long ot, long long oh, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 cgrid((unsigned)H, (unsigned)B, (unsigned)Tq);
+  if (D == 64)
+    hipLaunchKernelGGL(attn_extend_combine<64>, cgrid, dim3(64), 0, s, ws, static_cast<__bf16*>(o), lse, H, Tq, nsplit,
+                       ob, ot, oh);
+  else
+    hipLaunchKernelGGL(attn_extend_combine<128>, cgrid, dim3(128), 0, s, ws, static_cast<__bf16*>(o), lse, H, Tq,
+                       nsplit, ob, ot, oh);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
 // strides (elements): q (b, t, h), k_cache (b, h, t), v_cache (b, h, t), o (b, t, h) — 12 values
 extern "C" int kfamd_attn_extend_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
                                       float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
@@ -311,13 +327,6 @@ extern "C" int kfamd_attn_extend_bf16(const void* q, const void* k_cache, const 
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return static_cast<int>(e);
-  if (nsplit > 1) {
-    const dim3 cgrid((unsigned)H, (unsigned)B, (unsigned)Tq);
-    if (D == 64)
-      hipLaunchKernelGGL(attn_extend_combine<64>, cgrid, dim3(64), 0, s, a.ws, a.o, lse, H, Tq, nsplit, ob, ot, oh);
-    else
-      hipLaunchKernelGGL(attn_extend_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, H, Tq, nsplit, ob, ot, oh);
-    e = hipGetLastError();
-  }
-  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+  if (nsplit > 1) return kfamd_attn_extend_combine(a.ws, a.o, lse, B, H, D, Tq, nsplit, ob, ot, oh, stream);
+  return KFAMD_OK;
 }

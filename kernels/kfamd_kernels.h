@@ -244,6 +244,38 @@ int kfamd_attn_extend_bf16(const void* q, const void* k_cache, const void* v_cac
 // kt, vb, vh, vt}. Rows at or beyond Tcap are dropped.
 int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int H, int D,
                          int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream);
+// The split merges of the two kernels above as launches of their own: they read only the fp32 workspace,
+// so the FP8-cache kernels below share them. No argument checks: the callers have made them.
+int kfamd_attn_decode_combine(const float* ws, void* o, float* lse, int B, int H, int D, int nsplit, long long ob,
+                              long long oh, void* stream);
+int kfamd_attn_extend_combine(const float* ws, void* o, float* lse, int B, int H, int D, int Tq, int nsplit,
+                              long long ob, long long ot, long long oh, void* stream);
+
+// ---- FP8 KV cache (attn_kv_fp8.hip) -----------------------------------------------------------
+// The cache stored as OCP e4m3fn codes [B][H][Tcap][D] (one byte per element, strides b, h, t in
+// elements = bytes, multiples of 16; base 16-B aligned) with one fp32 scale per stored row: k_scale /
+// v_scale [B][H][Tcap] (strides b, h in elements; positions contiguous). A row x[0..D) of bf16 values is
+// stored as scale = max|x| / 448 (1 for an all-zero row) and code = RNE_e4m3(clamp(x / scale, +-448));
+// code * scale gives it back. D = 64 / 128.
+// kfamd_kv_append_fp8: the K and V rows of a fused QKV activation, as kfamd_kv_append_bf16, quantised on
+//   the way. cache_strides = {kb, kh, kt, vb, vh, vt, ksb, ksh, vsb, vsh}. Rows at or beyond Tcap are
+//   dropped: neither codes nor scale are written. Any T.
+// kfamd_attn_decode_fp8 / kfamd_attn_extend_fp8: the FP8-cache forms of kfamd_attn_decode_bf16 /
+//   kfamd_attn_extend_bf16: bf16 q and o, the same lens / t_bound / lse / workspace contract (the workspace
+//   sizes are kfamd_attn_decode_workspace / kfamd_attn_extend_workspace) and the same return codes. The
+//   score of key j is (q . codes_k[j]) * k_scale[j]; v_scale[j] is folded into p. Codes and scales at or
+//   beyond lens[b] are never used (they may be NaN).
+//   decode strides = {qb, qh, kb, kh, kt, vb, vh, vt, ob, oh, ksb, ksh, vsb, vsh};
+//   extend strides = {qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh}.
+int kfamd_kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale, const int* pos,
+                        int B, int T, int H, int D, int Tcap, long long qb, long long qt,
+                        const long long* cache_strides, void* stream);
+int kfamd_attn_decode_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                          const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
+                          int t_bound, float scale, const long long* strides, void* stream);
+int kfamd_attn_extend_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                          const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
+                          int Tq, int t_bound, float scale, const long long* strides, void* stream);
 
 // Weight-streaming NT GEMM for 1 <= M <= 16 (gemm_skinny_bf16.hip): C[M][N] = act(alpha * A[M][K] .
 // W[N][K]^T + bias[N]) (+ R[M][N]); K % 8 == 0, A / W rows 16-B aligned, any N, epilogue semantics of

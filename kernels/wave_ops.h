@@ -65,6 +65,17 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
+// max over the same groups (order-independent)
+template <int N>
+__device__ __forceinline__ float group_max(float v) {
+  static_assert(N == 8 || N == 16, "group_max: 8 or 16 lanes");
+  v = fmaxf(v, dpp_mov<dpp::kQuadXor1>(v));
+  v = fmaxf(v, dpp_mov<dpp::kQuadXor2>(v));
+  v = fmaxf(v, dpp_mov<dpp::kRowHalfMirror>(v));
+  if constexpr (N == 16) v = fmaxf(v, dpp_mov<dpp::kRowMirror>(v));
+  return v;
+}
+
 // sum / max over the 64 lanes, result in every lane
 __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_mov<dpp::kQuadXor1>(v);

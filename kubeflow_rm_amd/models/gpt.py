@@ -224,12 +224,16 @@ class GPT(torch.nn.Module):
     # Nothing in decode_step depends on a host-side position (the position embedding is gathered by
     # the device-side cache.lens), so it can be captured once into a hipGraph and replayed.
 
-    def new_cache(self, B: int, capacity: int, device=None) -> "ops.KVCache":
+    def new_cache(self, B: int, capacity: int, device=None, kv_dtype: torch.dtype | None = None) -> "ops.KVCache":
+        """A cache for B sequences of up to ``capacity`` tokens. ``kv_dtype``: what the cache stores;
+        ``None`` is the model's dtype, ``torch.float8_e4m3fn`` the 8-bit cache (codes plus one fp32 scale
+        per row: about half the bytes, see ``KVCache.nbytes``)."""
         c = self.cfg
         if capacity > c.max_seq:
             raise ValueError(f"cache capacity {capacity} exceeds max_seq {c.max_seq}")
         return ops.KVCache(c.n_layers, B, self.blocks[0].local_heads, c.head_dim, capacity,
-                           device=device if device is not None else self.tok.device, dtype=c.dtype)
+                           device=device if device is not None else self.tok.device,
+                           dtype=kv_dtype if kv_dtype is not None else c.dtype)
 
     def _native_decode(self, x: torch.Tensor) -> bool:
         # both paths read the sharded weights without the TP layers' all-reduces: refuse, on any device
@@ -250,7 +254,10 @@ class GPT(torch.nn.Module):
 
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
-        """Run the prompt ``idx [B, T0]`` into an empty ``cache``; logits ``[B, vocab]`` of the last position."""
+        """Run the prompt ``idx [B, T0]`` into an empty ``cache``; logits ``[B, vocab]`` of the last position.
+        The prompt's own attention runs on the unquantised QKV activation (the flash kernel on the GPU) and
+        never reads the cache: with an FP8 cache only what is STORED is quantised, and the logits are those
+        of a bf16 cache bit for bit."""
         B, T = idx.shape
         self._check_cache(cache, B, T)
         if cache._bound != 0:
@@ -394,15 +401,15 @@ class GPT(torch.nn.Module):
         logits = head_lin(ops.layer_norm_fwd(rows, self.ln_f.weight, self.ln_f.bias)[0], self.tok)
         return logits.view(*x.shape[:-1], c.vocab_size)
 
-    def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int):
+    def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int, kv_dtype=None):
         """Greedy draft-and-verify for one sequence: per round the draft proposes up to ``lookahead``
         tokens (``decode_step`` on its own cache), the target scores ``[last accepted, proposals...]`` in
         ONE ``extend`` and keeps the longest prefix that equals its own argmax, plus its own next token
         (the correction at the first mismatch, or the extra token after a full acceptance)."""
         T0 = idx.shape[1]
         total = T0 + max_new_tokens
-        tc = self.new_cache(1, total, device=idx.device)
-        dc = draft.new_cache(1, total, device=idx.device)
+        tc = self.new_cache(1, total, device=idx.device, kv_dtype=kv_dtype)
+        dc = draft.new_cache(1, total, device=idx.device, kv_dtype=kv_dtype)
         if T0 > 1:  # both caches hold the prompt but its last token: every new token comes from a round
             self.prefill(idx[:, :-1], tc)
             draft.prefill(idx[:, :-1], dc)
@@ -435,7 +442,7 @@ class GPT(torch.nn.Module):
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
-                 lookahead: int = 4, return_stats: bool = False):
+                 lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -443,7 +450,10 @@ class GPT(torch.nn.Module):
 
         ``draft`` (a ``GPT`` with the same vocabulary): greedy draft-and-verify decoding, ``lookahead``
         proposals per target ``extend``; greedy only, B = 1, no ``graph``. ``return_stats`` then also
-        returns ``{"target_steps", "proposed", "accepted"}``."""
+        returns ``{"target_steps", "proposed", "accepted"}``.
+
+        ``kv_dtype``: what the KV cache stores (``new_cache``); ``torch.float8_e4m3fn`` halves its bytes.
+        With a draft, both the target's and the draft's caches use it."""
         B, T0 = idx.shape
         total = T0 + max_new_tokens
         if max_new_tokens < 0 or T0 < 1 or total > self.cfg.max_seq:
@@ -457,7 +467,7 @@ class GPT(torch.nn.Module):
             if total > draft.cfg.max_seq:
                 raise ValueError(f"prompt + max_new_tokens must fit the draft's max_seq {draft.cfg.max_seq}")
             out, stats = ((idx.clone(), {"target_steps": 0, "proposed": 0, "accepted": 0}) if max_new_tokens == 0
-                          else self._generate_draft(idx, max_new_tokens, draft, int(lookahead)))
+                          else self._generate_draft(idx, max_new_tokens, draft, int(lookahead), kv_dtype))
             return (out, stats) if return_stats else out
         if return_stats:
             raise ValueError("generate(return_stats=True) reports draft decoding: pass draft=")
@@ -465,7 +475,7 @@ class GPT(torch.nn.Module):
             return idx.clone()
         if graph and not idx.is_cuda:
             raise ValueError("generate(graph=True) needs GPU tensors")
-        cache = self.new_cache(B, total, device=idx.device)
+        cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
         logits = self.prefill(idx, cache)
         step = lambda t: self.decode_step(t, cache)  # noqa: E731
         if graph and max_new_tokens > 1:

@@ -96,6 +96,12 @@ _SIGNATURES = {
                                        c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
                                      ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
+                                    ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_decode_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                      c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                      c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_gemm_nt_skinny_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
                                           c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_bf16_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,

@@ -19,6 +19,15 @@ new query rows per head, already appended, each attending the cache up to its ow
 
 On CPU tensors the same functions run plain torch (index copy, masked fp32 SDPA): the CPU model path
 and its tests. On a GPU there is no fallback: a shape the kernels reject raises.
+
+``KVCache(..., dtype=torch.float8_e4m3fn)`` is the 8-bit cache (``kernels/attn_kv_fp8.hip``): ``k`` / ``v``
+hold OCP e4m3fn codes ``[B, H, capacity, D]`` and ``k_scale`` / ``v_scale`` one fp32 scale per stored row
+``[B, H, capacity]``. ``kv_append`` quantises each K / V row on the way in (``quantize_rows``: ``scale =
+amax / 448``, ``code = RNE_e4m3(clamp(x / scale, -448, 448))``, an all-zero row stores ``scale = 1``); the
+attention kernels multiply the scales in (``(q . codes_k[j]) * k_scale[j]``, ``p * v_scale[j]``) and never
+write a dequantised tensor. The three functions dispatch on the cache's dtype; everything else about the
+cache (``lens``, ``t_bound``, ``advance``, ``rewind``, the workspaces) is the same. ``KVCache.nbytes`` is
+what a cache holds in device memory.
 """
 from __future__ import annotations
 
@@ -31,6 +40,9 @@ import torch.nn.functional as F
 from . import _lib
 
 HEAD_DIMS = (64, 128)
+FP8 = torch.float8_e4m3fn  # the 8-bit cache's code type (OCP e4m3fn: finite maximum 448, code 0x7E)
+FP8_MAX = 448.0
+CACHE_DTYPES = (torch.bfloat16, FP8)  # what the kernels read
 MAX_EXTEND_ROWS = 16  # query rows per attention_extend call
 _split_keys: int | None = None
 
@@ -63,8 +75,26 @@ def _ll(*vals) -> "ctypes.Array":
     return (ctypes.c_longlong * len(vals))(*(int(v) for v in vals))
 
 
+def quantize_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The FP8 cache's format in plain torch: rows ``x [..., D]`` -> ``(codes [..., D] float8_e4m3fn, scale
+    [...] fp32)`` with ``scale = max|x| / 448`` in fp32 (1 for an all-zero row) and ``code =
+    RNE_e4m3(clamp(x / scale, -448, 448))``. A non-finite input is out of contract."""
+    x = x.float()
+    amax = x.abs().amax(-1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    codes = (x / scale.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+    return codes, scale
+
+
+def dequantize_rows(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``codes * scale`` in fp32: the values an FP8 cache row stands for."""
+    return codes.float() * scale.float().unsqueeze(-1)
+
+
 class KVCache:
-    """Per-layer K / V ``[B, H, capacity, D]``, device ``lens`` (int32 [B]), host ``t_bound``."""
+    """Per-layer K / V ``[B, H, capacity, D]``, device ``lens`` (int32 [B]), host ``t_bound``.
+    ``dtype=torch.float8_e4m3fn``: ``k`` / ``v`` hold codes and ``k_scale`` / ``v_scale`` ``[B, H, capacity]``
+    fp32 the per-row scales (``None`` for every other dtype)."""
 
     def __init__(self, n_layers: int, B: int, H: int, D: int, capacity: int, device=None,
                  dtype: torch.dtype = torch.bfloat16):
@@ -74,14 +104,29 @@ class KVCache:
         self.device, self.dtype = torch.device(device if device is not None else "cpu"), dtype
         self.k = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
         self.v = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+        self.k_scale = self.v_scale = None
+        if dtype == FP8:
+            self.k_scale = [torch.zeros(B, H, capacity, device=self.device) for _ in range(n_layers)]
+            self.v_scale = [torch.zeros(B, H, capacity, device=self.device) for _ in range(n_layers)]
         self.lens = torch.zeros(B, device=self.device, dtype=torch.int32)
         self._lens_after = torch.zeros(B, device=self.device, dtype=torch.int32)  # lens_after()'s buffer
         self._bound, self._pinned = 0, False
         self.workspace = None
         self.extend_workspace = None  # attention_extend's, allocated on its first use
-        if self.device.type == "cuda" and dtype == torch.bfloat16 and D in HEAD_DIMS:  # the kernels' shapes
+        if self.device.type == "cuda" and dtype in CACHE_DTYPES and D in HEAD_DIMS:  # the kernels' shapes
             nbytes = _lib.lib().kfamd_attn_decode_workspace(B, H, D, capacity)
             self.workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
+
+    @property
+    def fp8(self) -> bool:
+        return self.dtype == FP8
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes this cache holds: K / V (codes), the scales of an FP8 cache, and the attention workspaces
+        allocated so far. ``lens`` and its step buffer (8 bytes per batch row) are not counted."""
+        ts = [*self.k, *self.v, *(self.k_scale or []), *(self.v_scale or []), self.workspace, self.extend_workspace]
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     @property
     def t_bound(self) -> int:
@@ -147,6 +192,9 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
         raise ValueError(f"kv_append: qkv [B={B}, T, {3 * H * D}] expected, got {tuple(qkv.shape)}")
     T = qkv.shape[1]
     k, v = cache.k[layer], cache.v[layer]
+    if cache.fp8 and not _native(qkv):
+        _kv_append_fp8_torch(qkv.reshape(B, T, 3, H, D), cache, layer)
+        return
     if not _native(qkv):
         x = qkv.reshape(B, T, 3, H, D)
         rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=qkv.device).unsqueeze(0)  # [B, T]
@@ -162,10 +210,44 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
         return
     if qkv.dtype != torch.bfloat16 or qkv.stride(2) != 1:
         raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
+    if cache.fp8:
+        if D not in HEAD_DIMS:
+            raise ValueError(f"kv_append: head dim in {HEAD_DIMS} expected for an FP8 cache on a GPU, got {D}")
+        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
+        rc = _lib.lib().kfamd_kv_append_fp8(
+            qkv.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(), cache.lens.data_ptr(), B, T, H, D,
+            cache.capacity, qkv.stride(0), qkv.stride(1),
+            _ll(*k.stride()[:3], *v.stride()[:3], *ks.stride()[:2], *vs.stride()[:2]), _stream_ptr(qkv))
+        _lib.check(rc, f"kv_append[fp8 B={B} T={T} H={H} D={D}]")
+        return
     rc = _lib.lib().kfamd_kv_append_bf16(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), cache.lens.data_ptr(), B, T, H, D,
                                          cache.capacity, qkv.stride(0), qkv.stride(1),
                                          _ll(*k.stride()[:3], *v.stride()[:3]), _stream_ptr(qkv))
     _lib.check(rc, f"kv_append[B={B} T={T} H={H} D={D}]")
+
+
+def _kv_append_fp8_torch(x, cache: KVCache, layer: int) -> None:
+    """The torch form of the quantising append: ``quantize_rows`` of the K / V rows, written through uint8
+    views (torch has no index_copy for float8). Rows at or beyond the capacity are dropped."""
+    B, T = x.shape[:2]
+    rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=x.device).unsqueeze(0)  # [B, T]
+    for s, codes, scales in ((1, cache.k[layer], cache.k_scale[layer]), (2, cache.v[layer], cache.v_scale[layer])):
+        c, sc = quantize_rows(x[:, :, s])  # [B, T, H, D], [B, T, H]
+        c = c.view(torch.uint8)
+        for b in range(B):
+            keep = rows[b] < cache.capacity
+            codes[b].view(torch.uint8).index_copy_(1, rows[b][keep], c[b, keep].transpose(0, 1))
+            scales[b].index_copy_(1, rows[b][keep], sc[b, keep].transpose(0, 1))
+
+
+def _dequantized_prefix(cache: KVCache, layer: int, lens, n: int, dtype):
+    """K, V of an FP8 cache's first n rows as ``dtype`` tensors, the rows at or beyond ``lens[b]`` zeroed
+    (dead codes and scales may be NaN): what the torch reference attends."""
+    live = (torch.arange(n, device=lens.device).view(1, 1, n) < lens.view(-1, 1, 1)).unsqueeze(-1)
+    zero = torch.zeros((), device=lens.device)
+    k = torch.where(live, dequantize_rows(cache.k[layer][:, :, :n], cache.k_scale[layer][:, :, :n]), zero)
+    v = torch.where(live, dequantize_rows(cache.v[layer][:, :, :n], cache.v_scale[layer][:, :, :n]), zero)
+    return k.to(dtype), v.to(dtype)
 
 
 def _attention_decode_torch(q, k, v, lens, scale):
@@ -193,6 +275,9 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     t_bound = cache.t_bound if t_bound is None else int(t_bound)
     k, v = cache.k[layer], cache.v[layer]
     if not _native(q):
+        if cache.fp8:  # the visible rows, dequantised; then the reference code as it is
+            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1),
+                                       q.dtype if q.is_cuda else torch.float32)
         o = _attention_decode_torch(q, k, v, lens, scale).to(q.dtype)
         if out is not None:
             out.copy_(o)
@@ -204,8 +289,8 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         return o
     if D not in HEAD_DIMS:
         raise ValueError(f"attention_decode: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
-    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype != torch.bfloat16:
-        raise ValueError("attention_decode: bf16 q (contiguous head dim) and a bf16 cache expected")
+    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
+        raise ValueError("attention_decode: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
     if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
         raise ValueError("attention_decode: lens must be a device int32 [B] tensor")
     if not 1 <= t_bound <= cache.capacity:
@@ -215,6 +300,15 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     elif tuple(out.shape) != (B, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
         raise ValueError(f"attention_decode: out must be a bf16 GPU [{B}, {H}, {D}] view with a contiguous head dim")
     lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
+    if cache.fp8:
+        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
+        rc = _lib.lib().kfamd_attn_decode_fp8(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(), lens.data_ptr(), out.data_ptr(),
+            lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
+            _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
+                *ks.stride()[:2], *vs.stride()[:2]), _stream_ptr(q))
+        _lib.check(rc, f"attention_decode[fp8 B={B} H={H} D={D} t_bound={t_bound}]")
+        return (out, lse) if return_lse else out
     rc = _lib.lib().kfamd_attn_decode_bf16(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), lens.data_ptr(), out.data_ptr(),
         lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
@@ -258,6 +352,8 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     t_bound = cache.t_bound if t_bound is None else int(t_bound)
     k, v = cache.k[layer], cache.v[layer]
     if not _native(q):
+        if cache.fp8:
+            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), torch.float32)
         o, lse = _attention_extend_torch(q, k, v, lens, scale)
         o = o.to(q.dtype)
         if out is not None:
@@ -268,8 +364,8 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         raise ValueError(f"attention_extend: 1 <= T <= {MAX_EXTEND_ROWS} query rows expected on a GPU, got {T}")
     if D not in HEAD_DIMS:
         raise ValueError(f"attention_extend: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
-    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype != torch.bfloat16:
-        raise ValueError("attention_extend: bf16 q (contiguous head dim) and a bf16 cache expected")
+    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
+        raise ValueError("attention_extend: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
     if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
         raise ValueError("attention_extend: lens must be a device int32 [B] tensor")
     if not 1 <= t_bound <= cache.capacity:
@@ -280,6 +376,15 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         raise ValueError(f"attention_extend: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
                          "head dim")
     lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
+    if cache.fp8:
+        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
+        rc = _lib.lib().kfamd_attn_extend_fp8(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(), lens.data_ptr(), out.data_ptr(),
+            lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, H, D, T, t_bound, scale,
+            _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3], *ks.stride()[:2],
+                *vs.stride()[:2]), _stream_ptr(q))
+        _lib.check(rc, f"attention_extend[fp8 B={B} T={T} H={H} D={D} t_bound={t_bound}]")
+        return (out, lse) if return_lse else out
     rc = _lib.lib().kfamd_attn_extend_bf16(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), lens.data_ptr(), out.data_ptr(),
         lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, H, D, T, t_bound, scale,

@@ -19,6 +19,11 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         ops.attention_decode on the same cache (D = 128, capacity 4096, B*H in {16, 128}, lens in {128,
         2048, 4096}; caches rotated as in attn). Model: gpt-small and gpt-1b, B = 1, position 1920:
         one GPT.extend of T tokens against T decode_steps, each eager and as a hipGraph, interleaved.
+  kv8   (not in the default list) the FP8 KV cache against the bf16 one, in the same process and in
+        interleaved blocks with rotated caches: ops.attention_decode and ops.attention_extend at Tq in
+        {4, 8} (D = 128, capacity 4096, B*H in {16, 128}, lens in {128, 2048, 4096}); ops.kv_append at T in
+        {1, 2048}; gpt-1b (gpt-small with --quick) end to end in ms/token at B in {1, 16}, eager and
+        graphed; KVCache.nbytes of both caches.
 """
 from __future__ import annotations
 
@@ -35,7 +40,8 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 ROOF = 6.29e12
-STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600}
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420}
+KV8_TS = (4, 8)
 EXTEND_TS = (1, 2, 4, 8, 16)
 GEMM_MS = (1, 2, 4, 8, 16)  # 2 and 4: where the VALU / MFMA cut-over of the skinny kernel is decided
 GEMM_SHAPES = [(6144, 2048), (2048, 2048), (8192, 2048), (2048, 8192), (32000, 2048)]  # (N, K)
@@ -265,7 +271,140 @@ def step_extend(quick: bool):
     return {"kernel": _extend_kernel_rows(quick), "model": _extend_model_rows(quick)}
 
 
-STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend}
+def _kv8_caches(B, H, D, cap, ncopy):
+    """A bf16 and an FP8 cache holding the same random rows (the FP8 one through the quantising append)."""
+    import torch
+    from kubeflow_rm_amd import ops
+    caches = {"bf16": ops.KVCache(ncopy, B, H, D, cap, device="cuda"),
+              "fp8": ops.KVCache(ncopy, B, H, D, cap, device="cuda", dtype=torch.float8_e4m3fn)}
+    chunk = 512
+    for layer in range(ncopy):
+        for c in caches.values():
+            c.reset()
+        for t0 in range(0, cap, chunk):
+            qkv = torch.randn(B, min(chunk, cap - t0), 3 * H * D, device="cuda").to(torch.bfloat16)
+            for c in caches.values():
+                ops.kv_append(qkv, c, layer)
+            for c in caches.values():
+                c.advance(qkv.shape[1])
+    return caches
+
+
+def _kv8_ratio(row, r):
+    for k, t in r.items():
+        row[k] = t
+    row["bf16_over_fp8"] = r["bf16"]["median_us"] / r["fp8"]["median_us"]
+    # a win or a loss only beyond the blocks' spread
+    row["separated"] = r["fp8"]["max_us"] < r["bf16"]["min_us"] or r["bf16"]["max_us"] < r["fp8"]["min_us"]
+    return row
+
+
+def _kv8_attention_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    D, cap = 128, 4096
+    blocks = 5 if quick else 7
+    for BH in (16, 128):
+        B, H = BH // 16, 16
+        ncopy = 1 if quick else max(1, min(4, (512 << 20) // (2 * B * H * cap * D * 2)))
+        caches = _kv8_caches(B, H, D, cap, ncopy)
+        for n in (128, 2048, 4096):
+            for c in caches.values():
+                c.set_lens([n] * B)
+            q = torch.randn(B, H, D, device="cuda").to(torch.bfloat16)
+            out = torch.empty(B, H, D, device="cuda", dtype=torch.bfloat16)
+            fns = {k: (lambda i, c=c: ops.attention_decode(q, c, i % ncopy, out=out, t_bound=n))
+                   for k, c in caches.items()}
+            r = _time_blocks(fns, blocks=blocks, iters=20)
+            row = _kv8_ratio({"op": "decode", "B": B, "H": H, "D": D, "len": n, "cache_copies": ncopy}, r)
+            row["bf16_KV_GBps"] = 2 * B * H * n * D * 2 / r["bf16"]["median_us"] / 1e3
+            row["fp8_KV_GBps"] = 2 * B * H * n * (D + 4) / r["fp8"]["median_us"] / 1e3
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            for Tq in KV8_TS:
+                qe = torch.randn(B, Tq, H, D, device="cuda").to(torch.bfloat16)
+                oe = torch.empty(B, Tq, H, D, device="cuda", dtype=torch.bfloat16)
+                fns = {k: (lambda i, c=c: ops.attention_extend(qe, c, i % ncopy, out=oe, t_bound=n))
+                       for k, c in caches.items()}
+                r = _time_blocks(fns, blocks=blocks, iters=20)
+                row = _kv8_ratio({"op": "extend", "Tq": Tq, "B": B, "H": H, "D": D, "len": n, "cache_copies": ncopy}, r)
+                row["bf16_KV_GBps"] = 2 * B * H * n * D * 2 / r["bf16"]["median_us"] / 1e3
+                row["fp8_KV_GBps"] = 2 * B * H * n * (D + 4) / r["fp8"]["median_us"] / 1e3
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+        del caches
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _kv8_append_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    B, H, D, cap, ncopy = 8, 16, 128, 4096, 2
+    caches = {"bf16": ops.KVCache(ncopy, B, H, D, cap, device="cuda"),
+              "fp8": ops.KVCache(ncopy, B, H, D, cap, device="cuda", dtype=torch.float8_e4m3fn)}
+    for T in (1, 2048):
+        qkv = torch.randn(B, T, 3 * H * D, device="cuda").to(torch.bfloat16)
+        for c in caches.values():
+            c.set_lens([cap - T] * B)  # lens is not advanced by the append: every call writes the same rows
+        fns = {k: (lambda i, c=c: ops.kv_append(qkv, c, i % ncopy)) for k, c in caches.items()}
+        r = _time_blocks(fns, blocks=5 if quick else 7, iters=20)
+        row = _kv8_ratio({"op": "kv_append", "B": B, "H": H, "D": D, "T": T}, r)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def _kv8_model_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    rows = []
+    prompt, new = 2048 - 128, 128
+    name = "gpt-small" if quick else "gpt-1b"
+    cfg = CONFIGS[name]
+    model = GPT(cfg, device="cuda").eval()
+    kinds = {"bf16": None, "fp8": torch.float8_e4m3fn}
+    for B in (1, 16):
+        idx = torch.randint(0, cfg.vocab_size, (B, prompt), device="cuda")
+        toks = torch.randint(0, cfg.vocab_size, (new, B), device="cuda")
+        nbytes = {}
+
+        def run(kind, mode):
+            cache = model.new_cache(B, prompt + new, kv_dtype=kinds[kind])
+            model.prefill(idx, cache)
+            step = (lambda t: model.decode_step(t, cache)) if mode != "graph" else model.graphed_decode_step(cache)
+            step(toks[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(1, new):
+                step(toks[i])
+            torch.cuda.synchronize()
+            nbytes[kind] = cache.nbytes
+            return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+        res = {f"{k}_{m}": [] for k in kinds for m in ("eager", "graph")}
+        for _ in range(3 if quick else 5):  # interleaved
+            for key in res:
+                res[key].append(run(*key.split("_")))
+        row = {"model": name, "B": B, "prompt": prompt, "new": new, "cache_nbytes": dict(nbytes),
+               "nbytes_fp8_over_bf16": nbytes["fp8"] / nbytes["bf16"]}
+        for k, v in res.items():
+            row[k] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+        for m in ("eager", "graph"):
+            row[f"bf16_over_fp8_{m}"] = row[f"bf16_{m}"]["ms_per_token"] / row[f"fp8_{m}"]["ms_per_token"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def step_kv8(quick: bool):
+    return {"attention": _kv8_attention_rows(quick), "append": _kv8_append_rows(quick),
+            "model": _kv8_model_rows(quick)}
+
+
+STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8}
 
 
 def main() -> int:
