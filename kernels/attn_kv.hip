@@ -1,0 +1,796 @@
+// attn_kv.hip — attention over a KV cache (split-KV, 1 .. 16 query rows, bf16 or FP8 cache) and the appends.
+//
+// Tq (1 .. 16) query rows per (batch, head), already appended to the cache [B][H][Tcap][D], attend it
+// causally: row i sees keys 0 .. lens[b] - Tq + i. Decode is Tq = 1. The step is a KV stream (one query
+// row: no MFMA tile to fill, cdna_hip_programming.md "Attention decode (single-token)"): K and V go
+// straight to VGPRs, the dot products and P.V run on the VALU in fp32, and K and V are streamed once per
+// (b, h, split) for up to 8 rows — the whole gain of a multi-row call over Tq single-row ones.
+//
+// Two kernel bodies, both over a row format Fmt (Bf16Rows / Fp8Rows below: the load width, the unpack, the
+// unroll, and whether a row carries scales; both formats put 8 elements in a lane, so a key row is D / 8
+// lanes wide, and the lane groups, the keys per block step and the accumulators per lane are the same):
+//   attn_extend_split<Fmt, D, R>  R row slots, 1 / 2 / 4 / 8: the row count rounded up to a power of two;
+//         slots beyond Tq never see a valid key and are never stored. Tq = 9 .. 16 runs two split launches
+//         (rows 0 .. 7, rows 8 .. Tq - 1). Sixteen slots (16 x 8 fp32 accumulators next to 16 rows of q)
+//         exceed the 256-VGPR budget and spill, so they are not instantiated.
+//   attn_decode_split<Fmt, D>  the single-row entry points' kernel: the same arithmetic in the same order as
+//         R = 1 with Tq = 1, row0 = 0 (o and lse are bit-identical: tests/test_gpu_attn_kv_unified.py), kept
+//         as a body of its own because a graphed single-token step at B*H = 16 is latency-bound and the
+//         general body, launched for it, was 1.0 - 1.5 % of a gpt-1b step slower (profiles/attn_kv_unify).
+// They share the formats, the split bookkeeping's constants, the host check and the launcher; each has its
+// combine (attn_decode_combine is attn_kv_combine at Tq = 1).
+// The MFMA form (16 rows fill one v_mfma_f32_16x16x32_bf16 tile for Q.K^T; P.V then needs V with keys
+// along k, an LDS transpose of every V tile) was NOT built: one form serves every Tq, no cut-over.
+//
+// Split structure: the key range [0, t_bound) is cut in fixed chunks of kSplitKeys keys; workgroup
+// (split, h, b) — 256 threads — walks its chunk. The block's 256 / (D / 8) lane groups take consecutive
+// keys, Fmt::unroll(R) keys per group and step, with the next step's loads issued before the current
+// step's arithmetic. Each lane group keeps its own fp32 online softmax (m, l, o[8 dims per lane]) per
+// row slot; the groups meet in LDS once, at the end. With one split the block writes the bf16 rows
+// directly; otherwise it writes (m, l, o[D]) fp32 per row to the workspace ([B][H][Tq][nsplit]) and a
+// second small launch (attn_kv_combine) merges the splits in a fixed order: two dependent launches on
+// one stream, no cross-workgroup waiting, no atomics, results bitwise repeatable.
+//
+// lens is DEVICE memory and is never advanced here: a captured step replays while the position advances.
+// Keys at or beyond a row's limit are excluded by a branch on the key index, never multiplied by zero:
+// the cache there may hold NaN (bf16), or codes 0x7F and NaN scales (FP8). Addresses, the scale loads'
+// too, are clamped to a valid key. The causal limit differs per row, so "no key in this split" (m = -inf,
+// l = 0, skipped by select in every merge) happens per row, not only per split.
+//
+// The FP8 cache holds OCP e4m3fn codes [B][H][Tcap][D] (one byte per element) and one fp32 scale per
+// stored row ([B][H][Tcap], one tensor for K and one for V). A row x[0..D) of bf16 values read as fp32 is
+// stored as
+//     scale = max|x| / 448   (1 for an all-zero row),   code = RNE_e4m3(clamp(x / scale, -448, 448)),
+// clamped in fp32 before v_cvt_pk_fp8_f32 so that nothing depends on the hardware's FP8 overflow mode;
+// code * scale gives the row back. Attention never dequantises to memory: the codes are unpacked to fp32
+// on the VALU (v_cvt_pk_f32_fp8, 4 per 8 elements where bf16 takes 8 shifts / ands), the score of key j
+// is (q . codes_k[j]) * kscale[j], and vscale[j] is folded into p before the P.V FMAs. The scale of key j
+// is loaded with its row (every lane of the group reads the same word) and prefetched with it. A lane
+// takes 8 code bytes in one 8-B load; the 16-B form (D / 16 lanes per row) was not built: at D = 64 it
+// leaves 4-lane groups, which wave_ops.h's group reductions do not cover, and it doubles the
+// accumulators per lane, a certain spill at 8 row slots.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): VGPRs, the same
+// at D = 64 and at D = 128 unless two are given; scratch is 0 for every instantiation. "before": the four
+// kernels this file replaced, D = 64 / 128.
+//   instantiation                      VGPRs   before
+//   attn_decode_split<Bf16Rows, D>       66    66 /  66
+//   attn_decode_split<Fp8Rows, D>        84    84 /  84
+//   attn_extend_split<Bf16Rows, D, 1>    64    72 /  67
+//   attn_extend_split<Bf16Rows, D, 2>    92    96 /  96
+//   attn_extend_split<Bf16Rows, D, 4>   129   130 / 130
+//   attn_extend_split<Bf16Rows, D, 8>   201   202 / 202
+//   attn_extend_split<Fp8Rows, D, 1>     84    97 /  84
+//   attn_extend_split<Fp8Rows, D, 2>    112   116 / 116
+//   attn_extend_split<Fp8Rows, D, 4>    149   150 / 150
+//   attn_extend_split<Fp8Rows, D, 8>    197   198 / 198
+//   kv_append / kv_append_fp8<D>     21 / 39   21 /  39
+// The extend body's LDS merge is written as one pass and, for R = 8, a guarded second one: as a loop over
+// the passes with an early exit it cost R = 1 up to 13 VGPRs (Fp8Rows, D = 64: 97, one wave per SIMD less).
+// Measured (profiles/decode, profiles/extend, profiles/kv_fp8, profiles/attn_kv_unify; D = 128, capacity
+// 4096): a multi-row call against Tq single-row calls is 1.7-2.3x at Tq = 2, 2.8-4.5x at 4, 3.4-7.0x at 8,
+// 3.5-7.5x at 16; up to Tq = 4 it stays a KV stream (4.0-4.5 TB/s at B*H = 128, >= 2048 keys), at Tq = 8
+// the VALU work sets the time and Tq = 16 costs twice Tq = 8. FP8 against bf16: decode 1.57-1.71x faster
+// at B*H = 128 with 2048 / 4096 keys; Tq = 4 1.17x at 2048 keys and a tie at 4096; Tq = 8 ties or loses
+// 4 %; ties within the launch floor at 128 keys and at B*H = 16. The FP8 append is 1.33x slower than the
+// bf16 copy at T = 2048 (8 IEEE divisions per lane): 63 us per layer of a 2048-token prefill.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kfamd_kernels.h"
+#include "wave_ops.h"
+
+namespace {
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kSplitKeys = 256;
+constexpr int kThreads = 256;
+constexpr int kMaxRows = 16;
+constexpr int kSlotRows = 8;   // query rows per split launch (16 row slots spill: see the header)
+constexpr int kMergeRows = 4;  // row slots merged per LDS pass
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+constexpr float kFp8Max = 448.f;  // largest finite e4m3fn value (code 0x7E)
+
+// ---- row formats -------------------------------------------------------------------------------
+// What a cache row is made of. Elem: the unit of the cache strides. Vec: one lane's load, 8 elements.
+// kStrideAlign: what every cache stride must be a multiple of, in Elem (16 B either way). unroll(R): keys
+// per lane group and block step, loaded one step ahead. kScaled: a row has an fp32 scale next to it.
+struct Bf16Rows {
+  typedef __bf16 Elem;
+  typedef u32x4 Vec;
+  static constexpr bool kScaled = false;
+  static constexpr int kStrideAlign = 8;
+  static constexpr int unroll(int) { return 2; }
+  static __device__ __forceinline__ void unpack8(const Vec& w, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __uint_as_float(w[i] << 16);
+      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+  }
+};
+
+struct Fp8Rows {
+  typedef uint8_t Elem;
+  typedef u32x2 Vec;
+  static constexpr bool kScaled = true;
+  static constexpr int kStrideAlign = 16;
+  // A lane's load is 8 B, half of bf16's: twice bf16's unroll keeps the same bytes in flight where the
+  // kernel is a KV stream (up to 4 row slots); at 8 row slots the VALU sets the time and the registers
+  // go to the accumulators.
+  static constexpr int unroll(int R) { return R >= 8 ? 2 : 4; }
+  // 8 e4m3 codes (memory order: byte 0 first) -> fp32
+  static __device__ __forceinline__ void unpack8(const Vec& w, float* f) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+      const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+      f[4 * i] = lo[0];
+      f[4 * i + 1] = lo[1];
+      f[4 * i + 2] = hi[0];
+      f[4 * i + 3] = hi[1];
+    }
+  }
+};
+
+// ---- attention ---------------------------------------------------------------------------------
+struct AttnArgs {
+  const __bf16* q;
+  const void* k;  // Fmt::Elem
+  const void* v;
+  const float* ks;  // Fmt::kScaled only, as ksb .. vsh
+  const float* vs;
+  const int* lens;
+  __bf16* o;
+  float* lse;
+  float* ws;
+  int B, H, Tq, row0, t_bound, nsplit;  // a split launch holds rows row0 .. row0 + R - 1 of the Tq
+  float scale_log2;
+  long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
+};
+
+// The single-row kernel's arguments: AttnArgs without Tq, row0 and the t strides.
+struct DecodeArgs {
+  const __bf16* q;
+  const void* k;
+  const void* v;
+  const int* lens;
+  __bf16* o;
+  float* lse;
+  float* ws;
+  int B, H, t_bound, nsplit;
+  float scale_log2;
+  long long qb, qh, kb, kh, kt, vb, vh, vt, ob, oh;
+  const float* ks;  // Fmt::kScaled only, as ksb .. vsh
+  const float* vs;
+  long long ksb, ksh, vsb, vsh;
+};
+
+// One query row per (b, h). workspace: [B][H][nsplit][2] (m, l) then [B][H][nsplit][D] (o), fp32: the
+// extend kernel's at Tq = 1. What the extend body's comments say about key validity, clamped addresses,
+// the block-uniform early return and whole block steps holds here word for word.
+template <class Fmt, int D>
+__global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
+  typedef typename Fmt::Elem Elem;
+  typedef typename Fmt::Vec Vec;
+  constexpr int kUnroll = Fmt::unroll(1);
+  constexpr int G = D / 8;             // lanes per key row
+  constexpr int NG = kThreads / G;     // lane groups per block (= keys per block and unroll slot)
+  constexpr int KSTEP = NG * kUnroll;  // keys per block step
+  static_assert(kSplitKeys % KSTEP == 0, "a split holds a whole number of block steps");
+  const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x;
+  const int grp = tid / G, piece = tid % G;
+
+  __shared__ float s_m[NG], s_l[NG];
+  __shared__ float s_o[NG][D + 4];
+
+  int len = a.lens[b];
+  len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
+  const int k0 = split * kSplitKeys;
+  const int k1 = min(k0 + kSplitKeys, len);  // valid keys of this split: [k0, k1)
+  const long long bh = ((long long)b * a.H + h);
+  float* ws_ml = a.ws + (bh * a.nsplit + split) * 2;
+  float* ws_o = a.ws + (long long)a.B * a.H * a.nsplit * 2 + (bh * a.nsplit + split) * D;
+
+  if (k1 <= k0) {  // empty split (only reachable with nsplit > 1 or len == 0)
+    if (a.nsplit > 1) {
+      if (tid == 0) {
+        ws_ml[0] = -INFINITY;
+        ws_ml[1] = 0.f;
+      }
+      if (tid < D) ws_o[tid] = 0.f;
+    } else {
+      if (tid < D) a.o[b * a.ob + h * a.oh + tid] = (__bf16)0.f;
+      if (tid == 0 && a.lse) a.lse[bh] = -INFINITY;
+    }
+    return;
+  }
+
+  float qf[8];
+  Bf16Rows::unpack8(*reinterpret_cast<const u32x4*>(a.q + b * a.qb + h * a.qh + piece * 8), qf);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) qf[i] *= a.scale_log2;
+
+  const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh + piece * 8;
+  const Elem* vbase = static_cast<const Elem*>(a.v) + b * a.vb + h * a.vh + piece * 8;
+  const float *ksbase = nullptr, *vsbase = nullptr;
+  if constexpr (Fmt::kScaled) {
+    ksbase = a.ks + b * a.ksb + h * a.ksh;
+    vsbase = a.vs + b * a.vsb + h * a.vsh;
+  }
+  const int last = k1 - 1;
+
+  float m = -INFINITY, l = 0.f, acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+
+  Vec kn[kUnroll], vn[kUnroll];
+  float ksn[kUnroll], vsn[kUnroll];  // Fmt::kScaled only
+  auto load_ahead = [&](int u, int key) {
+    key = min(key, last);
+    kn[u] = *reinterpret_cast<const Vec*>(kbase + key * a.kt);
+    vn[u] = *reinterpret_cast<const Vec*>(vbase + key * a.vt);
+    if constexpr (Fmt::kScaled) {
+      ksn[u] = ksbase[key];
+      vsn[u] = vsbase[key];
+    }
+  };
+#pragma unroll
+  for (int u = 0; u < kUnroll; ++u) load_ahead(u, k0 + u * NG + grp);
+  for (int kk = k0; kk < k1; kk += KSTEP) {
+    Vec kc[kUnroll], vc[kUnroll];
+    float ksc[kUnroll], vsc[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      kc[u] = kn[u];
+      vc[u] = vn[u];
+      if constexpr (Fmt::kScaled) {
+        ksc[u] = ksn[u];
+        vsc[u] = vsn[u];
+      }
+    }
+    if (kk + KSTEP < k1) {
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) load_ahead(u, kk + KSTEP + u * NG + grp);
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int key = kk + u * NG + grp;
+      float kf[8];
+      Fmt::unpack8(kc[u], kf);
+      float part = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) part = fmaf(qf[i], kf[i], part);
+      float s = kfw::group_sum<G>(part);
+      if constexpr (Fmt::kScaled) s *= ksc[u];
+      if (key < k1) {
+        float vf[8];
+        Fmt::unpack8(vc[u], vf);
+        const float mn = fmaxf(m, s);
+        const float corr = exp2f(m - mn);
+        float p = exp2f(s - mn);
+        l = l * corr + p;
+        if constexpr (Fmt::kScaled) p *= vsc[u];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(acc[i], corr, p * vf[i]);
+        m = mn;
+      }
+    }
+  }
+
+  // the block's lane groups meet in LDS
+  if (piece == 0) {
+    s_m[grp] = m;
+    s_l[grp] = l;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s_o[grp][piece * 8 + i] = acc[i];
+  __syncthreads();
+  if (tid < D) {
+    float M = -INFINITY;
+    for (int g = 0; g < NG; ++g) M = fmaxf(M, s_m[g]);  // finite: the split holds at least one key
+    float L = 0.f, O = 0.f;
+    for (int g = 0; g < NG; ++g) {
+      const float mg = s_m[g];
+      const float w = mg == -INFINITY ? 0.f : exp2f(mg - M);  // a group that saw no key
+      L += s_l[g] * w;
+      O += s_o[g][tid] * w;
+    }
+    if (a.nsplit > 1) {
+      ws_o[tid] = O;
+      if (tid == 0) {
+        ws_ml[0] = M;
+        ws_ml[1] = L;
+      }
+    } else {
+      a.o[b * a.ob + h * a.oh + tid] = (__bf16)(O / L);
+      if (tid == 0 && a.lse) a.lse[bh] = (M + log2f(L)) * kLn2;
+    }
+  }
+}
+// workspace: [B][H][Tq][nsplit][2] (m, l) then [B][H][Tq][nsplit][D] (o), fp32
+template <class Fmt, int D, int R>
+__global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
+  typedef typename Fmt::Elem Elem;
+  typedef typename Fmt::Vec Vec;
+  constexpr int kUnroll = Fmt::unroll(R);
+  constexpr int G = D / 8;             // lanes per key row
+  constexpr int NG = kThreads / G;     // lane groups per block
+  constexpr int KSTEP = NG * kUnroll;  // keys per block step
+  constexpr int RC = R < kMergeRows ? R : kMergeRows;
+  // a block step never reaches into the next split: `key < nk[r]` alone then decides a key's validity
+  static_assert(kSplitKeys % KSTEP == 0, "a split holds a whole number of block steps");
+  static_assert(R <= 2 * RC, "the LDS merge takes one or two passes");
+  const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x;
+  const int grp = tid / G, piece = tid % G;
+  const int Tq = a.Tq, row0 = a.row0;
+
+  __shared__ float s_m[NG][RC], s_l[NG][RC];
+  __shared__ float s_o[NG][RC][D + 4];
+
+  int len = a.lens[b];
+  len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
+  const int k0 = split * kSplitKeys;
+  const int k1 = min(k0 + kSplitKeys, len);  // keys of this split that the last row may see: [k0, k1)
+  const long long bh = (long long)b * a.H + h;
+  const long long nrows = (long long)a.B * a.H * Tq;
+
+  if (k1 <= k0) {  // empty split for every row (block-uniform, before any barrier)
+    for (int r = row0; r < min(row0 + R, Tq); ++r) {
+      const long long row = bh * Tq + r;
+      if (a.nsplit > 1) {
+        if (tid == 0) {
+          a.ws[(row * a.nsplit + split) * 2] = -INFINITY;
+          a.ws[(row * a.nsplit + split) * 2 + 1] = 0.f;
+        }
+        if (tid < D) a.ws[nrows * a.nsplit * 2 + (row * a.nsplit + split) * D + tid] = 0.f;
+      } else {
+        if (tid < D) a.o[b * a.ob + r * a.ot + h * a.oh + tid] = (__bf16)0.f;
+        if (tid == 0 && a.lse) a.lse[((long long)b * Tq + r) * a.H + h] = -INFINITY;
+      }
+    }
+    return;
+  }
+
+  // row slot r sees keys [0, nk[r]); a padding slot (r >= Tq) and a row before the sequence's start see none
+  float qf[R][8];
+  int nk[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int gr = row0 + r;               // the slot's row of the Tq
+    const int rr = gr < Tq ? gr : Tq - 1;  // padding slots read a valid row
+    Bf16Rows::unpack8(*reinterpret_cast<const u32x4*>(a.q + b * a.qb + rr * a.qt + h * a.qh + piece * 8), qf[r]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qf[r][i] *= a.scale_log2;
+    nk[r] = gr < Tq ? len - Tq + gr + 1 : 0;
+  }
+
+  const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh + piece * 8;
+  const Elem* vbase = static_cast<const Elem*>(a.v) + b * a.vb + h * a.vh + piece * 8;
+  const float *ksbase = nullptr, *vsbase = nullptr;
+  if constexpr (Fmt::kScaled) {
+    ksbase = a.ks + b * a.ksb + h * a.ksh;
+    vsbase = a.vs + b * a.vsb + h * a.vsh;
+  }
+  const int last = k1 - 1;  // addresses are clamped to a valid key; the key index decides validity
+
+  float m[R], l[R], acc[R][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[r][i] = 0.f;
+  }
+
+  Vec kn[kUnroll], vn[kUnroll];
+  float ksn[kUnroll], vsn[kUnroll];  // Fmt::kScaled only
+  auto load_ahead = [&](int u, int key) {
+    key = min(key, last);
+    kn[u] = *reinterpret_cast<const Vec*>(kbase + key * a.kt);
+    vn[u] = *reinterpret_cast<const Vec*>(vbase + key * a.vt);
+    if constexpr (Fmt::kScaled) {
+      ksn[u] = ksbase[key];
+      vsn[u] = vsbase[key];
+    }
+  };
+#pragma unroll
+  for (int u = 0; u < kUnroll; ++u) load_ahead(u, k0 + u * NG + grp);
+  for (int kk = k0; kk < k1; kk += KSTEP) {
+    Vec kc[kUnroll], vc[kUnroll];
+    float ksc[kUnroll], vsc[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      kc[u] = kn[u];
+      vc[u] = vn[u];
+      if constexpr (Fmt::kScaled) {
+        ksc[u] = ksn[u];
+        vsc[u] = vsn[u];
+      }
+    }
+    if (kk + KSTEP < k1) {  // the next step's loads go out before this step's arithmetic
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) load_ahead(u, kk + KSTEP + u * NG + grp);
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int key = kk + u * NG + grp;
+      float kf[8], vf[8];
+      Fmt::unpack8(kc[u], kf);
+      Fmt::unpack8(vc[u], vf);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        float part = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) part = fmaf(qf[r][i], kf[i], part);
+        float s = kfw::group_sum<G>(part);  // every lane of the group: scale * log2e * q_r.k
+        if constexpr (Fmt::kScaled) s *= ksc[u];
+        if (key < nk[r]) {  // group-uniform; an invalid key touches no state
+          const float mn = fmaxf(m[r], s);
+          const float corr = exp2f(m[r] - mn);  // m = -inf on the first key: exp2(-inf) = 0
+          float p = exp2f(s - mn);
+          l[r] = l[r] * corr + p;
+          if constexpr (Fmt::kScaled) p *= vsc[u];  // V's scale folded into p
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[r][i] = fmaf(acc[r][i], corr, p * vf[i]);
+          m[r] = mn;
+        }
+      }
+    }
+  }
+
+  // the block's lane groups meet in LDS, RC row slots per pass
+  auto merge_pass = [&](const int r0) {
+#pragma unroll
+    for (int j = 0; j < RC; ++j) {
+      if (piece == 0) {
+        s_m[grp][j] = m[r0 + j];
+        s_l[grp][j] = l[r0 + j];
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s_o[grp][j][piece * 8 + i] = acc[r0 + j][i];
+    }
+    __syncthreads();
+    for (int item = tid; item < RC * D; item += kThreads) {
+      const int j = item / D, d = item % D;
+      const int r = row0 + r0 + j;
+      if (r >= Tq) continue;  // padding: nothing of it is stored
+      float M = -INFINITY;
+      for (int g = 0; g < NG; ++g) M = fmaxf(M, s_m[g][j]);
+      float L = 0.f, O = 0.f;
+      for (int g = 0; g < NG; ++g) {
+        const float mg = s_m[g][j];
+        const float w = mg == -INFINITY ? 0.f : exp2f(mg - M);  // a group that saw no key of this row
+        L += s_l[g][j] * w;
+        O += s_o[g][j][d] * w;
+      }
+      const long long row = bh * Tq + r;
+      if (a.nsplit > 1) {  // M = -inf, L = 0 for a row with no key in this split
+        a.ws[nrows * a.nsplit * 2 + (row * a.nsplit + split) * D + d] = O;
+        if (d == 0) *reinterpret_cast<float2*>(a.ws + (row * a.nsplit + split) * 2) = make_float2(M, L);
+      } else {
+        const bool any = L > 0.f;  // a row before the sequence's start (lens[b] < Tq) sees no key
+        a.o[b * a.ob + r * a.ot + h * a.oh + d] = (__bf16)(any ? O / L : 0.f);
+        if (d == 0 && a.lse) a.lse[((long long)b * Tq + r) * a.H + h] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
+      }
+    }
+  };
+  merge_pass(0);
+  if constexpr (R > RC) {
+    if (row0 + RC < Tq) {  // block-uniform: otherwise only padding slots are left
+      __syncthreads();     // the first pass has been read
+      merge_pass(RC);
+    }
+  }
+}
+
+// The merge of the splits' per-row (m, l, o[D]) fp32 records into bf16 rows: reads only the workspace.
+// B is an argument, not gridDim.y: the launch dimensions are read from beyond the 64 bytes of arguments,
+// one more serial scalar-load miss per call of a kernel that runs for a few microseconds.
+template <int D>
+__global__ __launch_bounds__(D) void attn_kv_combine(const float* __restrict__ ws, __bf16* __restrict__ o,
+                                                     float* __restrict__ lse, int B, int H, int Tq, int nsplit,
+                                                     long long ob, long long ot, long long oh) {
+  const int h = blockIdx.x, b = blockIdx.y, r = blockIdx.z, d = threadIdx.x;
+  const long long nrows = (long long)B * H * Tq;
+  const long long row = ((long long)b * H + h) * Tq + r;
+  const float* ml = ws + row * nsplit * 2;
+  const float* po = ws + nrows * nsplit * 2 + row * nsplit * D;
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[2 * s]);
+  float L = 0.f, O = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float ms = ml[2 * s];
+    const float w = ms == -INFINITY ? 0.f : exp2f(ms - M);  // no key of this row in the split: skipped by select
+    L += ml[2 * s + 1] * w;
+    O += po[s * D + d] * w;
+  }
+  const bool any = L > 0.f;  // no key at all
+  o[b * ob + r * ot + h * oh + d] = (__bf16)(any ? O / L : 0.f);
+  if (d == 0 && lse) lse[((long long)b * Tq + r) * H + h] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
+}
+
+// The same merge for the single-row kernel's records (Tq = 1, no t stride), kept next to it for the reason
+// given in the header: through attn_kv_combine a graphed single-token step measured 0.1 - 0.2 us per call
+// slower at B*H = 16.
+template <int D>
+__global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict__ ws, __bf16* __restrict__ o,
+                                                         float* __restrict__ lse, int H, int nsplit, long long ob,
+                                                         long long oh) {
+  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+  const long long bh = (long long)b * H + h;
+  const float* ml = ws + bh * nsplit * 2;
+  const float* po = ws + (long long)gridDim.y * H * nsplit * 2 + bh * nsplit * D;
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ml[2 * s]);
+  float L = 0.f, O = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float ms = ml[2 * s];
+    const float w = ms == -INFINITY ? 0.f : exp2f(ms - M);  // an empty split: skipped by select
+    L += ml[2 * s + 1] * w;
+    O += po[s * D + d] * w;
+  }
+  const bool any = L > 0.f;  // lens[b] == 0: no key at all
+  o[b * ob + h * oh + d] = (__bf16)(any ? O / L : 0.f);
+  if (d == 0 && lse) lse[bh] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+template <class Fmt, int D>
+void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
+  const dim3 block(kThreads);
+  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1>), grid, block, 0, s, a);
+  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2>), grid, block, 0, s, a);
+  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8>), grid, block, 0, s, a);
+}
+
+// The one launcher behind the four attention entry points. st: the entry point's stride array, q (b, [t,]
+// h), k (b, h, t), v (b, h, t), o (b, [t,] h), then for a scaled format k_scale (b, h), v_scale (b, h);
+// has_t: the t strides are present. Without them it is a single-row entry point (Tq = 1), which launches
+// attn_decode_split. Every KFAMD_EINVAL condition is tested before any KFAMD_EALIGN one.
+template <class Fmt>
+int attn_kv(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens, void* o,
+            float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale, const long long* st,
+            bool has_t, void* stream) {
+  if (!q || !k || !v || !lens || !o || !st || B <= 0 || H <= 0 || B > 65535 || H > 65535) return KFAMD_EINVAL;
+  if (Fmt::kScaled && (!ks || !vs)) return KFAMD_EINVAL;
+  if ((D != 64 && D != 128) || Tq < 1 || Tq > kMaxRows || t_bound < 1) return KFAMD_EINVAL;
+  AttnArgs a = {};
+  a.qb = *st++, a.qt = has_t ? *st++ : 0, a.qh = *st++;
+  a.kb = *st++, a.kh = *st++, a.kt = *st++, a.vb = *st++, a.vh = *st++, a.vt = *st++;
+  a.ob = *st++, a.ot = has_t ? *st++ : 0, a.oh = *st++;
+  if (Fmt::kScaled) a.ksb = *st++, a.ksh = *st++, a.vsb = *st++, a.vsh = *st++;
+  if (a.kt < D || a.vt < D) return KFAMD_EINVAL;
+  const long long lim = (1ll << 31) / (long long)sizeof(typename Fmt::Elem);  // a (b, h) slice stays below 2^31 bytes
+  if ((long long)t_bound * a.kt >= lim || (long long)t_bound * a.vt >= lim) return KFAMD_EINVAL;
+  a.nsplit = (t_bound + kSplitKeys - 1) / kSplitKeys;
+  if (a.nsplit > 1 && !ws) return KFAMD_EINVAL;
+  if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || (ws && !al16(ws))) return KFAMD_EALIGN;
+  if (Fmt::kScaled && (!al4(ks) || !al4(vs))) return KFAMD_EALIGN;
+  if ((a.qb | a.qt | a.qh | a.ob | a.ot | a.oh) & 7) return KFAMD_EALIGN;
+  if ((a.kb | a.kh | a.kt | a.vb | a.vh | a.vt) & (Fmt::kStrideAlign - 1)) return KFAMD_EALIGN;
+  a.q = static_cast<const __bf16*>(q);
+  a.k = k, a.v = v, a.ks = ks, a.vs = vs, a.lens = lens;
+  a.o = static_cast<__bf16*>(o);
+  a.lse = lse;
+  a.ws = static_cast<float*>(ws);
+  a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound;
+  a.scale_log2 = scale * kLog2e;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)a.nsplit, (unsigned)H, (unsigned)B);
+  if (!has_t) {
+    const DecodeArgs d = {a.q,  a.k,  a.v,  a.lens, a.o,  a.lse, a.ws, B,    H,    t_bound, a.nsplit, a.scale_log2,
+                          a.qb, a.qh, a.kb, a.kh,   a.kt, a.vb,  a.vh, a.vt, a.ob, a.oh,    a.ks,     a.vs,
+                          a.ksb, a.ksh, a.vsb, a.vsh};
+    if (D == 64) hipLaunchKernelGGL((attn_decode_split<Fmt, 64>), grid, dim3(kThreads), 0, s, d);
+    else hipLaunchKernelGGL((attn_decode_split<Fmt, 128>), grid, dim3(kThreads), 0, s, d);
+  }
+  for (a.row0 = 0; has_t && a.row0 < Tq; a.row0 += kSlotRows) {  // one K / V stream per kSlotRows query rows
+    const int n = Tq - a.row0 < kSlotRows ? Tq - a.row0 : kSlotRows;
+    if (D == 64) launch_split<Fmt, 64>(a, n, grid, s);
+    else launch_split<Fmt, 128>(a, n, grid, s);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return static_cast<int>(e);
+  if (a.nsplit > 1 && !has_t) {
+    const dim3 cgrid((unsigned)H, (unsigned)B);
+    if (D == 64)
+      hipLaunchKernelGGL(attn_decode_combine<64>, cgrid, dim3(64), 0, s, a.ws, a.o, lse, H, a.nsplit, a.ob, a.oh);
+    else
+      hipLaunchKernelGGL(attn_decode_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, H, a.nsplit, a.ob, a.oh);
+    e = hipGetLastError();
+  } else if (a.nsplit > 1) {
+    const dim3 cgrid((unsigned)H, (unsigned)B, (unsigned)Tq);
+    if (D == 64)
+      hipLaunchKernelGGL(attn_kv_combine<64>, cgrid, dim3(64), 0, s, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot,
+                         a.oh);
+    else
+      hipLaunchKernelGGL(attn_kv_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot,
+                         a.oh);
+    e = hipGetLastError();
+  }
+  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
+// ---- append ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv, __bf16* __restrict__ kc,
+                                                 __bf16* __restrict__ vc, const int* __restrict__ pos, int B, int T,
+                                                 int H, int D8, int Tcap, long long qb, long long qt, long long kb,
+                                                 long long kh, long long kt, long long vb, long long vh,
+                                                 long long vt) {
+  const long long n = (long long)B * T * 2 * H * D8;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  long long r = idx;
+  const int d8 = (int)(r % D8);
+  r /= D8;
+  const int h = (int)(r % H);
+  r /= H;
+  const int s = (int)(r % 2);  // 0: k, 1: v
+  r /= 2;
+  const int t = (int)(r % T);
+  const int b = (int)(r / T);
+  const long long row = (long long)pos[b] + t;
+  if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, never written
+  const u32x4 val =
+      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)(s + 1) * H + h) * (D8 * 8) + d8 * 8);
+  __bf16* dst = s == 0 ? kc + b * kb + h * kh + row * kt : vc + b * vb + h * vh + row * vt;
+  *reinterpret_cast<u32x4*>(dst + d8 * 8) = val;
+}
+
+// One lane group (D / 8 lanes) per (b, t, k-or-v, h) row: a 16-B load of 8 bf16 per lane, the row's
+// amax by the group reduction, one scale store by the group's first lane, one 8-B code store per lane.
+// Groups are whole: the thread count is a multiple of D / 8 and so is the block size, and both early
+// returns are group-uniform.
+template <int D>
+__global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
+                                                     uint8_t* __restrict__ vc, float* __restrict__ ks,
+                                                     float* __restrict__ vs, const int* __restrict__ pos, int B, int T,
+                                                     int H, int Tcap, long long qb, long long qt, long long kb,
+                                                     long long kh, long long kt, long long vb, long long vh,
+                                                     long long vt, long long ksb, long long ksh, long long vsb,
+                                                     long long vsh) {
+  constexpr int G = D / 8;
+  const long long n = (long long)B * T * 2 * H * G;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  long long r = idx;
+  const int piece = (int)(r % G);
+  r /= G;
+  const int h = (int)(r % H);
+  r /= H;
+  const int s = (int)(r % 2);  // 0: k, 1: v
+  r /= 2;
+  const int t = (int)(r % T);
+  const int b = (int)(r / T);
+  const long long row = (long long)pos[b] + t;
+  if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, neither codes nor scale written
+  float x[8];
+  Bf16Rows::unpack8(
+      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)(s + 1) * H + h) * D + piece * 8), x);
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(x[i]));
+  am = kfw::group_max<G>(am);
+  const float scale = am > 0.f ? am / kFp8Max : 1.f;  // IEEE division: the torch reference's scale
+  float y[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(x[i] / scale, -kFp8Max), kFp8Max);
+  u32x2 w;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * i], y[4 * i + 1], 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * i + 2], y[4 * i + 3], p, true);
+    w[i] = (unsigned)p;
+  }
+  uint8_t* dst = s == 0 ? kc + b * kb + h * kh + row * kt : vc + b * vb + h * vh + row * vt;
+  *reinterpret_cast<u32x2*>(dst + piece * 8) = w;
+  if (piece == 0) {
+    float* sd = s == 0 ? ks + b * ksb + h * ksh : vs + b * vsb + h * vsh;
+    sd[row] = scale;
+  }
+}
+
+}  // namespace
+
+extern "C" int kfamd_attn_decode_split_keys(void) { return kSplitKeys; }
+
+extern "C" long long kfamd_attn_decode_workspace(int B, int H, int D, int t_bound) {
+  if (B <= 0 || H <= 0 || (D != 64 && D != 128) || t_bound < 1) return 0;
+  const long long nsplit = (t_bound + kSplitKeys - 1) / kSplitKeys;
+  return (long long)B * H * nsplit * (D + 2) * (long long)sizeof(float);
+}
+
+extern "C" long long kfamd_attn_extend_workspace(int B, int H, int D, int Tq, int t_bound) {
+  if (Tq < 1 || Tq > kMaxRows) return 0;
+  return kfamd_attn_decode_workspace(B, H, D, t_bound) * Tq;
+}
+
+// The four attention entry points (stride layouts: kfamd_kernels.h). Decode is Tq = 1 without t strides.
+extern "C" int kfamd_attn_decode_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                                      float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
+                                      const long long* st, void* stream) {
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, H, D, 1, t_bound, scale, st,
+                           false, stream);
+}
+
+extern "C" int kfamd_attn_extend_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                                      float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
+                                      const long long* st, void* stream) {
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, H, D, Tq, t_bound, scale, st,
+                           true, stream);
+}
+
+extern "C" int kfamd_attn_decode_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                     const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H,
+                                     int D, int t_bound, float scale, const long long* st, void* stream) {
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, H, D, 1, t_bound, scale, st,
+                          false, stream);
+}
+
+extern "C" int kfamd_attn_extend_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                     const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H,
+                                     int D, int Tq, int t_bound, float scale, const long long* st, void* stream) {
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, H, D, Tq, t_bound, scale, st,
+                          true, stream);
+}
+
+// K and V rows of a fused QKV activation [B][T][3][H][D] (element strides qb, qt; [3][H][D] dense)
+// into the caches [B][H][Tcap][D] (strides b, h, t) at rows pos[b] .. pos[b] + T - 1. pos: device
+// int32 [B], not advanced here. Rows at or beyond Tcap are dropped.
+extern "C" int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int H,
+                                    int D, int Tcap, long long qb, long long qt, const long long* cache_strides,
+                                    void* stream) {
+  if (!qkv || !k_cache || !v_cache || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 || D <= 0 || D % 8 ||
+      Tcap <= 0)
+    return KFAMD_EINVAL;
+  const long long* c = cache_strides;
+  if (!al16(qkv) || !al16(k_cache) || !al16(v_cache)) return KFAMD_EALIGN;
+  if ((qb | qt | c[0] | c[1] | c[2] | c[3] | c[4] | c[5]) & 7) return KFAMD_EALIGN;
+  const long long n = (long long)B * T * 2 * H * (D / 8);
+  if ((n + 255) / 256 > 0x7fffffffll) return KFAMD_EINVAL;
+  hipLaunchKernelGGL(kv_append, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const __bf16*>(qkv), static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos,
+                     B, T, H, D / 8, Tcap, qb, qt, c[0], c[1], c[2], c[3], c[4], c[5]);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
+// The same rows quantised row by row into codes [B][H][Tcap][D] and scales [B][H][Tcap].
+// cache_strides = {kb, kh, kt, vb, vh, vt, ksb, ksh, vsb, vsh}.
+extern "C" int kfamd_kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                   const int* pos, int B, int T, int H, int D, int Tcap, long long qb, long long qt,
+                                   const long long* cache_strides, void* stream) {
+  if (!qkv || !k_codes || !v_codes || !k_scale || !v_scale || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 ||
+      Tcap <= 0)
+    return KFAMD_EINVAL;
+  if (D != 64 && D != 128) return KFAMD_EINVAL;
+  const long long* c = cache_strides;
+  if (c[2] < D || c[5] < D) return KFAMD_EINVAL;
+  if (!al16(qkv) || !al16(k_codes) || !al16(v_codes) || !al4(k_scale) || !al4(v_scale)) return KFAMD_EALIGN;
+  if ((qb | qt) & 7) return KFAMD_EALIGN;
+  if ((c[0] | c[1] | c[2] | c[3] | c[4] | c[5]) & 15) return KFAMD_EALIGN;
+  const long long n = (long long)B * T * 2 * H * (D / 8);
+  if ((n + 255) / 256 > 0x7fffffffll) return KFAMD_EINVAL;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const __bf16* x = static_cast<const __bf16*>(qkv);
+  uint8_t* kc = static_cast<uint8_t*>(k_codes);
+  uint8_t* vc = static_cast<uint8_t*>(v_codes);
+  if (D == 64)
+    hipLaunchKernelGGL(kv_append_fp8<64>, grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, qb, qt,
+                       c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
+  else
+    hipLaunchKernelGGL(kv_append_fp8<128>, grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, qb,
+                       qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}

@@ -212,7 +212,8 @@ int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, const void*
                         int D, float scale, int causal, const long long* strides, void* stream);
 
 // ---- decode (KV-cache generation) ------------------------------------------------------------
-// Single-query attention over a KV cache (attn_decode_bf16.hip), bf16 I/O, fp32 softmax, D = 64 / 128.
+// Everything from here to the FP8 entry points is attn_kv.hip.
+// Single-query attention over a KV cache, bf16 I/O, fp32 softmax, D = 64 / 128.
 //   q [B][H][D] (element strides b, h), k_cache / v_cache [B][H][Tcap][D] (strides b, h, t),
 //   o [B][H][D] (strides b, h); head dim contiguous. strides = {qb, qh, kb, kh, kt, vb, vh, vt, ob, oh}.
 //   lens: DEVICE int32 [B]; row b attends keys 0 .. lens[b]-1 (clamped to t_bound). t_bound: host upper
@@ -225,8 +226,8 @@ long long kfamd_attn_decode_workspace(int B, int H, int D, int t_bound);
 int kfamd_attn_decode_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
                            float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
                            const long long* strides, void* stream);
-// Multi-query attention over the KV cache (attn_extend_bf16.hip): Tq (1 .. 16) new rows per (b, h), already
-// appended to the cache; K / V are streamed once per (b, h, split) for up to 8 rows (two split launches
+// Multi-query attention over the KV cache: Tq (1 .. 16) new rows per (b, h), already appended to
+// the cache; K / V are streamed once per (b, h, split) for up to 8 rows (two split launches
 // for Tq = 9 .. 16).
 //   q, o [B][Tq][H][D] (element strides b, t, h; head dim contiguous), caches as for decode.
 //   strides = {qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh}.
@@ -244,14 +245,8 @@ int kfamd_attn_extend_bf16(const void* q, const void* k_cache, const void* v_cac
 // kt, vb, vh, vt}. Rows at or beyond Tcap are dropped.
 int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int H, int D,
                          int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream);
-// The split merges of the two kernels above as launches of their own: they read only the fp32 workspace,
-// so the FP8-cache kernels below share them. No argument checks: the callers have made them.
-int kfamd_attn_decode_combine(const float* ws, void* o, float* lse, int B, int H, int D, int nsplit, long long ob,
-                              long long oh, void* stream);
-int kfamd_attn_extend_combine(const float* ws, void* o, float* lse, int B, int H, int D, int Tq, int nsplit,
-                              long long ob, long long ot, long long oh, void* stream);
 
-// ---- FP8 KV cache (attn_kv_fp8.hip) -----------------------------------------------------------
+// ---- FP8 KV cache (attn_kv.hip) ---------------------------------------------------------------
 // The cache stored as OCP e4m3fn codes [B][H][Tcap][D] (one byte per element, strides b, h, t in
 // elements = bytes, multiples of 16; base 16-B aligned) with one fp32 scale per stored row: k_scale /
 // v_scale [B][H][Tcap] (strides b, h in elements; positions contiguous). A row x[0..D) of bf16 values is

@@ -1,4 +1,4 @@
-"""KV-cache decode: the cache, the append and single-query attention (``kernels/attn_decode_bf16.hip``).
+"""KV-cache decode: the cache, the append and attention over it (``kernels/attn_kv.hip``).
 
 ``KVCache`` holds the per-layer K / V tensors ``[B, H, capacity, D]`` and the device-side ``lens``
 (``int32 [B]``): every kernel reads positions from ``lens``, so a decode step captured into a hipGraph
@@ -13,15 +13,15 @@ model step that appends T rows passes its attention ``lens=cache.lens_after(T)``
 calls ``cache.advance(T)`` (``lens.add_(T)``) once, after the last layer. The cache keeps no record of
 a step in flight.
 
-``attention_extend(q, cache, layer)`` is the multi-token form (``kernels/attn_extend_bf16.hip``): T <= 16
-new query rows per head, already appended, each attending the cache up to its own row; with
+``attention_extend(q, cache, layer)`` is the multi-token form (``attn_extend_split``, up to 8 row slots):
+T <= 16 new query rows per head, already appended, each attending the cache up to its own row; with
 ``KVCache.rewind(n)`` (drop the last n rows) it carries ``GPT.extend`` and draft-and-verify decoding.
 
 On CPU tensors the same functions run plain torch (index copy, masked fp32 SDPA): the CPU model path
 and its tests. On a GPU there is no fallback: a shape the kernels reject raises.
 
-``KVCache(..., dtype=torch.float8_e4m3fn)`` is the 8-bit cache (``kernels/attn_kv_fp8.hip``): ``k`` / ``v``
-hold OCP e4m3fn codes ``[B, H, capacity, D]`` and ``k_scale`` / ``v_scale`` one fp32 scale per stored row
+``KVCache(..., dtype=torch.float8_e4m3fn)`` is the 8-bit cache (the kernels' ``Fp8Rows`` format): ``k`` /
+``v`` hold OCP e4m3fn codes ``[B, H, capacity, D]`` and ``k_scale`` / ``v_scale`` one fp32 scale per stored row
 ``[B, H, capacity]``. ``kv_append`` quantises each K / V row on the way in (``quantize_rows``: ``scale =
 amax / 448``, ``code = RNE_e4m3(clamp(x / scale, -448, 448))``, an all-zero row stores ``scale = 1``); the
 attention kernels multiply the scales in (``(q . codes_k[j]) * k_scale[j]``, ``p * v_scale[j]``) and never
@@ -73,6 +73,14 @@ def _native(t: torch.Tensor) -> bool:
 
 def _ll(*vals) -> "ctypes.Array":
     return (ctypes.c_longlong * len(vals))(*(int(v) for v in vals))
+
+
+def _entry(name: str, cache: "KVCache", layer: int):
+    """The entry point ``name`` for the cache's dtype: (function, the scale tensors an FP8 cache adds to the
+    pointers and strides, the tag of its error messages)."""
+    if cache.fp8:
+        return getattr(_lib.lib(), name + "_fp8"), (cache.k_scale[layer], cache.v_scale[layer]), "fp8 "
+    return getattr(_lib.lib(), name + "_bf16"), (), ""
 
 
 def quantize_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -210,20 +218,13 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
         return
     if qkv.dtype != torch.bfloat16 or qkv.stride(2) != 1:
         raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
-    if cache.fp8:
-        if D not in HEAD_DIMS:
-            raise ValueError(f"kv_append: head dim in {HEAD_DIMS} expected for an FP8 cache on a GPU, got {D}")
-        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
-        rc = _lib.lib().kfamd_kv_append_fp8(
-            qkv.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(), cache.lens.data_ptr(), B, T, H, D,
-            cache.capacity, qkv.stride(0), qkv.stride(1),
-            _ll(*k.stride()[:3], *v.stride()[:3], *ks.stride()[:2], *vs.stride()[:2]), _stream_ptr(qkv))
-        _lib.check(rc, f"kv_append[fp8 B={B} T={T} H={H} D={D}]")
-        return
-    rc = _lib.lib().kfamd_kv_append_bf16(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), cache.lens.data_ptr(), B, T, H, D,
-                                         cache.capacity, qkv.stride(0), qkv.stride(1),
-                                         _ll(*k.stride()[:3], *v.stride()[:3]), _stream_ptr(qkv))
-    _lib.check(rc, f"kv_append[B={B} T={T} H={H} D={D}]")
+    if cache.fp8 and D not in HEAD_DIMS:
+        raise ValueError(f"kv_append: head dim in {HEAD_DIMS} expected for an FP8 cache on a GPU, got {D}")
+    fn, scales, tag = _entry("kfamd_kv_append", cache, layer)
+    rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(), B, T, H,
+            D, cache.capacity, qkv.stride(0), qkv.stride(1),
+            _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
+    _lib.check(rc, f"kv_append[{tag}B={B} T={T} H={H} D={D}]")
 
 
 def _kv_append_fp8_torch(x, cache: KVCache, layer: int) -> None:
@@ -300,20 +301,12 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     elif tuple(out.shape) != (B, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
         raise ValueError(f"attention_decode: out must be a bf16 GPU [{B}, {H}, {D}] view with a contiguous head dim")
     lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
-    if cache.fp8:
-        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
-        rc = _lib.lib().kfamd_attn_decode_fp8(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(), lens.data_ptr(), out.data_ptr(),
+    fn, scales, tag = _entry("kfamd_attn_decode", cache, layer)
+    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
             lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
             _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
-                *ks.stride()[:2], *vs.stride()[:2]), _stream_ptr(q))
-        _lib.check(rc, f"attention_decode[fp8 B={B} H={H} D={D} t_bound={t_bound}]")
-        return (out, lse) if return_lse else out
-    rc = _lib.lib().kfamd_attn_decode_bf16(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), lens.data_ptr(), out.data_ptr(),
-        lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
-        _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1)), _stream_ptr(q))
-    _lib.check(rc, f"attention_decode[B={B} H={H} D={D} t_bound={t_bound}]")
+                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
+    _lib.check(rc, f"attention_decode[{tag}B={B} H={H} D={D} t_bound={t_bound}]")
     return (out, lse) if return_lse else out
 
 
@@ -340,7 +333,7 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     layer ``layer``. ``lens[b]`` counts the keys INCLUDING the T new rows; row i attends keys
     ``0 .. lens[b] - T + i`` (a row whose limit is negative gives zeros, lse = -inf). ``out``: optional
     ``[B, T, H, D]`` view to write. ``lens`` / ``t_bound`` default to the cache's. K and V are read once
-    per 8 query rows (``kernels/attn_extend_bf16.hip``)."""
+    per 8 query rows (``kernels/attn_kv.hip``)."""
     B, H, D = cache.B, cache.H, cache.D
     if q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (H, D):
         raise ValueError(f"attention_extend: q [{B}, T, {H}, {D}] expected, got {tuple(q.shape)}")
@@ -376,18 +369,10 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         raise ValueError(f"attention_extend: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
                          "head dim")
     lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
-    if cache.fp8:
-        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
-        rc = _lib.lib().kfamd_attn_extend_fp8(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(), lens.data_ptr(), out.data_ptr(),
+    fn, scales, tag = _entry("kfamd_attn_extend", cache, layer)
+    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
             lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, H, D, T, t_bound, scale,
-            _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3], *ks.stride()[:2],
-                *vs.stride()[:2]), _stream_ptr(q))
-        _lib.check(rc, f"attention_extend[fp8 B={B} T={T} H={H} D={D} t_bound={t_bound}]")
-        return (out, lse) if return_lse else out
-    rc = _lib.lib().kfamd_attn_extend_bf16(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), lens.data_ptr(), out.data_ptr(),
-        lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, H, D, T, t_bound, scale,
-        _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3]), _stream_ptr(q))
-    _lib.check(rc, f"attention_extend[B={B} T={T} H={H} D={D} t_bound={t_bound}]")
+            _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
+                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
+    _lib.check(rc, f"attention_extend[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")
     return (out, lse) if return_lse else out

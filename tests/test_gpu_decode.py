@@ -1,5 +1,5 @@
 """KV-cache decode on the gfx950 kernels: single-query split-KV attention and the KV append
-(kernels/attn_decode_bf16.hip), the M <= 16 weight-streaming GEMM (kernels/gemm_skinny_bf16.hip),
+(kernels/attn_kv.hip), the M <= 16 weight-streaming GEMM (kernels/gemm_skinny_bf16.hip),
 and GPT.prefill / decode_step / generate built on them, against fp32 references."""
 from __future__ import annotations
 

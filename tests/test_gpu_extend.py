@@ -1,4 +1,4 @@
-"""Multi-token KV-cache steps on the gfx950 kernels: attention_extend (kernels/attn_extend_bf16.hip: Tq <= 16
+"""Multi-token KV-cache steps on the gfx950 kernels: attention_extend (kernels/attn_kv.hip: Tq <= 16
 new query rows per head over the cache, causal inside the new block), KVCache.rewind, GPT.extend and
 draft-and-verify generate, against fp32 references."""
 from __future__ import annotations

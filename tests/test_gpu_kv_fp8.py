@@ -1,4 +1,4 @@
-"""The FP8 KV cache on the gfx950 kernels (kernels/attn_kv_fp8.hip): the quantising append against the
+"""The FP8 KV cache on the gfx950 kernels (kernels/attn_kv.hip): the quantising append against the
 torch reference of the format, decode and extend attention against fp32 SDPA over the DEQUANTISED cache
 (which isolates the kernels from the quantisation error: the project's bf16 bounds apply unchanged), and
 GPT.prefill / decode_step / extend / generate with kv_dtype=torch.float8_e4m3fn."""
