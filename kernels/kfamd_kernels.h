@@ -283,6 +283,23 @@ int kfamd_gemm_nt_skinny_bf16_path(int path, const void* A, const void* W, void*
                                    int M, int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
                                    float alpha, int act, void* stream);
 
+// The same on 8-bit weights, W8A16 (gemm_skinny_w8.hip): C[M][N] = act(alpha * wscale[n] * (A[M][K] .
+// codes[N][K]^T) + bias[n]) (+ R[M][N]). codes: OCP e4m3fn bytes, row stride ldw BYTES; wscale: fp32 [N],
+// contiguous, required (the format of the FP8 KV cache's rows). K >= 16, K % 16 == 0, codes 16-B aligned,
+// ldw % 16 == 0, A as above. NaN codes (0x7F, 0xFF) are out of contract. Return codes and path as the
+// bf16 kernel's.
+int kfamd_gemm_nt_skinny_w8(const void* A, const void* codes, const float* wscale, void* C, const void* bias,
+                            const void* R, int M, int N, int K, long long lda, long long ldw, long long ldc,
+                            long long ldr, float alpha, int act, void* stream);
+int kfamd_gemm_nt_skinny_w8_path(int path, const void* A, const void* codes, const float* wscale, void* C,
+                                 const void* bias, const void* R, int M, int N, int K, long long lda, long long ldw,
+                                 long long ldc, long long ldr, float alpha, int act, void* stream);
+// bench only: also forces the MFMA form's 8-row tiles per workgroup (1, 2, 4) or the VALU form's weight
+// rows per wave (2, 4); tiles = 0 selects by N as the other two entry points do
+int kfamd_gemm_nt_skinny_w8_tiles(int path, int tiles, const void* A, const void* codes, const float* wscale,
+                                  void* C, const void* bias, const void* R, int M, int N, int K, long long lda,
+                                  long long ldw, long long ldc, long long ldr, float alpha, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

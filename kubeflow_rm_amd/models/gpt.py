@@ -15,6 +15,8 @@ On CPU tensors the same module runs torch's reference ops (used by the gloo test
 Sampling: ``GPT.generate`` (``prefill`` + ``decode_step`` over an ``ops.KVCache``) runs each new token
 on the decode kernels — the M <= 16 weight-streaming GEMM, the KV append and split-KV single-query
 attention — and can replay the step as one hipGraph (no tensor-parallel group; head dims 64 / 128).
+``GPT.decode_weights()`` / ``generate(weight_dtype=torch.float8_e4m3fn)`` run the steps of up to 16 rows on
+8-bit copies of the projection weights (W8A16: bf16 activations, fp32 accumulation).
 """
 from __future__ import annotations
 
@@ -176,6 +178,34 @@ def _sample(logits, temperature, top_k, generator):
     return torch.multinomial(torch.softmax(logits.float() / temperature, -1), 1, generator=generator).squeeze(1)
 
 
+_LINEARS = ("qkv", "proj", "fc1", "fc2")
+
+
+class DecodeWeights:
+    """8-bit copies of a ``GPT``'s projection weights for the KV-cache steps (``GPT.decode_weights``):
+    ``blocks[i]`` maps "qkv" / "proj" / "fc1" / "fc2" to an ``ops.QuantizedWeight``, ``head`` is the
+    quantised LM head (the tied embedding; the embedding gather itself keeps the model's ``tok``). The
+    biases are the model's own. Plain tensors: neither parameters nor buffers."""
+
+    def __init__(self, blocks: list, head, key: tuple):
+        self.blocks, self.head, self._key = blocks, head, key
+
+    def matrices(self) -> list:
+        return [b[n] for b in self.blocks for n in _LINEARS] + [self.head]
+
+    @property
+    def nbytes(self) -> int:
+        """The sum of the quantised matrices' ``nbytes`` (codes + fp32 row scales)."""
+        return sum(q.nbytes for q in self.matrices())
+
+
+def _flinear(x, w, bias=None):
+    """``F.linear`` of the torch path; a ``QuantizedWeight`` enters as its dequantised value in x's dtype."""
+    if isinstance(w, ops.QuantizedWeight):
+        w = w.dequantize().to(x.dtype)
+    return F.linear(x, w, bias)
+
+
 class _GraphedDecodeStep:
     """A captured ``decode_step``: the replay runs no Python of the step, so the capacity check and the
     host-side bound of ``decode_step`` are kept here (``cache.lens`` may never pass the capacity: the
@@ -301,13 +331,61 @@ class GPT(torch.nn.Module):
         # more than 16 rows (extend with B * T > 16): the "auto" route, as prefill
         return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual)
 
+    # ---- 8-bit decode weights ---------------------------------------------------------------------
+    def decode_weights(self, dtype: torch.dtype = torch.float8_e4m3fn) -> DecodeWeights:
+        """8-bit copies (``ops.quantize_weight``: e4m3fn codes + one fp32 scale per output row) of every
+        block's qkv / proj / fc1 / fc2 weight and of the LM head, for ``decode_step`` / ``extend`` /
+        ``graphed_decode_step`` / ``generate``. With a tensor-parallel group that issues no collective the
+        local shards are quantised. The biases and the embedding gather keep the model's tensors.
+
+        The copies are plain tensors, absent from ``state_dict()`` and from any optimiser. The result is
+        memoised on the model, keyed by the source parameters' ``_version`` (and storage): a call after an
+        in-place update (a training step) requantises what changed and returns a new object. An object kept
+        across an update is stale and out of contract: ask the model again after training.
+
+        Which steps read them: those of up to 16 rows, see ``extend``; ``prefill`` never does."""
+        if dtype != torch.float8_e4m3fn:
+            raise ValueError(f"decode_weights: torch.float8_e4m3fn expected, got {dtype}")
+        srcs = [getattr(blk, n).weight for blk in self.blocks for n in _LINEARS] + [self.tok]
+        key = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in srcs)
+        memo = self.__dict__.get("_decode_weights")
+        if memo is not None and memo._key == key:
+            return memo
+        old = memo.matrices() if memo is not None and len(memo._key) == len(key) else [None] * len(srcs)
+        with torch.no_grad():
+            qs = [q if q is not None and memo._key[i] == key[i] else ops.quantize_weight(p.detach())
+                  for i, (p, q) in enumerate(zip(srcs, old))]
+        n = len(_LINEARS)
+        blocks = [dict(zip(_LINEARS, qs[i * n:(i + 1) * n])) for i in range(len(self.blocks))]
+        memo = DecodeWeights(blocks, qs[-1], key)
+        self.__dict__["_decode_weights"] = memo  # not a parameter, buffer or submodule
+        return memo
+
+    def _weight_selector(self, weights, rows: int):
+        """(layer, name) -> the weight a step of ``rows`` rows reads in that linear: the 8-bit one when
+        ``weights`` is given and the step takes the weight-streaming route (rows <= 16), else the model's."""
+        if weights is not None and not isinstance(weights, DecodeWeights):
+            raise TypeError("weights: a DecodeWeights (GPT.decode_weights()) expected")
+        if weights is None or rows > ops.gemm.SKINNY_MAX_M:
+            return lambda li, name: getattr(self.blocks[li], name).weight
+        if len(weights.blocks) != len(self.blocks):
+            raise ValueError("weights do not match the model")
+        return lambda li, name: weights.blocks[li][name]
+
+    def _head_weight(self, weights, rows: int):
+        return self.tok if weights is None or rows > ops.gemm.SKINNY_MAX_M else weights.head
+
     @torch.no_grad()
-    def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
-        """One new token ``tok [B]`` per row against ``cache``; logits ``[B, vocab]``. Advances the cache."""
+    def decode_step(self, tok: torch.Tensor, cache, weights: "DecodeWeights | None" = None) -> torch.Tensor:
+        """One new token ``tok [B]`` per row against ``cache``; logits ``[B, vocab]``. Advances the cache.
+        ``weights`` (``decode_weights()``): a step of B <= 16 rows reads the 8-bit weights in every linear and
+        in the LM head; a wider batch reads the bf16 weights (the rule of ``extend``)."""
         B = tok.shape[0]
         self._check_cache(cache, B, 1)
         native = self._native_decode(self.tok)
         c = self.cfg
+        wsel = self._weight_selector(weights, B)
+        head_w = self._head_weight(weights, B)
         x = F.embedding(tok, self.tok) + F.embedding(cache.lens, self.pos)  # [B, d_model]
         # the step's attention sees the row it appends: lens + 1, computed on the device
         att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1)}
@@ -315,34 +393,41 @@ class GPT(torch.nn.Module):
             h, hd = blk.local_heads, c.head_dim
             if native:
                 y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
-                qkv = self._skinny(y, blk.qkv.weight, blk.qkv.bias)  # [B, 3 * h * hd]
+                qkv = self._skinny(y, wsel(li, "qkv"), blk.qkv.bias)  # [B, 3 * h * hd]
                 ops.kv_append(qkv.view(B, 1, 3 * h * hd), cache, li)
                 a = torch.empty(B, h * hd, device=x.device, dtype=x.dtype)
                 ops.attention_decode(qkv.view(B, 3, h, hd)[:, 0], cache, li, out=a.view(B, h, hd), **att)
-                x = self._skinny(a, blk.proj.weight, blk.proj.bias, residual=x)
+                x = self._skinny(a, wsel(li, "proj"), blk.proj.bias, residual=x)
                 y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
-                y = self._skinny(y, blk.fc1.weight, blk.fc1.bias, act=blk.fc1.act)
-                x = self._skinny(y, blk.fc2.weight, blk.fc2.bias, residual=x)
+                y = self._skinny(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
+                x = self._skinny(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
-                qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
+                qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
                 ops.kv_append(qkv.view(B, 1, -1), cache, li)  # torch ops: CPU tensors / torch_reference()
                 a = ops.attention_decode(qkv.view(B, 3, h, hd)[:, 0], cache, li, **att).reshape(B, h * hd)
-                x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
-                y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
-                x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
+                x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
+                y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
+                x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
         cache.advance(1)
         if native:
-            return self._skinny(ops.layer_norm_fwd(x, self.ln_f.weight, self.ln_f.bias)[0], self.tok)
-        return F.linear(self.ln_f(x), self.tok)
+            return self._skinny(ops.layer_norm_fwd(x, self.ln_f.weight, self.ln_f.bias)[0], head_w)
+        return _flinear(self.ln_f(x), head_w)
 
     @torch.no_grad()
-    def extend(self, idx: torch.Tensor, cache, last_only: bool = False) -> torch.Tensor:
+    def extend(self, idx: torch.Tensor, cache, last_only: bool = False,
+               weights: "DecodeWeights | None" = None) -> torch.Tensor:
         """Append ``idx [B, T]`` (T >= 1 tokens per row) to ``cache`` in any state, empty included; logits
         ``[B, T, vocab]`` of every new position (``[B, vocab]`` of the last one with ``last_only``).
         Advances the cache by T. On the GPU a step of up to 16 tokens runs the decode kernels with
         ``ops.attention_extend`` (K / V read once per 8 new rows; the weight-streaming GEMM while
         B * T <= 16); longer inputs run in chunks of 16. Like ``decode_step`` it reads the position
-        from the device-side ``cache.lens`` only, so a fixed T <= 16 can be captured into a hipGraph."""
+        from the device-side ``cache.lens`` only, so a fixed T <= 16 can be captured into a hipGraph.
+
+        ``weights`` (``decode_weights()``): a chunk whose linears take the weight-streaming route, B * T <= 16
+        rows, reads the 8-bit weights; the LM head does by its own row count (B with ``last_only``). Chunks
+        with more rows read the bf16 weights, as ``prefill`` always does (compute-bound, and the originals
+        are there). The rule looks at row counts only, on every device: the CPU / ``ops.torch_reference()``
+        path applies it with the dequantised weights."""
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError(f"extend: idx [B, T >= 1] expected, got {tuple(idx.shape)}")
         B, T = idx.shape
@@ -353,12 +438,13 @@ class GPT(torch.nn.Module):
         for t0 in range(0, T, R):
             final = t0 + R >= T
             if last_only and not final:
-                self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none")
+                self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none", weights=weights)
             else:
-                outs.append(self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="last" if last_only else "all"))
+                outs.append(self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="last" if last_only else "all",
+                                               weights=weights))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
 
-    def _extend_chunk(self, idx, cache, native: bool, head: str):
+    def _extend_chunk(self, idx, cache, native: bool, head: str, weights=None):
         """One extend step of T <= 16 tokens per row; ``head``: LM head on "all" rows, the "last", or "none"."""
         B, T = idx.shape
         c = self.cfg
@@ -367,41 +453,44 @@ class GPT(torch.nn.Module):
         # the step's attention sees the rows it appends: lens + T, computed on the device
         att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T)}
         lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
+        wsel = self._weight_selector(weights, B * T)
         if native:
             x = x.reshape(B * T, c.d_model)
         for li, blk in enumerate(self.blocks):
             h, hd = blk.local_heads, c.head_dim
             if native:
                 y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
-                qkv = lin(y, blk.qkv.weight, blk.qkv.bias).view(B, T, 3 * h * hd)
+                qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, 3 * h * hd)
                 ops.kv_append(qkv, cache, li)
                 a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
                 ops.attention_extend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, out=a.view(B, T, h, hd), **att)
-                x = lin(a.view(B * T, h * hd), blk.proj.weight, blk.proj.bias, residual=x)
+                x = lin(a.view(B * T, h * hd), wsel(li, "proj"), blk.proj.bias, residual=x)
                 y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
-                y = lin(y, blk.fc1.weight, blk.fc1.bias, act=blk.fc1.act)
-                x = lin(y, blk.fc2.weight, blk.fc2.bias, residual=x)
+                y = lin(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
+                x = lin(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
-                qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
+                qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
                 ops.kv_append(qkv, cache, li)  # torch ops: CPU tensors / torch_reference()
                 a = ops.attention_extend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, **att).reshape(B, T, h * hd)
-                x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
-                y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
-                x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
+                x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
+                y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
+                x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
         cache.advance(T)
         if head == "none":
             return None
         x = x.view(B, T, c.d_model)
         if head == "last":
             x = x[:, -1].contiguous()  # [B, d_model]
+        head_w = self._head_weight(weights, x.numel() // c.d_model)
         if not native:
-            return F.linear(self.ln_f(x), self.tok)
+            return _flinear(self.ln_f(x), head_w)
         rows = x.reshape(-1, c.d_model)
         head_lin = self._skinny if rows.shape[0] <= ops.gemm.SKINNY_MAX_M else self._auto
-        logits = head_lin(ops.layer_norm_fwd(rows, self.ln_f.weight, self.ln_f.bias)[0], self.tok)
+        logits = head_lin(ops.layer_norm_fwd(rows, self.ln_f.weight, self.ln_f.bias)[0], head_w)
         return logits.view(*x.shape[:-1], c.vocab_size)
 
-    def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int, kv_dtype=None):
+    def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int, kv_dtype=None, tw=None,
+                        dw=None):
         """Greedy draft-and-verify for one sequence: per round the draft proposes up to ``lookahead``
         tokens (``decode_step`` on its own cache), the target scores ``[last accepted, proposals...]`` in
         ONE ``extend`` and keeps the longest prefix that equals its own argmax, plus its own next token
@@ -420,10 +509,10 @@ class GPT(torch.nn.Module):
             last = torch.tensor([seq[-1]], dtype=idx.dtype, device=idx.device)
             props, tok = [], last
             for _ in range(K):
-                tok = draft.decode_step(tok, dc).argmax(-1)
+                tok = draft.decode_step(tok, dc, weights=dw).argmax(-1)
                 props.append(tok)
             row = torch.cat([last, *props]).view(1, K + 1)
-            want = self.extend(row, tc).argmax(-1)[0].tolist()  # the target's token after each row
+            want = self.extend(row, tc, weights=tw).argmax(-1)[0].tolist()  # the target's token after each row
             prop = row[0, 1:].tolist()
             n = 0
             while n < K and prop[n] == want[n]:
@@ -431,7 +520,7 @@ class GPT(torch.nn.Module):
             seq += prop[:n] + [want[n]]
             tc.rewind(K - n)  # the cache keeps [last, accepted proposals]
             if K > 0 and n == K:
-                draft.decode_step(props[-1], dc)  # the draft has not seen its own last proposal yet
+                draft.decode_step(props[-1], dc, weights=dw)  # the draft has not seen its own last proposal yet
             elif K > 0:
                 dc.rewind(K - 1 - n)  # the draft's cache holds [last, proposals but the final one]
             stats["target_steps"] += 1
@@ -442,7 +531,8 @@ class GPT(torch.nn.Module):
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
-                 lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None):
+                 lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None,
+                 weight_dtype: torch.dtype | None = None):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -453,7 +543,14 @@ class GPT(torch.nn.Module):
         returns ``{"target_steps", "proposed", "accepted"}``.
 
         ``kv_dtype``: what the KV cache stores (``new_cache``); ``torch.float8_e4m3fn`` halves its bytes.
-        With a draft, both the target's and the draft's caches use it."""
+        With a draft, both the target's and the draft's caches use it.
+
+        ``weight_dtype``: ``torch.float8_e4m3fn`` decodes on ``self.decode_weights()`` (and the draft on its
+        own): every step of up to 16 rows reads 8-bit projection weights and LM head, half the bytes of a
+        small-batch step; the prompt's ``prefill`` and steps of more rows read the bf16 weights. It combines
+        freely with ``kv_dtype`` and ``graph``. Any other dtype raises."""
+        if weight_dtype is not None and weight_dtype != torch.float8_e4m3fn:
+            raise ValueError(f"generate(weight_dtype=...): None or torch.float8_e4m3fn expected, got {weight_dtype}")
         B, T0 = idx.shape
         total = T0 + max_new_tokens
         if max_new_tokens < 0 or T0 < 1 or total > self.cfg.max_seq:
@@ -467,7 +564,9 @@ class GPT(torch.nn.Module):
             if total > draft.cfg.max_seq:
                 raise ValueError(f"prompt + max_new_tokens must fit the draft's max_seq {draft.cfg.max_seq}")
             out, stats = ((idx.clone(), {"target_steps": 0, "proposed": 0, "accepted": 0}) if max_new_tokens == 0
-                          else self._generate_draft(idx, max_new_tokens, draft, int(lookahead), kv_dtype))
+                          else self._generate_draft(idx, max_new_tokens, draft, int(lookahead), kv_dtype,
+                                                    self.decode_weights() if weight_dtype is not None else None,
+                                                    draft.decode_weights() if weight_dtype is not None else None))
             return (out, stats) if return_stats else out
         if return_stats:
             raise ValueError("generate(return_stats=True) reports draft decoding: pass draft=")
@@ -477,9 +576,10 @@ class GPT(torch.nn.Module):
             raise ValueError("generate(graph=True) needs GPU tensors")
         cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
         logits = self.prefill(idx, cache)
-        step = lambda t: self.decode_step(t, cache)  # noqa: E731
+        weights = self.decode_weights() if weight_dtype is not None else None
+        step = lambda t: self.decode_step(t, cache, weights=weights)  # noqa: E731
         if graph and max_new_tokens > 1:
-            step = self.graphed_decode_step(cache)
+            step = self.graphed_decode_step(cache, weights=weights)
         out = [idx]
         for i in range(max_new_tokens):
             nxt = _sample(logits, temperature, top_k, generator)
@@ -488,12 +588,13 @@ class GPT(torch.nn.Module):
                 logits = step(nxt)
         return torch.cat(out, 1)
 
-    def graphed_decode_step(self, cache) -> "_GraphedDecodeStep":
+    def graphed_decode_step(self, cache, weights: "DecodeWeights | None" = None) -> "_GraphedDecodeStep":
         """``decode_step`` on ``cache`` captured once into a hipGraph (its attention grid sized for the
         whole capacity); each call replays it on a new token ``[B]`` and returns the logits, valid until
         the next call. The position lives in the device-side ``cache.lens``, which the replay advances;
         the host-side bound follows, and a call with no free cache row raises like ``decode_step``. The
-        cache needs one free row for the warm-up step, whose effect on ``lens`` is undone here."""
+        cache needs one free row for the warm-up step, whose effect on ``lens`` is undone here. ``weights``: as
+        ``decode_step``; the graph holds the quantised tensors' addresses, so keep the object alive."""
         if cache._bound + 1 > cache.capacity:
             raise ValueError("graphed_decode_step needs a free cache row")
         cache.pin_bound()
@@ -501,13 +602,15 @@ class GPT(torch.nn.Module):
 
         def step(t):  # warm-up and capture both start from the same host bound
             cache._bound = bound
-            return self.decode_step(t, cache)
+            return self.decode_step(t, cache, weights=weights)
 
         g = ops.GraphedCallable(step, torch.zeros(cache.B, dtype=torch.long, device=cache.lens.device), warmup=1)
         torch.cuda.current_stream().synchronize()
         cache.lens.copy_(saved)
         cache._bound = bound
-        return _GraphedDecodeStep(g, cache)
+        gs = _GraphedDecodeStep(g, cache)
+        gs.weights = weights  # the captured kernels read these tensors: they live as long as the step
+        return gs
 
     def flops_per_token(self, seq: int) -> float:
         """Training FLOPs/token (fwd+bwd = 3x fwd): dense matmuls + attention scores."""

@@ -106,6 +106,12 @@ _SIGNATURES = {
                                           c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_bf16_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,
                                                c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_w8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
+                                        c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_w8_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,
+                                             c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_w8_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                              c_ll, c_ll, c_ll, c_ll, c_float, c_int, c_vp]),
     "kfamd_build_info": (ctypes.c_char_p, []),
 }
 

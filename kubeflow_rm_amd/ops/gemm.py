@@ -12,12 +12,104 @@ import os
 import torch
 
 from . import _lib
+from .decode import dequantize_rows, quantize_rows
 
 ACTS = {"none": 0, "relu": 1, "gelu_tanh": 2, "gelu": 2, "silu": 3}
 VARIANTS = {"auto": 0, "fast": 1, "generic": 2, "pipe": 3, "pipe_sched": 4, "w4": 6, "w4s": 9}
 # the M <= 16 weight-streaming kernel: "skinny" picks VALU / MFMA by M, the other two force one (bench)
 SKINNY_PATHS = {"skinny": 0, "skinny_valu": 1, "skinny_mfma": 2}
 SKINNY_MAX_M = 16
+FP8 = torch.float8_e4m3fn
+
+
+class QuantizedWeight:
+    """An 8-bit weight ``[N, K]`` for ``gemm_nt``'s weight-streaming kernel (W8A16,
+    ``kernels/gemm_skinny_w8.hip``): ``codes [N, K]`` ``float8_e4m3fn`` and ``scale [N]`` fp32, one per
+    output row, in the format of the FP8 KV cache's rows (``ops.decode.quantize_rows``). The weight it
+    stands for is ``dequantize()``: ``codes * scale``. NaN codes are out of contract."""
+
+    def __init__(self, codes: torch.Tensor, scale: torch.Tensor):
+        if codes.dim() != 2 or codes.dtype != FP8:
+            raise ValueError(f"QuantizedWeight: codes [N, K] float8_e4m3fn expected, got {tuple(codes.shape)} "
+                             f"{codes.dtype}")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (codes.shape[0],) or scale.device != codes.device:
+            raise ValueError(f"QuantizedWeight: scale fp32 [{codes.shape[0]}] on {codes.device} expected, got "
+                             f"{tuple(scale.shape)} {scale.dtype} on {scale.device}")
+        self.codes, self.scale = codes, scale
+
+    @property
+    def shape(self) -> torch.Size:
+        return self.codes.shape
+
+    @property
+    def device(self) -> torch.device:
+        return self.codes.device
+
+    @property
+    def nbytes(self) -> int:
+        """N * K code bytes + 4 * N scale bytes."""
+        return self.codes.numel() + 4 * self.scale.numel()
+
+    def dequantize(self) -> torch.Tensor:
+        """The fp32 weight ``codes * scale`` the kernel multiplies by."""
+        return dequantize_rows(self.codes, self.scale)
+
+
+def quantize_weight(w: torch.Tensor) -> QuantizedWeight:
+    """A bf16 or fp32 weight ``[N, K]`` (CPU or GPU) as a ``QuantizedWeight``: exactly
+    ``ops.decode.quantize_rows(w)``, i.e. scale = row amax / 448 (1 for a zero row), codes =
+    RNE_e4m3(clamp(w / scale, -448, 448))."""
+    if w.dim() != 2 or w.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"quantize_weight: a 2-D bf16 or fp32 tensor expected, got {tuple(w.shape)} {w.dtype}")
+    codes, scale = quantize_rows(w.detach())
+    return QuantizedWeight(codes.contiguous(), scale.contiguous())
+
+
+def _gemm_nt_w8(a, qw: QuantizedWeight, bias, residual, alpha, act, out, variant, tiles: int = 0):
+    """gemm_nt on a QuantizedWeight: the W8A16 weight-streaming kernel or an error, never a dequantised copy."""
+    if variant not in SKINNY_PATHS:
+        raise ValueError(f"gemm_nt with a QuantizedWeight runs the weight-streaming kernel only: variant in "
+                         f"{sorted(SKINNY_PATHS)} expected, got {variant!r}")
+    _check_operand(a, "a")
+    codes, scale = qw.codes, qw.scale
+    if not codes.is_cuda or codes.device != a.device:
+        raise ValueError("gemm_nt: the QuantizedWeight must live on a's GPU")
+    N, K = codes.shape
+    if a.shape[-1] != K:
+        raise ValueError(f"inner dims differ: a has K={a.shape[-1]}, the weight has K={K}")
+    a2 = a.reshape(-1, K) if a.dim() != 2 else a
+    if a2.stride(-1) != 1:
+        a2 = a2.contiguous()
+    M = a2.shape[0]
+    if not 1 <= M <= SKINNY_MAX_M or K < 16 or K % 16:
+        raise ValueError(f"gemm_nt[w8] variant={variant!r}: 1 <= M <= {SKINNY_MAX_M}, K >= 16 and K % 16 == 0 expected, "
+                         f"got M={M} K={K}")
+    if codes.stride(1) != 1 or not scale.is_contiguous():
+        raise ValueError("gemm_nt[w8]: codes with a unit inner stride and a contiguous scale expected")
+    out_shape = (*a.shape[:-1], N)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.bfloat16, device=a.device)
+    else:
+        _check_operand(out, "out")
+        if out.device != a.device or tuple(out.shape) != tuple(out_shape):
+            raise ValueError(f"out must be a bf16 {tuple(out_shape)} tensor on {a.device}, got {tuple(out.shape)} on "
+                             f"{out.device}")
+    c2 = out.view(M, N)
+    if bias is not None:
+        _check_operand(bias, "bias")
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError("bias must be a contiguous [N] tensor")
+    r_ptr, ldr = None, 0
+    if residual is not None:
+        _check_operand(residual, "residual")
+        r2 = residual.reshape(M, N)
+        r_ptr, ldr = r2.data_ptr(), r2.stride(0)
+    rc = _lib.lib().kfamd_gemm_nt_skinny_w8_tiles(
+        SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), codes.data_ptr(), scale.data_ptr(), c2.data_ptr(),
+        bias.data_ptr() if bias is not None else None, r_ptr, M, N, K, a2.stride(0), codes.stride(0), c2.stride(0), ldr,
+        float(alpha), ACTS[act], _stream_ptr(a))
+    _lib.check(rc, f"gemm_nt[skinny w8 {M}x{N}x{K}]")
+    return out
 
 
 def _stream_ptr(t: torch.Tensor) -> int:
@@ -104,10 +196,14 @@ def _gemm_nt_padded(a3, b, bias, residual, alpha, act, out, batched, batch, M, N
     return out
 
 
-def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias: torch.Tensor | None = None,
+def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight", *, bias: torch.Tensor | None = None,
             residual: torch.Tensor | None = None, alpha: float = 1.0, act: str = "none",
             out: torch.Tensor | None = None, variant: str = "auto") -> torch.Tensor:
-    """C = act(alpha * a @ b^T + bias) (+ residual). a: [..., M, K] or [B, M, K]; b: [N, K] or [B, N, K]."""
+    """C = act(alpha * a @ b^T + bias) (+ residual). a: [..., M, K] or [B, M, K]; b: [N, K] or [B, N, K].
+    ``b`` may be a ``QuantizedWeight`` with ``variant`` "skinny" / "skinny_valu" / "skinny_mfma" (M <= 16, K % 16 == 0):
+    the W8A16 weight-streaming kernel; every other variant or shape raises ``ValueError``."""
+    if isinstance(b, QuantizedWeight):
+        return _gemm_nt_w8(a, b, bias, residual, alpha, act, out, variant)
     _check_operand(a, "a")
     _check_operand(b, "b")
     batched = b.dim() == 3

@@ -24,6 +24,14 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         {4, 8} (D = 128, capacity 4096, B*H in {16, 128}, lens in {128, 2048, 4096}); ops.kv_append at T in
         {1, 2048}; gpt-1b (gpt-small with --quick) end to end in ms/token at B in {1, 16}, eager and
         graphed; KVCache.nbytes of both caches.
+  w8    (not in the default list) FP8 decode weights against bf16 ones, same process, interleaved blocks,
+        weights rotated past the last-level cache. Kernel: gemm_nt on a QuantizedWeight ("skinny", each form
+        forced, and every tile count of each form forced) against the bf16 weight-streaming kernel on the
+        gpt-1b projection shapes at M in {1, 2, 4, 8, 16}: us, bytes/s of W, ratio. Model: ms/token near
+        position 2048 for gpt-small B = 1 and gpt-1b B in {1, 16} (gpt-small only with --quick), bf16 / FP8
+        weights x bf16 / FP8 KV cache x eager / graphed; one extend of T in {4, 16} tokens at B = 1;
+        DecodeWeights.nbytes against the bf16 bytes of the same matrices; the max-abs logit difference of
+        one step on FP8 against bf16 weights (gpt-tiny and gpt-1b; reported, not judged).
 """
 from __future__ import annotations
 
@@ -40,7 +48,7 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 ROOF = 6.29e12
-STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420}
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900}
 KV8_TS = (4, 8)
 EXTEND_TS = (1, 2, 4, 8, 16)
 GEMM_MS = (1, 2, 4, 8, 16)  # 2 and 4: where the VALU / MFMA cut-over of the skinny kernel is decided
@@ -404,7 +412,178 @@ def step_kv8(quick: bool):
             "model": _kv8_model_rows(quick)}
 
 
-STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8}
+def _sep(a, b):
+    """A win or a loss only beyond the blocks' spread (a, b: {"min", "max"} in any unit)."""
+    return a["max"] < b["min"] or b["max"] < a["min"]
+
+
+def _w8_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.ops.gemm import _gemm_nt_w8
+    rows = []
+    for N, K in GEMM_SHAPES:
+        ncopy = 2 if quick else max(2, -(-(512 << 20) // (N * K)))  # the 8-bit copies alone exceed the cache
+        ws = [torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16) for _ in range(ncopy)]
+        qs = [ops.quantize_weight(w) for w in ws]
+        bias = torch.randn(N, device="cuda").to(torch.bfloat16)
+        for M in GEMM_MS:
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+
+            def w8(variant, tiles=0):
+                return lambda i: _gemm_nt_w8(a, qs[i % ncopy], bias, None, 1.0, "none", out, variant, tiles)
+
+            fns = {"bf16": lambda i: ops.gemm_nt(a, ws[i % ncopy], bias=bias, out=out, variant="skinny"),
+                   "w8": w8("skinny"), "w8_mfma": w8("skinny_mfma"),
+                   **{f"w8_mfma_t{t}": w8("skinny_mfma", t) for t in (1, 2, 4)}}
+            if M <= 8:
+                fns.update({"w8_valu": w8("skinny_valu"), "w8_valu_r2": w8("skinny_valu", 2),
+                            "w8_valu_r4": w8("skinny_valu", 4)})
+            r = _time_blocks(fns, blocks=5 if quick else 7, iters=ncopy)
+            row = {"M": M, "N": N, "K": K, "weight_copies": ncopy}
+            for v, t in r.items():
+                row[v] = {**t, "weight_GBps": N * K * (2 if v == "bf16" else 1) / t["median_us"] / 1e3}
+            row["bf16_over_w8"] = r["bf16"]["median_us"] / r["w8"]["median_us"]
+            row["separated"] = _sep({"min": r["w8"]["min_us"], "max": r["w8"]["max_us"]},
+                                    {"min": r["bf16"]["min_us"], "max": r["bf16"]["max_us"]})
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del ws, qs
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _w8_model_rows(model, name: str, B: int, quick: bool):
+    """ms/token around position 2048: bf16 / FP8 weights x bf16 / FP8 KV cache x eager / graphed, interleaved."""
+    import torch
+    cfg = model.cfg
+    prompt, new = 2048 - 128, 64 if quick else 128
+    weights = {"wbf16": None, "wfp8": model.decode_weights()}
+    kvs = {"kvbf16": None, "kvfp8": torch.float8_e4m3fn}
+    idx = torch.randint(0, cfg.vocab_size, (B, prompt), device="cuda")
+    toks = torch.randint(0, cfg.vocab_size, (new, B), device="cuda")
+
+    def run(w, kv, mode):
+        cache = model.new_cache(B, prompt + new, kv_dtype=kvs[kv])
+        model.prefill(idx, cache)
+        W = weights[w]
+        step = ((lambda t: model.decode_step(t, cache, weights=W)) if mode != "graph"
+                else model.graphed_decode_step(cache, weights=W))
+        step(toks[0])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(1, new):
+            step(toks[i])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+    res = {f"{w}_{kv}_{m}": [] for w in weights for kv in kvs for m in ("eager", "graph")}
+    for _ in range(3 if quick else 7):  # interleaved
+        for key in res:
+            res[key].append(run(*key.split("_")))
+    row = {"model": name, "B": B, "prompt": prompt, "new": new}
+    for k, v in res.items():
+        row[k] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+    for kv in kvs:
+        for m in ("eager", "graph"):
+            b, f = row[f"wbf16_{kv}_{m}"], row[f"wfp8_{kv}_{m}"]
+            row[f"bf16_over_fp8_weights_{kv}_{m}"] = b["ms_per_token"] / f["ms_per_token"]
+            row[f"separated_{kv}_{m}"] = _sep(b, f)
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def _w8_extend_rows(model, name: str, quick: bool):
+    """One extend of T tokens at B = 1, position 1920: bf16 against FP8 weights, eager and as a hipGraph."""
+    import torch
+    from kubeflow_rm_amd import ops
+    cfg = model.cfg
+    pos, cap, iters = 1920, 2048, 4
+    W = model.decode_weights()
+    eager, pinned = model.new_cache(1, cap), model.new_cache(1, cap)
+    for c in (eager, pinned):
+        for t in (*c.k, *c.v):
+            t.normal_()
+        c.set_lens([pos])
+    pinned.pin_bound()
+    rows = []
+    for T in (4, 16):
+        toks = torch.randint(0, cfg.vocab_size, (1, T), device="cuda")
+        graphs = {}
+        for k, w in (("wbf16", None), ("wfp8", W)):
+            pinned.set_lens([pos])
+            graphs[k] = ops.GraphedCallable(lambda t, w=w: model.extend(t, pinned, weights=w), toks.clone(), warmup=1)
+        torch.cuda.synchronize()
+        cands = {"wbf16_eager": (eager, lambda: model.extend(toks, eager)),
+                 "wfp8_eager": (eager, lambda: model.extend(toks, eager, weights=W)),
+                 "wbf16_graph": (pinned, lambda: graphs["wbf16"](toks)),
+                 "wfp8_graph": (pinned, lambda: graphs["wfp8"](toks))}
+        times = {k: [] for k in cands}
+        for b in range(-1, 5 if quick else 7):  # block -1: warm-up, not recorded
+            for k, (c, f) in cands.items():
+                c.set_lens([pos])  # a sync, outside the timed region: every block starts at the same position
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    f()
+                e1.record()
+                e1.synchronize()
+                if b >= 0:
+                    times[k].append(e0.elapsed_time(e1) / iters)  # ms per extend of T tokens
+        row = {"model": name, "B": 1, "T": T, "position": pos, "capacity": cap}
+        for k, v in times.items():
+            row[k] = {"median_ms": statistics.median(v), "min": min(v), "max": max(v)}
+        for m in ("eager", "graph"):
+            row[f"bf16_over_fp8_weights_{m}"] = row[f"wbf16_{m}"]["median_ms"] / row[f"wfp8_{m}"]["median_ms"]
+            row[f"separated_{m}"] = _sep(row[f"wbf16_{m}"], row[f"wfp8_{m}"])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del graphs
+    return rows
+
+
+def _w8_logit_row(model, name: str):
+    """max-abs logit difference of one decode step on FP8 against bf16 weights (one prompt; reported only)."""
+    import torch
+    cfg = model.cfg
+    T0 = min(128, cfg.max_seq - 2)
+    idx = torch.randint(0, cfg.vocab_size, (1, T0), device="cuda", generator=torch.Generator("cuda").manual_seed(0))
+    outs = []
+    for W in (None, model.decode_weights()):
+        cache = model.new_cache(1, T0 + 1)
+        tok = model.prefill(idx, cache).argmax(-1)
+        outs.append(model.decode_step(tok, cache, weights=W).float())
+    row = {"model": name, "prompt": T0, "max_abs_logit_diff": (outs[0] - outs[1]).abs().max().item(),
+           "max_abs_logit": outs[0].abs().max().item(), "argmax_equal": bool((outs[0].argmax(-1) == outs[1].argmax(-1)).all())}
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def step_w8(quick: bool):
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    result = {"kernel": _w8_kernel_rows(quick), "model": [], "extend": [], "nbytes": [], "logits": []}
+    plan = [("gpt-tiny", ()), ("gpt-small", (1,))] + ([] if quick else [("gpt-1b", (1, 16))])
+    for name, batches in plan:
+        model = GPT(CONFIGS[name], device="cuda").eval()
+        W = model.decode_weights()
+        bf16 = sum(q.shape[0] * q.shape[1] * 2 for q in W.matrices())
+        row = {"model": name, "decode_weights_nbytes": W.nbytes, "bf16_nbytes": bf16, "ratio": W.nbytes / bf16}
+        print(json.dumps(row), flush=True)
+        result["nbytes"].append(row)
+        if name != "gpt-small":  # the test model and gpt-1b
+            result["logits"].append(_w8_logit_row(model, name))
+        for B in batches:
+            result["model"].append(_w8_model_rows(model, name, B, quick))
+        if batches:
+            result["extend"] += _w8_extend_rows(model, name, quick)
+        del model, W
+        torch.cuda.empty_cache()
+    return result
+
+
+STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
