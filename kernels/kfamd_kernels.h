@@ -300,6 +300,24 @@ int kfamd_gemm_nt_skinny_w8_tiles(int path, int tiles, const void* A, const void
                                   void* C, const void* bias, const void* R, int M, int N, int K, long long lda,
                                   long long ldw, long long ldc, long long ldr, float alpha, int act, void* stream);
 
+// Token sampling (sample_bf16.hip): one token per row of bf16 logits [B][V] (row stride ld elements, the
+// vocabulary contiguous, 2-byte alignment only; 1 <= V <= 2^20; -inf allowed, NaN / an all -inf row out of
+// contract). Tokens are ordered by logit descending, equal logits by index ascending.
+//   inv_temp == 0 or top_k == 1: the first token of that order (u is not read).
+//   otherwise w_i = exp((x_i - x_max) * inv_temp); top_k (0 = none) keeps the first min(top_k, V) tokens of
+//   the order; top_p (1 = none) then keeps the shortest prefix whose mass reaches top_p * (mass of the
+//   top-k set), at least one token; the result is the first kept token in INDEX order whose inclusive
+//   running sum of kept weights exceeds u * W (W: the kept mass).
+// u: fp32 [S][B]; step: device int32 selecting the row u[*step] (nullptr: row 0; a *step outside [0, S)
+// makes the launch write nothing). out: int64 [B]. seq (optional): int64 [B][seq_ld >= S], column *step
+// is written. stop_token >= 0 with done (int32 [B], required then): a row whose flag is set emits
+// stop_token; any other row emits its token and sets its flag when the token is stop_token. stop_token
+// < 0: no stop (done must be nullptr). Everything a step needs is read from device memory, so a captured
+// launch replays while *step advances; the kernel never advances it.
+int kfamd_sample_bf16(const void* logits, long long ld, const float* u, const int* step, long long* out,
+                      long long* seq, long long seq_ld, int* done, int B, int V, int S, float inv_temp, int top_k,
+                      float top_p, long long stop_token, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

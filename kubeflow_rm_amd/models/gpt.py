@@ -17,6 +17,9 @@ on the decode kernels — the M <= 16 weight-streaming GEMM, the KV append and s
 attention — and can replay the step as one hipGraph (no tensor-parallel group; head dims 64 / 128).
 ``GPT.decode_weights()`` / ``generate(weight_dtype=torch.float8_e4m3fn)`` run the steps of up to 16 rows on
 8-bit copies of the projection weights (W8A16: bf16 activations, fp32 accumulation).
+``generate(sampler="fused")`` samples on ``ops.sample`` (top-k, top-p, a stop token; seeded uniforms, so the
+result does not depend on the device) and with ``graph=True`` replays step + sampler + token feedback as
+one hipGraph per token.
 """
 from __future__ import annotations
 
@@ -221,6 +224,22 @@ class _GraphedDecodeStep:
         out = self.graphed(tok)
         c._bound += 1
         return out
+
+
+class _GraphedGenerateStep:
+    """A captured ``decode_step`` -> ``ops.sample`` -> ``step += 1`` (``GPT.graphed_generate_step``): one
+    ``replay()`` per generated token and no other host work. As in ``_GraphedDecodeStep`` the capacity check
+    and the host-side bound of ``decode_step`` are kept here."""
+
+    def __init__(self, graphed, cache, keep):
+        self.graphed, self.cache, self._keep = graphed, cache, keep  # the captured kernels read `keep`
+
+    def replay(self) -> None:
+        c = self.cache
+        if c._bound + 1 > c.capacity:
+            raise ValueError(f"cache capacity {c.capacity} exceeded")
+        self.graphed.graph.replay()
+        c._bound += 1
 
 
 class GPT(torch.nn.Module):
@@ -532,7 +551,8 @@ class GPT(torch.nn.Module):
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
                  lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None,
-                 weight_dtype: torch.dtype | None = None):
+                 weight_dtype: torch.dtype | None = None, top_p: float | None = None, stop_token: int | None = None,
+                 sampler: str = "torch"):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -548,7 +568,25 @@ class GPT(torch.nn.Module):
         ``weight_dtype``: ``torch.float8_e4m3fn`` decodes on ``self.decode_weights()`` (and the draft on its
         own): every step of up to 16 rows reads 8-bit projection weights and LM head, half the bytes of a
         small-batch step; the prompt's ``prefill`` and steps of more rows read the bf16 weights. It combines
-        freely with ``kv_dtype`` and ``graph``. Any other dtype raises."""
+        freely with ``kv_dtype`` and ``graph``. Any other dtype raises.
+
+        ``sampler``: ``"torch"`` (the default) is the sampler described above; ``top_p`` / ``stop_token`` raise
+        with it. ``"fused"`` samples every token with ``ops.sample`` (one HIP kernel on the GPU, the same rule
+        in fp64 torch on the CPU): ``top_k``, then nucleus ``top_p`` on the top-k set's mass, ties broken by
+        token index. Its uniforms are drawn once, ``torch.rand(max_new_tokens, B, generator=generator)`` on the
+        generator's device (the CPU without one), so a seeded generation is the same on every device up to
+        the logits. With ``stop_token`` a row that emits it is finished: the output keeps its shape ``[B, T0 +
+        max_new_tokens]`` and the rest of such a row is padded with ``stop_token``; there is no per-token host
+        sync and no early exit, every row runs ``max_new_tokens`` steps. It combines with ``kv_dtype``,
+        ``weight_dtype`` and ``graph``; with ``graph=True`` the captured graph holds the step, the sampler and
+        the token feedback (``graphed_generate_step``), so a token costs one replay. ``draft`` keeps its own
+        greedy sampler: ``sampler="fused"`` with it raises."""
+        if sampler not in ("torch", "fused"):
+            raise ValueError(f'generate(sampler=...): "torch" or "fused" expected, got {sampler!r}')
+        if sampler == "torch" and (top_p is not None or stop_token is not None):
+            raise ValueError('generate(top_p=..., stop_token=...) need sampler="fused"')
+        if sampler == "fused" and draft is not None:
+            raise ValueError('generate(draft=...) keeps its greedy sampler: sampler="fused" cannot be combined with it')
         if weight_dtype is not None and weight_dtype != torch.float8_e4m3fn:
             raise ValueError(f"generate(weight_dtype=...): None or torch.float8_e4m3fn expected, got {weight_dtype}")
         B, T0 = idx.shape
@@ -577,6 +615,9 @@ class GPT(torch.nn.Module):
         cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
         logits = self.prefill(idx, cache)
         weights = self.decode_weights() if weight_dtype is not None else None
+        if sampler == "fused":
+            return self._generate_fused(idx, logits, cache, weights, max_new_tokens, temperature, top_k, top_p,
+                                        stop_token, generator, graph)
         step = lambda t: self.decode_step(t, cache, weights=weights)  # noqa: E731
         if graph and max_new_tokens > 1:
             step = self.graphed_decode_step(cache, weights=weights)
@@ -587,6 +628,66 @@ class GPT(torch.nn.Module):
             if i + 1 < max_new_tokens:
                 logits = step(nxt)
         return torch.cat(out, 1)
+
+    def _generate_fused(self, idx, logits, cache, weights, S: int, temperature, top_k, top_p, stop_token, generator,
+                        graph: bool):
+        """The token loop of ``generate(sampler="fused")`` after the prefill (``logits``: its output)."""
+        B, dev = idx.shape[0], idx.device
+        u = torch.rand(S, B, generator=generator, device=generator.device if generator is not None else "cpu").to(dev)
+        seq = torch.empty(B, S, dtype=torch.long, device=dev)  # the new tokens, one column per step
+        tok = torch.empty(B, dtype=torch.long, device=dev)
+        step = torch.zeros(1, dtype=torch.int32, device=dev)
+        done = torch.zeros(B, dtype=torch.int32, device=dev) if stop_token is not None else None
+        kw = dict(temperature=temperature, top_k=top_k, top_p=top_p, step=step, out=tok, seq=seq, done=done,
+                  stop_token=stop_token)
+        ops.sample(logits, u, **kw)  # the first token: from the prefill's logits, eagerly
+        step.add_(1)
+        if graph and S > 1:
+            g = self.graphed_generate_step(cache, weights, tok=tok, u=u, **{k: v for k, v in kw.items() if k != "out"})
+            for _ in range(S - 1):
+                g.replay()
+        else:
+            for _ in range(S - 1):
+                ops.sample(self.decode_step(tok, cache, weights=weights), u, **kw)
+                step.add_(1)
+        return torch.cat([idx, seq], 1)
+
+    def graphed_generate_step(self, cache, weights: "DecodeWeights | None" = None, *, tok: torch.Tensor,
+                              u: torch.Tensor, step: torch.Tensor, temperature: float = 1.0, top_k: int | None = None,
+                              top_p: float | None = None, seq: torch.Tensor | None = None,
+                              done: torch.Tensor | None = None,
+                              stop_token: int | None = None) -> "_GraphedGenerateStep":
+        """``decode_step(tok) -> ops.sample(..., out=tok) -> step += 1`` on ``cache`` captured once into a
+        hipGraph, on a single stream: ``tok`` (int64 ``[B]``) is both the step's input and the sampler's
+        output, so each ``replay()`` of the result turns the token of one position into the token of the next
+        and writes it into column ``step`` of ``seq``, with no host work besides the replay. ``u [S, B]``,
+        ``step``, ``seq``, ``done``, ``stop_token`` and the sampling arguments are ``ops.sample``'s. Nothing is
+        returned per replay: read ``tok`` / ``seq`` once at the end.
+
+        Everything the replay reads per token lives on the device (``cache.lens``, ``step``, ``tok``, ``done``);
+        the host-side capacity check is kept (a ``replay()`` with no free cache row raises like
+        ``decode_step``). The cache needs one free row, and ``step`` one free row of ``u``, for the warm-up
+        step, whose effects (``lens``, ``step``, ``tok``, ``seq``, ``done``) are undone here. The graph holds the
+        tensors' addresses: the returned object keeps them (and ``weights``) alive."""
+        if cache._bound + 1 > cache.capacity:
+            raise ValueError("graphed_generate_step needs a free cache row")
+        cache.pin_bound()
+        bound = cache._bound
+        state = [t for t in (cache.lens, step, tok, seq, done) if t is not None]
+        saved = [t.clone() for t in state]
+
+        def body(t):  # warm-up and capture both start from the same host bound
+            cache._bound = bound
+            ops.sample(self.decode_step(t, cache, weights=weights), u, temperature=temperature, top_k=top_k,
+                       top_p=top_p, step=step, out=t, seq=seq, done=done, stop_token=stop_token)
+            step.add_(1)
+
+        g = ops.GraphedCallable(body, tok, warmup=1)
+        torch.cuda.current_stream().synchronize()
+        for t, s0 in zip(state, saved):
+            t.copy_(s0)
+        cache._bound = bound
+        return _GraphedGenerateStep(g, cache, (weights, u, step, tok, seq, done))
 
     def graphed_decode_step(self, cache, weights: "DecodeWeights | None" = None) -> "_GraphedDecodeStep":
         """``decode_step`` on ``cache`` captured once into a hipGraph (its attention grid sized for the

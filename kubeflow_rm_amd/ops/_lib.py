@@ -112,6 +112,8 @@ _SIGNATURES = {
                                              c_ll, c_ll, c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_w8_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                               c_ll, c_ll, c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_sample_bf16": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_float, c_int,
+                                  c_float, c_ll, c_vp]),
     "kfamd_build_info": (ctypes.c_char_p, []),
 }
 

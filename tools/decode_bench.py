@@ -32,6 +32,12 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         weights x bf16 / FP8 KV cache x eager / graphed; one extend of T in {4, 16} tokens at B = 1;
         DecodeWeights.nbytes against the bf16 bytes of the same matrices; the max-abs logit difference of
         one step on FP8 against bf16 weights (gpt-tiny and gpt-1b; reported, not judged).
+  sample  (not in the default list) the fused sampler. Kernel: ops.sample against the model's torch _sample
+        at V = 32000, B in {1, 16}, interleaved blocks: greedy, top_k = 50, top_p = 0.9 and both (_sample has
+        no top_p: those two rows time it at the nearest setting it has, named in the row). Model: gpt-small
+        and gpt-1b (gpt-small only with --quick), B in {1, 16}, temperature 1, top_k = 50, graphed, ms/token:
+        the torch sampler between replays of graphed_decode_step against graphed_generate_step (step,
+        sampler and token feedback in one graph), interleaved runs.
 """
 from __future__ import annotations
 
@@ -48,7 +54,7 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 ROOF = 6.29e12
-STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900}
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420}
 KV8_TS = (4, 8)
 EXTEND_TS = (1, 2, 4, 8, 16)
 GEMM_MS = (1, 2, 4, 8, 16)  # 2 and 4: where the VALU / MFMA cut-over of the skinny kernel is decided
@@ -583,7 +589,88 @@ def step_w8(quick: bool):
     return result
 
 
-STEPS = {"gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+def _sample_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.models.gpt import _sample
+    rows, V, ncopy = [], 32000, 8
+    settings = {"greedy": (0.0, None, None), "top_k50": (1.0, 50, None), "top_p0.9": (1.0, None, 0.9),
+                "top_k50_top_p0.9": (1.0, 50, 0.9)}
+    for B in (1, 16):
+        logits = [(torch.randn(B, V, device="cuda") * 4).to(torch.bfloat16) for _ in range(ncopy)]
+        u = torch.rand(ncopy, B, device="cuda")
+        out = torch.empty(B, dtype=torch.long, device="cuda")
+        for name, (temp, k, p) in settings.items():
+            fns = {"fused": lambda i: ops.sample(logits[i % ncopy], u[i % ncopy], temp, k, p, out=out),
+                   "torch": lambda i: _sample(logits[i % ncopy], temp, k, None)}
+            r = _time_blocks(fns, 5 if quick else 15, 50)
+            row = {"B": B, "V": V, "setting": name, "torch_setting": "greedy" if temp == 0 else f"top_k={k}", **r,
+                   "torch_over_fused": r["torch"]["median_us"] / r["fused"]["median_us"]}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def _sample_model_rows(model, name: str, B: int, quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.models.gpt import _sample
+    cfg = model.cfg
+    prompt, new, temp, k = 512 - 128, 128, 1.0, 50
+    idx = torch.randint(0, cfg.vocab_size, (B, prompt), device="cuda")
+
+    def run(kind):
+        cache = model.new_cache(B, prompt + new)
+        logits = model.prefill(idx, cache)
+        if kind == "torch_between_replays":  # generate(graph=True): the parent's token loop
+            step = model.graphed_decode_step(cache)
+            logits = step(_sample(logits, temp, k, None))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(new - 2):
+                logits = step(_sample(logits, temp, k, None))
+        else:  # generate(graph=True, sampler="fused")
+            u = torch.rand(new, B, device="cuda")
+            tok = torch.empty(B, dtype=torch.long, device="cuda")
+            seq = torch.empty(B, new, dtype=torch.long, device="cuda")
+            pos = torch.zeros(1, dtype=torch.int32, device="cuda")
+            ops.sample(logits, u, temp, k, step=pos, out=tok, seq=seq)
+            pos.add_(1)
+            g = model.graphed_generate_step(cache, tok=tok, u=u, step=pos, seq=seq, temperature=temp, top_k=k)
+            g.replay()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(new - 2):
+                g.replay()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / (new - 2)
+
+    res = {"torch_between_replays": [], "fused_in_graph": []}
+    for _ in range(3 if quick else 7):  # interleaved
+        for key in res:
+            res[key].append(run(key))
+    row = {"model": name, "B": B, "prompt": prompt, "new": new, "temperature": temp, "top_k": k}
+    for key, v in res.items():
+        row[key] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+    row["torch_over_fused"] = row["torch_between_replays"]["ms_per_token"] / row["fused_in_graph"]["ms_per_token"]
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def step_sample(quick: bool):
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    result = {"kernel": _sample_kernel_rows(quick), "model": []}
+    for name in ("gpt-small",) if quick else ("gpt-small", "gpt-1b"):
+        model = GPT(CONFIGS[name], device="cuda").eval()
+        for B in (1, 16):
+            result["model"].append(_sample_model_rows(model, name, B, quick))
+        del model
+        torch.cuda.empty_cache()
+    return result
+
+
+STEPS = {"sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
