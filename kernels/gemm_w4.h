@@ -126,6 +126,66 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
+#ifndef KFW4_GROUP_M
+#define KFW4_GROUP_M 4  // tile-row group of the grouped raster (A/B runs build other values)
+#endif
+#ifndef KFW4_SUPER
+#define KFW4_SUPER 1  // 16 x 16-tile superblocks across the 8 XCDs for operands past the MALL (tile_of_block)
+#endif
+constexpr int kGroupM = KFW4_GROUP_M;
+
+// grouped raster: work item wg of a tiles_m x tiles_n problem -> (tm, tn), groups of kGroupM tile rows
+__device__ __forceinline__ void raster_tile(int wg, int tiles_m, int tiles_n, int& tm, int& tn) {
+  const int per_group = kGroupM * tiles_n;
+  const int g = wg / per_group, first_m = g * kGroupM;
+  const int gm = min(tiles_m - first_m, kGroupM);
+  tm = first_m + (wg % per_group) % gm;
+  tn = (wg % per_group) / gm;
+}
+
+// Block -> output tile: the one mapping both a block's own tile and its successor's (block id + 256,
+// the successor prefetch) come from. prob = 0, 1 (GRP: the launch's second problem, M2 x N2) or -1:
+// no tile for this block id; wg = the tile's index in its problem's XCD-remapped order.
+struct TileId {
+  int prob, wg, tm, tn;
+};
+template <int BM, bool GRP>
+__device__ __forceinline__ TileId tile_of_block(int bid, int grid, int M, int N, int K, int M2, int N2) {
+  int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BM - 1) / BM;
+  const int nwg = tiles_m * tiles_n;
+  TileId t;
+  if constexpr (GRP) {
+    const int t1 = nwg, t2 = ((M2 + BM - 1) / BM) * ((N2 + BM - 1) / BM);
+    t.wg = xcd_remap(bid, t1 + t2);
+    t.prob = bid >= t1 + t2 ? -1 : t.wg >= t1;
+    if (t.wg >= t1) {  // problem 2 (uniform per block)
+      t.wg -= t1;
+      tiles_m = (M2 + BM - 1) / BM;
+      tiles_n = (N2 + BM - 1) / BM;
+    }
+  } else {
+    t.wg = xcd_remap(bid, nwg);
+    t.prob = bid >= nwg ? -1 : 0;
+  }
+  raster_tile(t.wg, tiles_m, tiles_n, t.tm, t.tn);
+  if constexpr (KFW4_SUPER && !GRP && BM == 256) {
+    // the chip's 256 resident tiles (one per CU) as ONE 16 x 16 block of the output: XCD x (block b
+    // runs on XCD b % 8) takes its 4 x 8 sub-block, rows 4 (x & 3), columns 8 (x >> 2); the waves walk
+    // the superblocks column-major. 16 A + 16 B panels are live at once instead of 32 A + 8 B with the
+    // per-XCD row groups (at 16384^3 a panel is 8 MiB: 256 vs 320 MiB against the 256 MiB MALL):
+    // 16384^3 0.987 -> 1.012 of hipBLASLt, 4096^3 / 8192^3 level (profiles/r6zm_super). Only where A
+    // and B together exceed the MALL; smaller problems keep the row groups.
+    if ((tiles_m & 15) == 0 && (tiles_n & 15) == 0 && grid == nwg &&  // (not the persistent grid)
+        (long long)(M + N) * K * 2 > (256LL << 20)) {
+      const int b = bid, x = b & 7, i = b >> 3, wave = i >> 5, j = i & 31;
+      const int sbm = tiles_m >> 4, sr = wave % sbm, sc = wave / sbm;
+      t.tm = 16 * sr + 4 * (x & 3) + (j & 3);
+      t.tn = 16 * sc + 8 * (x >> 2) + (j >> 2);
+    }
+  }
+  return t;
+}
+
 __device__ __forceinline__ void mfma(f32x4& acc, const bf16x8& b, const bf16x8& a) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(b), "v"(a));
 }
@@ -349,15 +409,15 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   }
 
   int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, nwg = tiles_m * tiles_n;
-  int wg;
   int grp_base = 0, nwg_all = nwg;  // GRP: this problem's first tile / both problems' tiles (split-K slots)
+  // (the own tile always exists: a grid is never larger than the tile count)
+  const TileId own = tile_of_block<BM, GRP>(blockIdx.x, gridDim.x, M, N, K, g2.M, g2.N);
+  const int wg = own.wg;
   if constexpr (GRP) {
     const int t1 = nwg, t2 = ((g2.M + BM - 1) / BM) * ((g2.N + BN - 1) / BN);
     nwg_all = t1 + t2;
-    wg = xcd_remap(blockIdx.x, t1 + t2);
-    if (wg >= t1) {  // problem 2 (uniform per block)
+    if (own.prob == 1) {  // problem 2 (uniform per block)
       grp_base = t1;
-      wg -= t1;
       A = g2.A;
       B = g2.B;
       C = g2.C;
@@ -370,39 +430,11 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       tiles_n = (N + BN - 1) / BN;
       nwg = t2;
     }
-  } else {
-    wg = xcd_remap(blockIdx.x, nwg);
   }
 #ifndef KFW4_SK_AB
 #define KFW4_SK_AB 0  // stream-K timing ablations (tools/sk_ab.py builds): 1 no partial traffic, 2 no owner wait
 #endif
-#ifndef KFW4_GROUP_M
-#define KFW4_GROUP_M 4  // tile-row group of the grouped raster (A/B runs build other values)
-#endif
-  constexpr int kGroupM = KFW4_GROUP_M;
-  const int per_group = kGroupM * tiles_n;
-  const int g = wg / per_group, first_m = g * kGroupM;
-  const int gm = min(tiles_m - first_m, kGroupM);
-  int tm = first_m + (wg % per_group) % gm;
-  int tn = (wg % per_group) / gm;
-#ifndef KFW4_SUPER
-#define KFW4_SUPER 1  // 16 x 16-tile superblocks across the 8 XCDs for operands past the MALL (below)
-#endif
-  if constexpr (KFW4_SUPER && !GRP && BM == 256) {
-    // the chip's 256 resident tiles (one per CU) as ONE 16 x 16 block of the output: XCD x (block b
-    // runs on XCD b % 8) takes its 4 x 8 sub-block, rows 4 (x & 3), columns 8 (x >> 2); the waves walk
-    // the superblocks column-major. 16 A + 16 B panels are live at once instead of 32 A + 8 B with the
-    // per-XCD row groups (at 16384^3 a panel is 8 MiB: 256 vs 320 MiB against the 256 MiB MALL):
-    // 16384^3 0.987 -> 1.012 of hipBLASLt, 4096^3 / 8192^3 level (profiles/r6zm_super). Only where A
-    // and B together exceed the MALL; smaller problems keep the row groups.
-    if ((tiles_m & 15) == 0 && (tiles_n & 15) == 0 && gridDim.x == (unsigned)nwg &&  // (not the persistent grid)
-        (long long)(M + N) * K * 2 > (256LL << 20)) {
-      const int b = blockIdx.x, x = b & 7, i = b >> 3, wave = i >> 5, j = i & 31;
-      const int sbm = tiles_m >> 4, sr = wave % sbm, sc = wave / sbm;
-      tm = 16 * sr + 4 * (x & 3) + (j & 3);
-      tn = 16 * sc + 8 * (x >> 2) + (j >> 2);
-    }
-  }
+  const int tm = own.tm, tn = own.tn;
   int m_lo = tm * BM, n_lo = tn * BN;                  // first output row / column this block stores
   int m0 = min(m_lo, M - BM), n0 = min(n_lo, N - BN);  // edge tiles shifted inside
 
@@ -736,6 +768,56 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     for (int n = 0; n < NR; ++n) asm volatile("" : "+a"(acc[i][n]));
   };  // run_k
 
+  // Successor prefetch (KFW4_PREFETCH_NEXT). One block per CU is resident, so the block that takes
+  // this CU's place is about block id + 256, which the dispatcher puts on the same XCD (b % 8), i.e.
+  // behind the same L2. While this block only stores, touch one dword of every 128-B row of the
+  // successor's first two K-tiles of A and B (thread t: row t of each 256-row panel; four loads per
+  // wave), so the successor's prologue finds them in L2 instead of fetching them cold with every other
+  // CU of the XCD at the same moment. The dword is the LAST of the row's K-tile: with a partial first
+  // K-tile (koff < 0) its k < 0 part is never addressed. The descriptors start at the successor's
+  // panel and end with the operand, so an address outside A / B would read as zero, never fault.
+  // The loads are ordinary counted loads whose results nobody reads: they stay live up to the end of
+  // the epilogue (keep_prefetch), whose wait sits right before s_endpgm (which waits for the wave's
+  // memory operations anyway).
+  // OFF in production (tools/w4_ab.py builds it as `prefetch`): the successor's prologue gets ~650
+  // cycles shorter, but the 1024 scattered line requests per block queue ahead of this block's stores
+  // and its epilogue gets ~2000 cycles longer: 8192^3 level, the K = 2048 shapes 1-2 % slower
+  // (profiles/w4_prefetch).
+#ifndef KFW4_PREFETCH_NEXT
+#define KFW4_PREFETCH_NEXT 0
+#endif
+  constexpr int kResident = 256;  // blocks between a block and its successor on the same CU / XCD
+  constexpr bool kPrefetch = KFW4_PREFETCH_NEXT && BM == 256 && LA == 0 && LB == 0 && !SPLIT && !SK && !PO &&
+                             !GRP && !DACT && ABL == 0;
+  int pf[4] = {0, 0, 0, 0};
+  auto prefetch_next = [&]() __attribute__((always_inline)) {
+    if constexpr (kPrefetch) {
+      const int nb = blockIdx.x + kResident;
+      if (nb < (int)gridDim.x) {  // (uniform; grid == tile count here, so the successor has a tile)
+        const TileId s = tile_of_block<BM, false>(nb, gridDim.x, M, N, K, 0, 0);
+        const long long pa = (long long)min(s.tm * BM, M - BM) * lda, pb = (long long)min(s.tn * BN, N - BN) * ldb;
+        // bytes from the panel's first element to the operand's last (this batch entry)
+        const long long ea = (((long long)(M - 1) * lda + K) - pa) * 2, eb = (((long long)(N - 1) * ldb + K) - pb) * 2;
+        __amdgpu_buffer_rsrc_t sra = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(A_in + bz * sa + pa), (short)0, (int)min(ea, (long long)kNumRecords), kRsrcWord3);
+        __amdgpu_buffer_rsrc_t srb = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(B_in + bz * sb + pb), (short)0, (int)min(eb, (long long)kNumRecords), kRsrcWord3);
+        const int klast = (koff + kBK - 2) * 2;  // byte offset of K-tile 0's last dword in a row (>= 0: K % 8 == 0)
+        const int va = (int)(tid * lda * 2) + klast, vb = (int)(tid * ldb * 2) + klast;
+        pf[0] = __builtin_amdgcn_raw_buffer_load_b32(sra, va, 0, 0);
+        pf[1] = __builtin_amdgcn_raw_buffer_load_b32(srb, vb, 0, 0);
+        if (nk > 1) {  // (a one-tile K has no second K-tile: nothing past the row's end is touched)
+          pf[2] = __builtin_amdgcn_raw_buffer_load_b32(sra, va + kBK * 2, 0, 0);
+          pf[3] = __builtin_amdgcn_raw_buffer_load_b32(srb, vb + kBK * 2, 0, 0);
+        }
+        KFW4_FENCE();  // the loads issue here: nothing sinks them towards keep_prefetch
+      }
+    }
+  };
+  auto keep_prefetch = [&]() __attribute__((always_inline)) {
+    if constexpr (kPrefetch) asm volatile("" ::"v"(pf[0]), "v"(pf[1]), "v"(pf[2]), "v"(pf[3]));
+  };
+
   // Epilogue. Lane (lr, lh) holds row lr, columns 4lh..4lh+3 of every 16x16 block n. For each pair
   // of blocks (n, n+1) one v_permlane16_swap per dword trades rows 1<->0 and 3<->2 of the lane
   // groups (cdna_hip_programming.md T21, 16-lane form), after which every lane holds 8 contiguous
@@ -763,6 +845,9 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
 #pragma unroll
     for (int n = 0; n < NR; ++n) bpre[n] = *reinterpret_cast<const bf16x4*>(bias + n0 + wn * WT + n * 16 + elh * 4);
   }
+  // behind the bias loads in the in-order load counter (their wait does not cover these), ahead of
+  // every store; a residual's rows are loaded span by span later, so the first of their waits does
+  prefetch_next();
   // VEC (compile time): bias / residual as 8-B vector loads (the fast path) or element loads
   // UNIT (compile time): alpha == 1, the scale is skipped (128 v_pk_mul_f32 per wave)
   auto finish = [&](auto VEC, auto UNIT, int i, int n, int m, uint2& pre_out) -> uint2 {
@@ -942,6 +1027,20 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   // (no wave reads the ring after the last tile's mid barrier) and reads back row-major. Row r's 16-B
   // slot c sits at r * 128 + 16 * (c ^ ((r >> 1) & 7)): the writes (16 rows, one slot each per 16
   // lanes) and the reads (two rows of 8 slots per 16 lanes) both cover 16 distinct bank quads.
+  // KFW4_STORE_NT: these C stores, whole lines nobody reads again in this GEMM, with the non-temporal
+  // policy (global_store_dwordx4 ... nt), so the 128 KiB a block writes (4 MiB, a whole L2, per XCD and
+  // tile wave) stop displacing the A / B panels its neighbours re-read: 8192^3 +1.9 % against plain
+  // stores in interleaved rounds (profiles/w4_prefetch; tools/w4_ab.py `r4` = plain, `storent`)
+#ifndef KFW4_STORE_NT
+#define KFW4_STORE_NT 1
+#endif
+  auto store_line = [&](__bf16* p, uint4 v) __attribute__((always_inline)) {
+    if constexpr (KFW4_STORE_NT) {
+      __builtin_nontemporal_store(i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w}, reinterpret_cast<i32x4*>(p));
+    } else {
+      *reinterpret_cast<uint4*>(p) = v;
+    }
+  };
   auto emit_fullline = [&](auto UNIT) {
     static_assert(NR % 4 == 0, "full-line stores: two block pairs per span");
     char* stage = smem + kEpiBase + wid * 2048;
@@ -980,8 +1079,8 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
         }
         const uint4 X = *reinterpret_cast<const uint4*>(stage + r0);
         const uint4 Y = *reinterpret_cast<const uint4*>(stage + r1);
-        *reinterpret_cast<uint4*>(xrow + n * 16) = X;
-        *reinterpret_cast<uint4*>(xrow + 8 * ldc + n * 16) = Y;
+        store_line(xrow + n * 16, X);
+        store_line(xrow + 8 * ldc + n * 16, Y);
         if (HAS_AUX) {
           const long long ao = (long long)(xrow - C);
           const uint4 XA = *reinterpret_cast<const uint4*>(stage + 8192 + r0);
@@ -1157,6 +1256,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   } else {
     emit(F{}, store_og, F{});
   }
+  keep_prefetch();
   };  // epilogue
 
   if constexpr (SK) {
@@ -1164,9 +1264,8 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     const int G = gridDim.x, KT = nk, koff_full = koff;
     const int T_dp = nwg - nwg % G;
     auto set_tile = [&](int w) __attribute__((always_inline)) {
-      const int gg = w / per_group, fm = gg * kGroupM;
-      const int gmm = min(tiles_m - fm, kGroupM);
-      const int tm_ = fm + (w % per_group) % gmm, tn_ = (w % per_group) / gmm;
+      int tm_, tn_;
+      raster_tile(w, tiles_m, tiles_n, tm_, tn_);
       m_lo = tm_ * BM;
       n_lo = tn_ * BN;
       m0 = min(m_lo, M - BM);
@@ -1347,9 +1446,8 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     // ring refill hide under its stores; no block boundary between tiles.
     const int G = gridDim.x;
     auto set_tile = [&](int w) __attribute__((always_inline)) {
-      const int gg = w / per_group, fm = gg * kGroupM;
-      const int gmm = min(tiles_m - fm, kGroupM);
-      const int tm_ = fm + (w % per_group) % gmm, tn_ = (w % per_group) / gmm;
+      int tm_, tn_;
+      raster_tile(w, tiles_m, tiles_n, tm_, tn_);
       m_lo = tm_ * BM;
       n_lo = tn_ * BN;
       m0 = min(m_lo, M - BM);

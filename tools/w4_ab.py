@@ -7,7 +7,7 @@
                                             # variants' cheap K-loop stamps (cycles per 64-k tile by segment)
 
 Prints one JSON line per measurement. Knobs: kernels/gemm_w4.h (KFW4_RG, KFW4_DMA_EVERY, KFW4_DMA_PHASE,
-KFW4_PIN_MFMA, KFW4_PRIO); every variant also carries KFW4_CHEAP_STAMPS=1, which only touches its diag
+KFW4_PIN_MFMA, KFW4_PRIO, and outside the K loop KFW4_PREFETCH_NEXT, KFW4_STORE_NT); every variant also carries KFW4_CHEAP_STAMPS=1, which only touches its diag
 kernel (s_memtime with no wait of its own, read after the loop's own lgkmcnt(0)).
 """
 import argparse
@@ -27,7 +27,10 @@ VARIANTS = {
     "base": ["-DKFW4_FASTK=0", "-DKFW4_UNROLL5=0", "-DKFW4_ASM_DMA=0", "-DKFW4_PREBAR=0"],  # the round-3 K loop
     "unroll5": ["-DKFW4_FASTK=0", "-DKFW4_UNROLL5=1"],
     "f2u5": ["-DKFW4_FASTK=2", "-DKFW4_UNROLL5=1", "-DKFW4_ASM_DMA=0", "-DKFW4_PREBAR=0"],
-    "r4": [],  # the production knobs
+    "r4": ["-DKFW4_PREFETCH_NEXT=0", "-DKFW4_STORE_NT=0"],  # production before the non-temporal C stores
+    "prefetch": ["-DKFW4_PREFETCH_NEXT=1", "-DKFW4_STORE_NT=0"],  # successor tile's first K-tiles into L2
+    "storent": ["-DKFW4_PREFETCH_NEXT=0", "-DKFW4_STORE_NT=1"],  # non-temporal full-line C stores (production)
+    "prefetch_storent": ["-DKFW4_PREFETCH_NEXT=1", "-DKFW4_STORE_NT=1"],
     "noful": ["-DKFW4_FULLLINE=0"],  # the half-line epilogue stores
     "asmdma": ["-DKFW4_ASM_DMA=1"],
     "prebar1": ["-DKFW4_PREBAR=1"],
@@ -82,6 +85,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--diag", default="8192")
     ap.add_argument("--po-grid", type=int, default=256, help="blocks of the persistent-overlapped (PO) launch")
+    ap.add_argument("--no-po", action="store_true", help="skip the persistent-overlapped launches")
+    ap.add_argument("--launches", type=int, default=0,
+                    help="profiling mode (under rocprofv3): only launch each variant N times at the first size, "
+                         "in --variants order (the kernel name is the same in every library)")
     a = ap.parse_args()
     names = [v for v in a.variants.split(",") if v]
     if a.build:
@@ -110,11 +117,20 @@ def main():
         B = (torch.rand(N, K, device=dev) * 2 - 1).to(torch.bfloat16)
         ref = ops.gemm_nt(A, B)
         C = torch.empty_like(ref)
+        if a.launches:
+            for n, L in libs.items():
+                for _ in range(a.launches):
+                    assert L.w4ab_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, st) == 0
+                torch.cuda.synchronize()
+            print(json.dumps({"size": s, "launches": a.launches, "order": list(libs)}), flush=True)
+            return
         same = {}
         for n, L in libs.items():
             assert L.w4ab_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, st) == 0
             torch.cuda.synchronize()
             same[n] = bool(torch.equal(C, ref))
+            if a.no_po:
+                continue
             C.zero_()
             assert L.w4ab_po(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, a.po_grid, st) == 0
             torch.cuda.synchronize()
@@ -124,8 +140,12 @@ def main():
         fns = {"prod": lambda: ops.gemm_nt(A, B, out=C), "torch": lambda: torch.matmul(A, B.t())}
         for n, L in libs.items():
             fns[n] = (lambda L=L: L.w4ab_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, st))
-            fns[n + "_po"] = (lambda L=L: L.w4ab_po(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, a.po_grid, st))
-        t_end = time.perf_counter() + 1.0
+            if not a.no_po:
+                fns[n + "_po"] = (lambda L=L: L.w4ab_po(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, a.po_grid, st))
+        for fn in fns.values():  # first calls (hipBLASLt picks its algorithm) stay out of the rounds
+            fn()
+        torch.cuda.synchronize()
+        t_end = time.perf_counter() + 1.0  # settle: 1 s of back-to-back GEMMs before round 1
         while time.perf_counter() < t_end:
             fns["prod"]()
         tf = {k: [] for k in fns}
@@ -139,7 +159,10 @@ def main():
                 tf[k].append(flop * iters / (time.perf_counter() - t0) / 1e12)
         print(json.dumps({"size": s, "bitwise_equal_to_prod": same,
                           "median_tf": {k: round(statistics.median(v), 1) for k, v in tf.items()},
-                          "best_tf": {k: round(max(v), 1) for k, v in tf.items()}}), flush=True)
+                          "best_tf": {k: round(max(v), 1) for k, v in tf.items()},
+                          # (max - min) / median of each build's own rounds: what a difference has to beat
+                          "spread": {k: round((max(v) - min(v)) / statistics.median(v), 4) for k, v in tf.items()},
+                          "rounds_tf": {k: [round(x, 1) for x in v] for k, v in tf.items()}}), flush=True)
         del A, B, C, ref
     for spec in [x for x in a.diag.split(",") if x]:
         # s (s^3) or MxNxK: e.g. 1024x1024x8192 puts 16 blocks on 16 CUs (no chip-wide store burst)
