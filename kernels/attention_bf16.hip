@@ -40,19 +40,13 @@
 // SURVEY §7.1C rules out Triton on the hot path.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "attn_tile.h"
 #include "kfamd_kernels.h"
 #include "wave_ops.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+using namespace kfa;  // the LDS tile image, its reads, mfma32, pack2, buffer loads: attn_tile.h
 
 constexpr float kLog2e = 1.4426950408889634f;
 
@@ -102,54 +96,6 @@ __device__ __forceinline__ BlockId block_order(int bid, int nblk, int BH, int sl
   const int lid = (nwg & 7) == 0 ? xcd_remap(bid, nwg) : bid;
   return {lid / nblk, lid % nblk};
 }
-
-template <int D>
-__device__ __forceinline__ int swz(int row, int ch) {
-  if constexpr (D == 128) {
-    return ch ^ (((row & 3) << 2) | ((row >> 2) & 3));
-  } else {
-    const int x = (row >> 1) & 7;
-    return ch ^ (((x & 1) << 2) | (x >> 1));
-  }
-}
-
-// byte offset of 16-B chunk ch of row `row` in an image of D-element bf16 rows
-template <int D>
-__device__ __forceinline__ int img_off(int row, int ch) {
-  return row * (D * 2) + (swz<D>(row, ch) << 4);
-}
-
-__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// v_exp_f32 as is: the libm exp2f wraps it in a denormal range reduction (v_cmp, v_cndmask, v_ldexp
-// per call) that softmax does not need — a result below 2^-126 is 0 for a probability
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ uint32_t pack2(float x, float y) {
-  const bf16x2 v = __builtin_convertvector((f32x2){x, y}, bf16x2);
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// ds_read_b64_tr_b16 at an LDS byte offset: 4 consecutive rows x 16 columns per 16-lane group,
-// lane i of the group receives column i (row q in element q)
-__device__ __forceinline__ s16x4 tr_read(const char* smem, int byte_off) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + byte_off));
-}
-
-__device__ __forceinline__ bf16x8 join(s16x4 lo, s16x4 hi) {
-  const short __attribute__((ext_vector_type(8))) v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ bf16x8 lds_row(const char* smem, int byte_off) {
-  return *reinterpret_cast<const bf16x8*>(smem + byte_off);
-}
-
-__device__ __forceinline__ u32x4 gload16(const __bf16* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 // KFATT_BUF: row-guarded loads and the dQ atomics as raw buffer operations over one (b, h) slice
 // whose range ends at row T: a row past T reads as zero / is dropped by the address unit, so the
@@ -203,13 +149,6 @@ __device__ __forceinline__ u32x4 gload16(const __bf16* p) { return *reinterpret_
 #ifndef KFATT_FWD_DMA
 #define KFATT_FWD_DMA 0  // forward K / V tiles by LDS-DMA (attn_fwd stage_dma)
 #endif
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t slice_rsrc(const void* base, long long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, int byte_off, int soff = 0) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, soff, 0));
-}
-
 // LDS-DMA as inline asm (KFATT_DMA): the compiler, seeing a buffer_load ... lds builtin, waits
 // vmcnt(0) before later LDS reads it cannot prove disjoint (it did, mid-tile, before the dV / dK tr
 // reads: the next tile's DMA latency exposed). The kernel's own waits cover the pieces instead.

@@ -19,8 +19,10 @@
 //         general body, launched for it, was 1.0 - 1.5 % of a gpt-1b step slower (profiles/attn_kv_unify).
 // They share the formats, the split bookkeeping's constants, the host check and the launcher; each has its
 // combine (attn_decode_combine is attn_kv_combine at Tq = 1).
-// The MFMA form (16 rows fill one v_mfma_f32_16x16x32_bf16 tile for Q.K^T; P.V then needs V with keys
-// along k, an LDS transpose of every V tile) was NOT built: one form serves every Tq, no cut-over.
+// Up to 16 rows this VALU form serves every Tq, no cut-over inside attention_extend. More rows per call
+// take the MFMA form, attn_chunk_split in attn_kv_mfma.hip (128-row query tiles on
+// v_mfma_f32_32x32x16_bf16, V read transposed from LDS; any Tq, ops.attention_chunk): it shares the row
+// formats, kSplitKeys, the split records and attn_kv_combine with this file through attn_kv_rows.h.
 //
 // Split structure: the key range [0, t_bound) is cut in fixed chunks of kSplitKeys keys; workgroup
 // (split, h, b) — 256 threads — walks its chunk. The block's 256 / (D / 8) lane groups take consecutive
@@ -76,65 +78,18 @@
 // bf16 copy at T = 2048 (8 IEEE divisions per lane): 63 us per layer of a 2048-token prefill.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "attn_kv_rows.h"
 #include "kfamd_kernels.h"
 #include "wave_ops.h"
 
 namespace {
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace kfkv;  // the row formats (Bf16Rows, Fp8Rows), kSplitKeys and the host checks: attn_kv_rows.h
 
-constexpr int kSplitKeys = 256;
 constexpr int kThreads = 256;
 constexpr int kMaxRows = 16;
 constexpr int kSlotRows = 8;   // query rows per split launch (16 row slots spill: see the header)
 constexpr int kMergeRows = 4;  // row slots merged per LDS pass
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kFp8Max = 448.f;  // largest finite e4m3fn value (code 0x7E)
-
-// ---- row formats -------------------------------------------------------------------------------
-// What a cache row is made of. Elem: the unit of the cache strides. Vec: one lane's load, 8 elements.
-// kStrideAlign: what every cache stride must be a multiple of, in Elem (16 B either way). unroll(R): keys
-// per lane group and block step, loaded one step ahead. kScaled: a row has an fp32 scale next to it.
-struct Bf16Rows {
-  typedef __bf16 Elem;
-  typedef u32x4 Vec;
-  static constexpr bool kScaled = false;
-  static constexpr int kStrideAlign = 8;
-  static constexpr int unroll(int) { return 2; }
-  static __device__ __forceinline__ void unpack8(const Vec& w, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(w[i] << 16);
-      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-};
-
-struct Fp8Rows {
-  typedef uint8_t Elem;
-  typedef u32x2 Vec;
-  static constexpr bool kScaled = true;
-  static constexpr int kStrideAlign = 16;
-  // A lane's load is 8 B, half of bf16's: twice bf16's unroll keeps the same bytes in flight where the
-  // kernel is a KV stream (up to 4 row slots); at 8 row slots the VALU sets the time and the registers
-  // go to the accumulators.
-  static constexpr int unroll(int R) { return R >= 8 ? 2 : 4; }
-  // 8 e4m3 codes (memory order: byte 0 first) -> fp32
-  static __device__ __forceinline__ void unpack8(const Vec& w, float* f) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
-      const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
-      f[4 * i] = lo[0];
-      f[4 * i + 1] = lo[1];
-      f[4 * i + 2] = hi[0];
-      f[4 * i + 3] = hi[1];
-    }
-  }
-};
 
 // ---- attention ---------------------------------------------------------------------------------
 struct AttnArgs {
@@ -540,9 +495,6 @@ __global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict
   if (d == 0 && lse) lse[bh] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 template <class Fmt, int D>
 void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
   const dim3 block(kThreads);
@@ -608,14 +560,7 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
       hipLaunchKernelGGL(attn_decode_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, H, a.nsplit, a.ob, a.oh);
     e = hipGetLastError();
   } else if (a.nsplit > 1) {
-    const dim3 cgrid((unsigned)H, (unsigned)B, (unsigned)Tq);
-    if (D == 64)
-      hipLaunchKernelGGL(attn_kv_combine<64>, cgrid, dim3(64), 0, s, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot,
-                         a.oh);
-    else
-      hipLaunchKernelGGL(attn_kv_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot,
-                         a.oh);
-    e = hipGetLastError();
+    e = launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s);
   }
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
@@ -700,6 +645,16 @@ __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ 
 }
 
 }  // namespace
+
+hipError_t kfkv::launch_kv_combine(int D, const float* ws, __bf16* o, float* lse, int B, int H, int Tq, int nsplit,
+                                   long long ob, long long ot, long long oh, hipStream_t s) {
+  const dim3 cgrid((unsigned)H, (unsigned)B, (unsigned)Tq);
+  if (D == 64)
+    hipLaunchKernelGGL(attn_kv_combine<64>, cgrid, dim3(64), 0, s, ws, o, lse, B, H, Tq, nsplit, ob, ot, oh);
+  else
+    hipLaunchKernelGGL(attn_kv_combine<128>, cgrid, dim3(128), 0, s, ws, o, lse, B, H, Tq, nsplit, ob, ot, oh);
+  return hipGetLastError();
+}
 
 extern "C" int kfamd_attn_decode_split_keys(void) { return kSplitKeys; }
 

@@ -272,6 +272,28 @@ int kfamd_attn_extend_fp8(const void* q, const void* k_codes, const void* v_code
                           const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
                           int Tq, int t_bound, float scale, const long long* strides, void* stream);
 
+// ---- chunked-prefill attention (attn_kv_mfma.hip) ---------------------------------------------
+// kfamd_attn_extend_bf16 / _fp8 without the row limit, on MFMA query tiles: Tq (1 .. 65535) new rows per
+// (b, h), already appended to the cache; the same tensors, stride arrays, lens / t_bound contract (row i
+// attends keys 0 .. lens[b] - Tq + i; a negative limit writes zeros and lse = -inf; nothing at or beyond
+// lens[b] is used), lse [B][Tq][H] and return codes. One workgroup takes kfamd_attn_chunk_tile_rows() query
+// rows of one (b, h) and one split of the keys.
+//   kfamd_attn_chunk_nsplit: the launcher's split count, from host values only: with tiles = ceil(Tq /
+//     tile_rows), clamp(ceil(256 / (tiles * H * B)), 1, ceil(t_bound / split_keys)); 0 for a rejected shape.
+//     It does not fall when t_bound grows.
+//   kfamd_attn_chunk_workspace: bytes of ws for that split count, B * H * Tq * nsplit * (D + 2) * 4 (below
+//     2 * 256 * tile_rows * (D + 2) * 4: 34.1 MB at D = 128); 16 with one split, where ws is unused and may
+//     be null; 0 for a rejected shape (D not 64 / 128, Tq outside 1 .. 65535, t_bound < 1).
+int kfamd_attn_chunk_tile_rows(void);
+int kfamd_attn_chunk_nsplit(int B, int H, int Tq, int t_bound);
+long long kfamd_attn_chunk_workspace(int B, int H, int D, int Tq, int t_bound);
+int kfamd_attn_chunk_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                          float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
+                          const long long* strides, void* stream);
+int kfamd_attn_chunk_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                         const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
+                         int Tq, int t_bound, float scale, const long long* strides, void* stream);
+
 // Weight-streaming NT GEMM for 1 <= M <= 16 (gemm_skinny_bf16.hip): C[M][N] = act(alpha * A[M][K] .
 // W[N][K]^T + bias[N]) (+ R[M][N]); K % 8 == 0, A / W rows 16-B aligned, any N, epilogue semantics of
 // kfamd_gemm_nt_bf16. KFAMD_EINVAL: M outside 1..16 (or K % 8); KFAMD_EALIGN: alignment.

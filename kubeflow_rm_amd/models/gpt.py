@@ -434,7 +434,7 @@ class GPT(torch.nn.Module):
 
     @torch.no_grad()
     def extend(self, idx: torch.Tensor, cache, last_only: bool = False,
-               weights: "DecodeWeights | None" = None) -> torch.Tensor:
+               weights: "DecodeWeights | None" = None, chunk: int | None = None) -> torch.Tensor:
         """Append ``idx [B, T]`` (T >= 1 tokens per row) to ``cache`` in any state, empty included; logits
         ``[B, T, vocab]`` of every new position (``[B, vocab]`` of the last one with ``last_only``).
         Advances the cache by T. On the GPU a step of up to 16 tokens runs the decode kernels with
@@ -446,26 +446,43 @@ class GPT(torch.nn.Module):
         rows, reads the 8-bit weights; the LM head does by its own row count (B with ``last_only``). Chunks
         with more rows read the bf16 weights, as ``prefill`` always does (compute-bound, and the originals
         are there). The rule looks at row counts only, on every device: the CPU / ``ops.torch_reference()``
-        path applies it with the dequantised weights."""
+        path applies it with the dequantised weights.
+
+        ``chunk=N`` (16 < N <= the cache's capacity): the input runs in steps of N tokens per row instead of 16,
+        attention on ``ops.attention_chunk`` (MFMA query tiles over the cache, K / V read once per 128 new
+        rows), the linears on the route the step's row count B * N picks (the bf16 weights above 16 rows,
+        whatever ``weights`` holds). It always means that kernel, a last step of 16 tokens or fewer included.
+        What a follow-up turn or a long prompt over a cache in any state takes: N rows of activations at a
+        time, one pass over the weights per N tokens. Capturable for a fixed T like the default path (one
+        eager call first: the attention workspace is allocated on first use). ``chunk=None`` is the path
+        described above, unchanged."""
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError(f"extend: idx [B, T >= 1] expected, got {tuple(idx.shape)}")
         B, T = idx.shape
         self._check_cache(cache, B, T)
         native = self._native_decode(self.tok)
         R = ops.decode.MAX_EXTEND_ROWS
+        if chunk is not None:
+            if isinstance(chunk, bool) or not isinstance(chunk, int) or not R < chunk <= cache.capacity:
+                raise ValueError(f"extend(chunk=...): an int in {R + 1} .. the cache's capacity ({cache.capacity}) "
+                                 f"expected, got {chunk!r}")
+            R = chunk
         outs = []
         for t0 in range(0, T, R):
             final = t0 + R >= T
             if last_only and not final:
-                self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none", weights=weights)
+                self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none", weights=weights,
+                                   mfma=chunk is not None)
             else:
                 outs.append(self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="last" if last_only else "all",
-                                               weights=weights))
+                                               weights=weights, mfma=chunk is not None))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
 
-    def _extend_chunk(self, idx, cache, native: bool, head: str, weights=None):
-        """One extend step of T <= 16 tokens per row; ``head``: LM head on "all" rows, the "last", or "none"."""
+    def _extend_chunk(self, idx, cache, native: bool, head: str, weights=None, mfma: bool = False):
+        """One extend step of T tokens per row (T <= 16 on ``ops.attention_extend``; any T with ``mfma``, on
+        ``ops.attention_chunk``); ``head``: LM head on "all" rows, the "last", or "none"."""
         B, T = idx.shape
+        attend = ops.attention_chunk if mfma else ops.attention_extend
         c = self.cfg
         pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
         x = F.embedding(idx, self.tok) + F.embedding(pos, self.pos)  # [B, T, d_model]
@@ -482,7 +499,7 @@ class GPT(torch.nn.Module):
                 qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, 3 * h * hd)
                 ops.kv_append(qkv, cache, li)
                 a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
-                ops.attention_extend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, out=a.view(B, T, h, hd), **att)
+                attend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, out=a.view(B, T, h, hd), **att)
                 x = lin(a.view(B * T, h * hd), wsel(li, "proj"), blk.proj.bias, residual=x)
                 y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
                 y = lin(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
@@ -490,7 +507,7 @@ class GPT(torch.nn.Module):
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
                 ops.kv_append(qkv, cache, li)  # torch ops: CPU tensors / torch_reference()
-                a = ops.attention_extend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, **att).reshape(B, T, h * hd)
+                a = attend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, **att).reshape(B, T, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
                 y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
                 x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
@@ -552,7 +569,7 @@ class GPT(torch.nn.Module):
                  generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
                  lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None,
                  weight_dtype: torch.dtype | None = None, top_p: float | None = None, stop_token: int | None = None,
-                 sampler: str = "torch"):
+                 sampler: str = "torch", prefill_chunk: int | None = None):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -580,7 +597,16 @@ class GPT(torch.nn.Module):
         sync and no early exit, every row runs ``max_new_tokens`` steps. It combines with ``kv_dtype``,
         ``weight_dtype`` and ``graph``; with ``graph=True`` the captured graph holds the step, the sampler and
         the token feedback (``graphed_generate_step``), so a token costs one replay. ``draft`` keeps its own
-        greedy sampler: ``sampler="fused"`` with it raises."""
+        greedy sampler: ``sampler="fused"`` with it raises.
+
+        ``prefill_chunk=N`` (16 < N <= prompt + max_new_tokens, the cache's capacity): the prompt runs as
+        ``extend(idx, cache, last_only=True, chunk=N)`` instead of ``prefill``: N tokens per row at a time through
+        ``ops.attention_chunk``, so the prompt's activation memory is bounded by N rows whatever its length.
+        Each step attends the cache, not the QKV activation: with ``kv_dtype=torch.float8_e4m3fn`` the prompt
+        then attends the QUANTISED K / V it has stored, where ``prefill`` attends the unquantised rows, so the
+        logits differ from a bf16 cache's from the first token on. It raises with ``draft``."""
+        if prefill_chunk is not None and draft is not None:
+            raise ValueError("generate(prefill_chunk=...) cannot be combined with draft=")
         if sampler not in ("torch", "fused"):
             raise ValueError(f'generate(sampler=...): "torch" or "fused" expected, got {sampler!r}')
         if sampler == "torch" and (top_p is not None or stop_token is not None):
@@ -613,7 +639,10 @@ class GPT(torch.nn.Module):
         if graph and not idx.is_cuda:
             raise ValueError("generate(graph=True) needs GPU tensors")
         cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
-        logits = self.prefill(idx, cache)
+        if prefill_chunk is None:
+            logits = self.prefill(idx, cache)
+        else:  # the bf16 weights, as prefill: a prompt is not a decode step
+            logits = self.extend(idx, cache, last_only=True, chunk=prefill_chunk)
         weights = self.decode_weights() if weight_dtype is not None else None
         if sampler == "fused":
             return self._generate_fused(idx, logits, cache, weights, max_new_tokens, temperature, top_k, top_p,

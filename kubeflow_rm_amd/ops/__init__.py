@@ -8,7 +8,7 @@ from .attention import attention_qkv, attn_block, flash_attention, split_heads  
 from .attention import supported as attention_supported  # noqa: F401
 from .allreduce import OneShotAllReduce  # noqa: F401
 from .graph import GraphedCallable  # noqa: F401
-from .decode import KVCache, attention_decode, attention_extend, kv_append  # noqa: F401
+from .decode import KVCache, attention_chunk, attention_decode, attention_extend, kv_append  # noqa: F401
 from . import decode  # noqa: F401
 from .sample import sample  # noqa: F401  (the function shadows its module: import names from ops.sample directly)
 

@@ -102,6 +102,13 @@ _SIGNATURES = {
                                       c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_attn_extend_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                       c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_tile_rows": (c_int, []),
+    "kfamd_attn_chunk_nsplit": (c_int, [c_int, c_int, c_int, c_int]),
+    "kfamd_attn_chunk_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_chunk_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                      c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                     c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_gemm_nt_skinny_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
                                           c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_bf16_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,

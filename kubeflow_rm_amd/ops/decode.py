@@ -17,6 +17,11 @@ a step in flight.
 T <= 16 new query rows per head, already appended, each attending the cache up to its own row; with
 ``KVCache.rewind(n)`` (drop the last n rows) it carries ``GPT.extend`` and draft-and-verify decoding.
 
+``attention_chunk(q, cache, layer)`` is the same contract without the row limit, on MFMA query tiles
+(``attn_chunk_split`` in ``kernels/attn_kv_mfma.hip``: K / V read once per 128 new rows): 1 <= T <= capacity
+new rows, which carries ``GPT.extend(chunk=N)`` and ``GPT.generate(prefill_chunk=N)`` — a follow-up turn or a
+long prompt over a cache that is not empty, N rows of activations at a time.
+
 On CPU tensors the same functions run plain torch (index copy, masked fp32 SDPA): the CPU model path
 and its tests. On a GPU there is no fallback: a shape the kernels reject raises.
 
@@ -121,6 +126,7 @@ class KVCache:
         self._bound, self._pinned = 0, False
         self.workspace = None
         self.extend_workspace = None  # attention_extend's, allocated on its first use
+        self.chunk_workspace = None  # attention_chunk's, allocated on its first use, grown when a call needs more
         if self.device.type == "cuda" and dtype in CACHE_DTYPES and D in HEAD_DIMS:  # the kernels' shapes
             nbytes = _lib.lib().kfamd_attn_decode_workspace(B, H, D, capacity)
             self.workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
@@ -133,7 +139,8 @@ class KVCache:
     def nbytes(self) -> int:
         """Bytes this cache holds: K / V (codes), the scales of an FP8 cache, and the attention workspaces
         allocated so far. ``lens`` and its step buffer (8 bytes per batch row) are not counted."""
-        ts = [*self.k, *self.v, *(self.k_scale or []), *(self.v_scale or []), self.workspace, self.extend_workspace]
+        ts = [*self.k, *self.v, *(self.k_scale or []), *(self.v_scale or []), self.workspace, self.extend_workspace,
+              self.chunk_workspace]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     @property
@@ -190,6 +197,18 @@ class KVCache:
             nbytes = _lib.lib().kfamd_attn_extend_workspace(self.B, self.H, self.D, MAX_EXTEND_ROWS, self.capacity)
             self.extend_workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
         return self.extend_workspace
+
+    def _chunk_ws(self, T: int) -> torch.Tensor:
+        """attention_chunk's split workspace for T query rows: ``kfamd_attn_chunk_workspace`` at the capacity
+        (the split count does not fall when t_bound grows, so it serves every t_bound), allocated on first
+        use and replaced by a larger one when a later T needs more, never inside a capture."""
+        nbytes = int(_lib.lib().kfamd_attn_chunk_workspace(self.B, self.H, self.D, T, self.capacity))
+        if self.chunk_workspace is None or self.chunk_workspace.numel() < nbytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"attention_chunk: run one step of T = {T} rows before capturing (the workspace "
+                                   "is allocated on first use)")
+            self.chunk_workspace = torch.empty(max(nbytes, 16), device=self.device, dtype=torch.uint8)
+        return self.chunk_workspace
 
 
 def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
@@ -375,4 +394,60 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
             _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
                 *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
     _lib.check(rc, f"attention_extend[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")
+    return (out, lse) if return_lse else out
+
+
+def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
+                    out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
+                    t_bound: int | None = None, return_lse: bool = False):
+    """``attention_extend`` without the row limit: softmax(scale * q k^T) v for T new query rows per head
+    (1 <= T <= capacity on a GPU), q ``[B, T, H, D]`` (any b / t / h strides), already appended to ``cache``
+    layer ``layer``; ``lens[b]`` counts the keys INCLUDING the T new rows, row i attends keys
+    ``0 .. lens[b] - T + i`` (a negative limit gives zeros, lse = -inf). ``out``, ``lens``, ``t_bound`` and
+    ``return_lse`` as there. On a GPU it always runs the MFMA kernel (``kernels/attn_kv_mfma.hip``: 128-row
+    query tiles, K / V read once per tile and split, P rounded to bf16 for the P.V product), whatever T is:
+    for T <= 16 it agrees with ``attention_extend`` within the kernels' bounds, not bit for bit. On CPU
+    tensors and under ``ops.torch_reference()`` it is the same torch code as ``attention_extend``."""
+    B, H, D = cache.B, cache.H, cache.D
+    if q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (H, D):
+        raise ValueError(f"attention_chunk: q [{B}, T, {H}, {D}] expected, got {tuple(q.shape)}")
+    T = q.shape[1]
+    if T < 1:
+        raise ValueError("attention_chunk: at least one query row expected")
+    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    lens = cache.lens if lens is None else lens
+    t_bound = cache.t_bound if t_bound is None else int(t_bound)
+    k, v = cache.k[layer], cache.v[layer]
+    if not _native(q):
+        if cache.fp8:
+            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), torch.float32)
+        o, lse = _attention_extend_torch(q, k, v, lens, scale)
+        o = o.to(q.dtype)
+        if out is not None:
+            out.copy_(o)
+            o = out
+        return (o, lse) if return_lse else o
+    if T > cache.capacity:
+        raise ValueError(f"attention_chunk: 1 <= T <= capacity ({cache.capacity}) query rows expected on a GPU, "
+                         f"got {T}")
+    if D not in HEAD_DIMS:
+        raise ValueError(f"attention_chunk: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
+    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
+        raise ValueError("attention_chunk: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
+    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
+        raise ValueError("attention_chunk: lens must be a device int32 [B] tensor")
+    if not 1 <= t_bound <= cache.capacity:
+        raise ValueError(f"attention_chunk: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
+    if out is None:
+        out = torch.empty(B, T, H, D, device=q.device, dtype=q.dtype)
+    elif tuple(out.shape) != (B, T, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
+        raise ValueError(f"attention_chunk: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
+                         "head dim")
+    lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
+    fn, scales, tag = _entry("kfamd_attn_chunk", cache, layer)
+    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
+            lse.data_ptr() if lse is not None else None, cache._chunk_ws(T).data_ptr(), B, H, D, T, t_bound, scale,
+            _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
+                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
+    _lib.check(rc, f"attention_chunk[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")
     return (out, lse) if return_lse else out

@@ -38,6 +38,13 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         and gpt-1b (gpt-small only with --quick), B in {1, 16}, temperature 1, top_k = 50, graphed, ms/token:
         the torch sampler between replays of graphed_decode_step against graphed_generate_step (step,
         sampler and token feedback in one graph), interleaved runs.
+  chunk   (not in the default list) chunked prefill. Kernel: ops.attention_chunk at T in {16, 32, 64, 128, 256,
+        512} new rows over 128 / 2048 / 4096 prior keys (D = 128, capacity 4096, B*H in {16, 128}, bf16 and FP8
+        caches, rotated) against the only other way to do the same work, ceil(T / 16) calls of
+        ops.attention_extend on 16-row slices with lens stepped, and against the ceiling, ops.attention_qkv
+        (the flash kernel, causal) on T rows with no prior keys. Model: gpt-small and gpt-1b, B = 1, a
+        512-token turn on a cache of 1536: extend(chunk=128 / 256 / 512) against extend without chunk, eager.
+        Medians of 7 interleaved blocks with min and max.
 """
 from __future__ import annotations
 
@@ -54,7 +61,9 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 ROOF = 6.29e12
-STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420}
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
+                "chunk": 900}
+CHUNK_TS = (16, 32, 64, 128, 256, 512)
 KV8_TS = (4, 8)
 EXTEND_TS = (1, 2, 4, 8, 16)
 GEMM_MS = (1, 2, 4, 8, 16)  # 2 and 4: where the VALU / MFMA cut-over of the skinny kernel is decided
@@ -283,6 +292,94 @@ def _extend_model_rows(quick: bool):
 
 def step_extend(quick: bool):
     return {"kernel": _extend_kernel_rows(quick), "model": _extend_model_rows(quick)}
+
+
+def _chunk_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    D, cap = 128, 4096
+    for BH in ((16,) if quick else (16, 128)):
+        B, H = BH // 16, 16
+        ncopy = 1 if quick else max(1, min(4, (512 << 20) // (2 * B * H * cap * D * 2)))
+        caches = _kv8_caches(B, H, D, cap, ncopy)
+        for prior in (128, 2048, 4096):
+            for T in CHUNK_TS:
+                n = prior + T
+                if n > cap:  # 4096 prior keys: the block is the cache's last T rows
+                    n, prior = cap, cap - T
+                qkv = torch.randn(B, T, 3 * H * D, device="cuda").to(torch.bfloat16)
+                q = qkv.view(B, T, 3, H, D)[:, :, 0]
+                out = torch.empty(B, T, H, D, device="cuda", dtype=torch.bfloat16)
+                lens16 = [torch.full((B,), prior + min(t0 + 16, T), device="cuda", dtype=torch.int32)
+                          for t0 in range(0, T, 16)]
+                fns = {"flash_no_prior": lambda i: ops.attention_qkv(qkv, H, D, causal=True)}
+                for kind, cache in caches.items():
+                    cache.set_lens([n] * B)
+
+                    def chunk(i, c=cache):
+                        ops.attention_chunk(q, c, i % ncopy, out=out, t_bound=n)
+
+                    def extend16(i, c=cache):  # the same rows, 16 at a time, each slice up to its own last row
+                        for j, t0 in enumerate(range(0, T, 16)):
+                            ops.attention_extend(q[:, t0:t0 + 16], c, i % ncopy, out=out[:, t0:t0 + 16], lens=lens16[j],
+                                                 t_bound=n)
+
+                    fns[f"chunk_{kind}"], fns[f"extend16_{kind}"] = chunk, extend16
+                r = _time_blocks(fns, blocks=5 if quick else 7, iters=10)
+                row = {"B": B, "H": H, "D": D, "prior": prior, "T": T, "cache_copies": ncopy, **r}
+                for kind in caches:
+                    a, b = r[f"chunk_{kind}"], r[f"extend16_{kind}"]
+                    row[f"extend16_over_chunk_{kind}"] = b["median_us"] / a["median_us"]
+                    row[f"verdict_{kind}"] = ("tie" if a["min_us"] <= b["max_us"] and b["min_us"] <= a["max_us"]
+                                              else "chunk wins" if a["median_us"] < b["median_us"] else "chunk loses")
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+        del caches
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _chunk_model_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    rows = []
+    pos, T, cap = 1536, 512, 2048
+    for name in (("gpt-small",) if quick else ("gpt-small", "gpt-1b")):
+        cfg = CONFIGS[name]
+        model = GPT(cfg, device="cuda").eval()
+        cache = model.new_cache(1, cap)
+        for t in (*cache.k, *cache.v):
+            t.normal_()
+        toks = torch.randint(0, cfg.vocab_size, (1, T), device="cuda")
+        cands = {"extend16": lambda: model.extend(toks, cache, last_only=True)}
+        for N in (128, 256, 512):
+            cands[f"chunk{N}"] = lambda N=N: model.extend(toks, cache, last_only=True, chunk=N)
+        times = {k: [] for k in cands}
+        for b in range(-1, 5 if quick else 7):  # block -1: warm-up, not recorded
+            for k, f in cands.items():
+                cache.set_lens([pos])  # a sync, outside the timed region: every run starts at the same position
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                e1.synchronize()
+                if b >= 0:
+                    times[k].append(e0.elapsed_time(e1))  # ms per turn of T tokens
+        row = {"model": name, "B": 1, "T": T, "position": pos, "capacity": cap}
+        for k, v in times.items():
+            row[k] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)}
+        for N in (128, 256, 512):
+            row[f"extend16_over_chunk{N}"] = row["extend16"]["median_ms"] / row[f"chunk{N}"]["median_ms"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del model, cache
+        torch.cuda.empty_cache()
+    return rows
+
+
+def step_chunk(quick: bool):
+    return {"kernel": _chunk_kernel_rows(quick), "model": _chunk_model_rows(quick)}
 
 
 def _kv8_caches(B, H, D, cap, ncopy):
@@ -670,7 +767,7 @@ def step_sample(quick: bool):
     return result
 
 
-STEPS = {"sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+STEPS = {"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
