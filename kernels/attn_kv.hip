@@ -52,6 +52,28 @@
 // leaves 4-lane groups, which wave_ops.h's group reductions do not cover, and it doubles the
 // accumulators per lane, a certain spill at 8 row slots.
 //
+// Grouped-query attention (G query heads per K / V head, query head h on K / V head h / G; G in {1, 2, 4, 8,
+// 16}): the G heads of a token are more rows on the same K / V stream. The grouped entry points launch
+// attn_extend_split<Fmt, D, R, true> on the grid (split, K / V head, b) with the T * G rows of a K / V head
+// flattened token-major (RowMap below: r = t * G + g, limit lens[b] - T + r / G, non-decreasing in r, which
+// the split launches row0 .. row0 + 7 rely on). The mapping enters the q load, the limit, the o / lse stores;
+// the split records are indexed by (b, K / V head, r) and attn_kv_combine_gqa<D> applies the same mapping to
+// its store. Routing: T * G <= 16 rows, 1 .. 8 row slots per launch and two launches for 9 .. 16 rows, as
+// for plain rows; decode (T = 1) with G > 1 is this body with R = G slots (G = 16: two launches), and
+// attn_decode_split stays the G = 1 single-row body. G = 1 through a grouped entry point launches the plain
+// kernels. The group size is a kernel argument (lg = log2 G) read only by the GQ = true instantiations: the
+// GQ = false ones are the kernels as they were (same registers, o and lse bit-identical to the previous build
+// on 186 decode / extend / chunk / append outputs).
+// Cut-over (profiles/gqa; D = 128, capacity 4096, B = 8 x 16 query heads, 2048 / 4096 keys, medians of 7
+// interleaved blocks, caches rotated): at 8 rows per K / V head (G = 8 decode; G = 4, T = 2; G = 2, T = 4) this
+// form takes 26 - 67 us where attn_chunk_split takes 16 - 41 us, 1.5 - 2.0x; at 16 rows (two launches here)
+// 46 - 124 us against 16 - 41 us, 2.5 - 3.7x; bf16 and FP8 alike, every case beyond the blocks' spread. 8 row
+// slots are VALU-bound, as for plain rows, and the grouped grid has only B * Hkv * nsplit workgroups. So for
+// G > 1 ops.attention_decode / attention_extend take this form below 8 rows (G = 2, 4 decode; G = 2, T <= 3)
+// and the MFMA form from 8 rows on (ops.decode.GQA_MFMA_MIN_ROWS); G = 1 does not move. The entry points
+// here still serve every T * G <= 16. Decode time against G as routed: profiles/gqa/README.md — it does
+// not follow the K / V bytes: G = 2 is 1.2 - 1.6x and G = 4 1.1 - 2.1x faster than G = 1 on this form.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): VGPRs, the same
 // at D = 64 and at D = 128 unless two are given; scratch is 0 for every instantiation. "before": the four
 // kernels this file replaced, D = 64 / 128.
@@ -67,6 +89,9 @@
 //   attn_extend_split<Fp8Rows, D, 4>    149   150 / 150
 //   attn_extend_split<Fp8Rows, D, 8>    197   198 / 198
 //   kv_append / kv_append_fp8<D>     21 / 39   21 /  39
+// The GQ = true instantiations of attn_extend_split use the same VGPRs as the GQ = false rows above, R for R
+// (64 / 92 / 129 / 201 and 84 / 112 / 149 / 197), the same LDS, scratch 0; attn_kv_combine<D> and
+// attn_kv_combine_gqa<D> 12 VGPRs each.
 // The extend body's LDS merge is written as one pass and, for R = 8, a guarded second one: as a loop over
 // the passes with an early exit it cost R = 1 up to 13 VGPRs (Fp8Rows, D = 64: 97, one wave per SIMD less).
 // Measured (profiles/decode, profiles/extend, profiles/kv_fp8, profiles/attn_kv_unify; D = 128, capacity
@@ -104,6 +129,7 @@ struct AttnArgs {
   float* ws;
   int B, H, Tq, row0, t_bound, nsplit;  // a split launch holds rows row0 .. row0 + R - 1 of the Tq
   float scale_log2;
+  int lg;  // GQ kernels only: log2 of the group size G. H is then Hkv and Tq the T * G flattened rows
   long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
 };
 
@@ -267,8 +293,21 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
     }
   }
 }
+// Where row r of the Tq rows of (b, h) lives. Plain (GQ = false): row r is token r of head h. Grouped
+// (GQ = true): h is a K / V head, the rows are the T * G (token, head-in-group) pairs flattened token-major,
+// r = t * G + g: token r >> lg of query head (h << lg) + (r & (G - 1)), which attends keys
+// 0 .. len - T + (r >> lg) — non-decreasing in r, as the split launches row0 .. row0 + 7 assume.
+template <bool GQ>
+struct RowMap {
+  int lg, T, Hq, h0;
+  __device__ __forceinline__ RowMap(int lg_, int Tq, int H, int h)
+      : lg(GQ ? lg_ : 0), T(Tq >> lg), Hq(H << lg), h0(h << lg) {}
+  __device__ __forceinline__ int tok(int r) const { return r >> lg; }
+  __device__ __forceinline__ int head(int r) const { return h0 + (r & ((1 << lg) - 1)); }
+};
+
 // workspace: [B][H][Tq][nsplit][2] (m, l) then [B][H][Tq][nsplit][D] (o), fp32
-template <class Fmt, int D, int R>
+template <class Fmt, int D, int R, bool GQ>
 __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
@@ -284,6 +323,7 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   const int tid = threadIdx.x;
   const int grp = tid / G, piece = tid % G;
   const int Tq = a.Tq, row0 = a.row0;
+  const RowMap<GQ> rm(a.lg, Tq, a.H, h);
 
   __shared__ float s_m[NG][RC], s_l[NG][RC];
   __shared__ float s_o[NG][RC][D + 4];
@@ -305,8 +345,8 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
         }
         if (tid < D) a.ws[nrows * a.nsplit * 2 + (row * a.nsplit + split) * D + tid] = 0.f;
       } else {
-        if (tid < D) a.o[b * a.ob + r * a.ot + h * a.oh + tid] = (__bf16)0.f;
-        if (tid == 0 && a.lse) a.lse[((long long)b * Tq + r) * a.H + h] = -INFINITY;
+        if (tid < D) a.o[b * a.ob + rm.tok(r) * a.ot + rm.head(r) * a.oh + tid] = (__bf16)0.f;
+        if (tid == 0 && a.lse) a.lse[((long long)b * rm.T + rm.tok(r)) * rm.Hq + rm.head(r)] = -INFINITY;
       }
     }
     return;
@@ -319,10 +359,11 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   for (int r = 0; r < R; ++r) {
     const int gr = row0 + r;               // the slot's row of the Tq
     const int rr = gr < Tq ? gr : Tq - 1;  // padding slots read a valid row
-    Bf16Rows::unpack8(*reinterpret_cast<const u32x4*>(a.q + b * a.qb + rr * a.qt + h * a.qh + piece * 8), qf[r]);
+    Bf16Rows::unpack8(
+        *reinterpret_cast<const u32x4*>(a.q + b * a.qb + rm.tok(rr) * a.qt + rm.head(rr) * a.qh + piece * 8), qf[r]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) qf[r][i] *= a.scale_log2;
-    nk[r] = gr < Tq ? len - Tq + gr + 1 : 0;
+    nk[r] = gr < Tq ? len - rm.T + rm.tok(gr) + 1 : 0;
   }
 
   const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh + piece * 8;
@@ -430,8 +471,9 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
         if (d == 0) *reinterpret_cast<float2*>(a.ws + (row * a.nsplit + split) * 2) = make_float2(M, L);
       } else {
         const bool any = L > 0.f;  // a row before the sequence's start (lens[b] < Tq) sees no key
-        a.o[b * a.ob + r * a.ot + h * a.oh + d] = (__bf16)(any ? O / L : 0.f);
-        if (d == 0 && a.lse) a.lse[((long long)b * Tq + r) * a.H + h] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
+        a.o[b * a.ob + rm.tok(r) * a.ot + rm.head(r) * a.oh + d] = (__bf16)(any ? O / L : 0.f);
+        if (d == 0 && a.lse)
+          a.lse[((long long)b * rm.T + rm.tok(r)) * rm.Hq + rm.head(r)] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
       }
     }
   };
@@ -447,11 +489,12 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
 // The merge of the splits' per-row (m, l, o[D]) fp32 records into bf16 rows: reads only the workspace.
 // B is an argument, not gridDim.y: the launch dimensions are read from beyond the 64 bytes of arguments,
 // one more serial scalar-load miss per call of a kernel that runs for a few microseconds.
-template <int D>
-__global__ __launch_bounds__(D) void attn_kv_combine(const float* __restrict__ ws, __bf16* __restrict__ o,
-                                                     float* __restrict__ lse, int B, int H, int Tq, int nsplit,
-                                                     long long ob, long long ot, long long oh) {
+template <int D, bool GQ>
+__device__ __forceinline__ void kv_combine_row(const float* __restrict__ ws, __bf16* __restrict__ o,
+                                               float* __restrict__ lse, int B, int H, int Tq, int nsplit, long long ob,
+                                               long long ot, long long oh, int lg) {
   const int h = blockIdx.x, b = blockIdx.y, r = blockIdx.z, d = threadIdx.x;
+  const RowMap<GQ> rm(lg, Tq, H, h);
   const long long nrows = (long long)B * H * Tq;
   const long long row = ((long long)b * H + h) * Tq + r;
   const float* ml = ws + row * nsplit * 2;
@@ -466,8 +509,25 @@ __global__ __launch_bounds__(D) void attn_kv_combine(const float* __restrict__ w
     O += po[s * D + d] * w;
   }
   const bool any = L > 0.f;  // no key at all
-  o[b * ob + r * ot + h * oh + d] = (__bf16)(any ? O / L : 0.f);
-  if (d == 0 && lse) lse[((long long)b * Tq + r) * H + h] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
+  o[b * ob + rm.tok(r) * ot + rm.head(r) * oh + d] = (__bf16)(any ? O / L : 0.f);
+  if (d == 0 && lse)
+    lse[((long long)b * rm.T + rm.tok(r)) * rm.Hq + rm.head(r)] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
+}
+
+template <int D>
+__global__ __launch_bounds__(D) void attn_kv_combine(const float* __restrict__ ws, __bf16* __restrict__ o,
+                                                     float* __restrict__ lse, int B, int H, int Tq, int nsplit,
+                                                     long long ob, long long ot, long long oh) {
+  kv_combine_row<D, false>(ws, o, lse, B, H, Tq, nsplit, ob, ot, oh, 0);
+}
+
+// The grouped form (RowMap<true>): H is Hkv, Tq the T * G flattened rows. A kernel of its own: the plain
+// one's arguments end at 64 bytes (above).
+template <int D>
+__global__ __launch_bounds__(D) void attn_kv_combine_gqa(const float* __restrict__ ws, __bf16* __restrict__ o,
+                                                         float* __restrict__ lse, int B, int H, int Tq, int nsplit,
+                                                         long long ob, long long ot, long long oh, int lg) {
+  kv_combine_row<D, true>(ws, o, lse, B, H, Tq, nsplit, ob, ot, oh, lg);
 }
 
 // The same merge for the single-row kernel's records (Tq = 1, no t stride), kept next to it for the reason
@@ -495,26 +555,38 @@ __global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict
   if (d == 0 && lse) lse[bh] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
 }
 
-template <class Fmt, int D>
+template <class Fmt, int D, bool GQ>
 void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
   const dim3 block(kThreads);
-  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1>), grid, block, 0, s, a);
-  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2>), grid, block, 0, s, a);
-  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8>), grid, block, 0, s, a);
+  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ>), grid, block, 0, s, a);
+  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ>), grid, block, 0, s, a);
+  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ>), grid, block, 0, s, a);
+}
+
+template <class Fmt, int D>
+void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
+  if (a.lg > 0) launch_split<Fmt, D, true>(a, n, grid, s);  // G = 1 through a grouped entry point: the plain kernels
+  else launch_split<Fmt, D, false>(a, n, grid, s);
 }
 
 // The one launcher behind the four attention entry points. st: the entry point's stride array, q (b, [t,]
 // h), k (b, h, t), v (b, h, t), o (b, [t,] h), then for a scaled format k_scale (b, h), v_scale (b, h);
 // has_t: the t strides are present. Without them it is a single-row entry point (Tq = 1), which launches
-// attn_decode_split. Every KFAMD_EINVAL condition is tested before any KFAMD_EALIGN one.
+// attn_decode_split. The grouped entry points pass G > 0: H is then Hkv, Tq the token count T, the q / o
+// strides' h runs over the Hkv * G query heads, and the kernels see T * G rows per (b, K / V head); G = 1
+// there launches what the plain entry points launch. Every KFAMD_EINVAL condition is tested before any
+// KFAMD_EALIGN one.
 template <class Fmt>
 int attn_kv(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens, void* o,
             float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale, const long long* st,
-            bool has_t, void* stream) {
+            bool has_t, void* stream, int G = 0) {
   if (!q || !k || !v || !lens || !o || !st || B <= 0 || H <= 0 || B > 65535 || H > 65535) return KFAMD_EINVAL;
   if (Fmt::kScaled && (!ks || !vs)) return KFAMD_EINVAL;
-  if ((D != 64 && D != 128) || Tq < 1 || Tq > kMaxRows || t_bound < 1) return KFAMD_EINVAL;
+  const int lg = G > 0 ? group_log2(G) : 0;
+  if (lg < 0 || Tq < 1 || Tq > (kMaxRows >> lg)) return KFAMD_EINVAL;
+  Tq <<= lg;  // rows per (b, K / V head) from here on
+  if ((D != 64 && D != 128) || t_bound < 1) return KFAMD_EINVAL;
   AttnArgs a = {};
   a.qb = *st++, a.qt = has_t ? *st++ : 0, a.qh = *st++;
   a.kb = *st++, a.kh = *st++, a.kt = *st++, a.vb = *st++, a.vh = *st++, a.vt = *st++;
@@ -534,7 +606,7 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
   a.o = static_cast<__bf16*>(o);
   a.lse = lse;
   a.ws = static_cast<float*>(ws);
-  a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound;
+  a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound, a.lg = lg;
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)a.nsplit, (unsigned)H, (unsigned)B);
@@ -560,7 +632,7 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
       hipLaunchKernelGGL(attn_decode_combine<128>, cgrid, dim3(128), 0, s, a.ws, a.o, lse, H, a.nsplit, a.ob, a.oh);
     e = hipGetLastError();
   } else if (a.nsplit > 1) {
-    e = launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s);
+    e = launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s, lg);
   }
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
@@ -570,7 +642,7 @@ __global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv,
                                                  __bf16* __restrict__ vc, const int* __restrict__ pos, int B, int T,
                                                  int H, int D8, int Tcap, long long qb, long long qt, long long kb,
                                                  long long kh, long long kt, long long vb, long long vh,
-                                                 long long vt) {
+                                                 long long vt, int Hq) {  // Hq q heads come before the H k heads
   const long long n = (long long)B * T * 2 * H * D8;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
@@ -586,7 +658,7 @@ __global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv,
   const long long row = (long long)pos[b] + t;
   if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, never written
   const u32x4 val =
-      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)(s + 1) * H + h) * (D8 * 8) + d8 * 8);
+      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)Hq + s * H + h) * (D8 * 8) + d8 * 8);
   __bf16* dst = s == 0 ? kc + b * kb + h * kh + row * kt : vc + b * vb + h * vh + row * vt;
   *reinterpret_cast<u32x4*>(dst + d8 * 8) = val;
 }
@@ -602,7 +674,7 @@ __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ 
                                                      int H, int Tcap, long long qb, long long qt, long long kb,
                                                      long long kh, long long kt, long long vb, long long vh,
                                                      long long vt, long long ksb, long long ksh, long long vsb,
-                                                     long long vsh) {
+                                                     long long vsh, int Hq) {
   constexpr int G = D / 8;
   const long long n = (long long)B * T * 2 * H * G;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -620,7 +692,7 @@ __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ 
   if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, neither codes nor scale written
   float x[8];
   Bf16Rows::unpack8(
-      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)(s + 1) * H + h) * D + piece * 8), x);
+      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)Hq + s * H + h) * D + piece * 8), x);
   float am = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(x[i]));
@@ -647,9 +719,13 @@ __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ 
 }  // namespace
 
 hipError_t kfkv::launch_kv_combine(int D, const float* ws, __bf16* o, float* lse, int B, int H, int Tq, int nsplit,
-                                   long long ob, long long ot, long long oh, hipStream_t s) {
+                                   long long ob, long long ot, long long oh, hipStream_t s, int lg) {
   const dim3 cgrid((unsigned)H, (unsigned)B, (unsigned)Tq);
-  if (D == 64)
+  if (lg > 0 && D == 64)
+    hipLaunchKernelGGL(attn_kv_combine_gqa<64>, cgrid, dim3(64), 0, s, ws, o, lse, B, H, Tq, nsplit, ob, ot, oh, lg);
+  else if (lg > 0)
+    hipLaunchKernelGGL(attn_kv_combine_gqa<128>, cgrid, dim3(128), 0, s, ws, o, lse, B, H, Tq, nsplit, ob, ot, oh, lg);
+  else if (D == 64)
     hipLaunchKernelGGL(attn_kv_combine<64>, cgrid, dim3(64), 0, s, ws, o, lse, B, H, Tq, nsplit, ob, ot, oh);
   else
     hipLaunchKernelGGL(attn_kv_combine<128>, cgrid, dim3(128), 0, s, ws, o, lse, B, H, Tq, nsplit, ob, ot, oh);
@@ -698,14 +774,38 @@ extern "C" int kfamd_attn_extend_fp8(const void* q, const void* k_codes, const v
                           true, stream);
 }
 
+// The grouped-query forms (contract: kfamd_kernels.h): Hkv K / V heads, G query heads on each, T tokens:
+// T * G <= 16 rows per (b, K / V head) on the extend kernels. Decode is T = 1 with t strides of 0.
+extern "C" long long kfamd_attn_extend_gqa_workspace(int B, int Hkv, int G, int D, int T, int t_bound) {
+  const int lg = group_log2(G);
+  if (lg < 0 || T < 1 || T > (kMaxRows >> lg)) return 0;
+  return kfamd_attn_decode_workspace(B, Hkv, D, t_bound) * (T << lg);
+}
+
+extern "C" int kfamd_attn_extend_gqa_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                          void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T,
+                                          int t_bound, float scale, const long long* st, void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
+                           true, stream, G);
+}
+
+extern "C" int kfamd_attn_extend_gqa_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                         const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                         int Hkv, int G, int D, int T, int t_bound, float scale, const long long* st,
+                                         void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
+                          true, stream, G);
+}
+
 // K and V rows of a fused QKV activation [B][T][3][H][D] (element strides qb, qt; [3][H][D] dense)
 // into the caches [B][H][Tcap][D] (strides b, h, t) at rows pos[b] .. pos[b] + T - 1. pos: device
 // int32 [B], not advanced here. Rows at or beyond Tcap are dropped.
-extern "C" int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int H,
-                                    int D, int Tcap, long long qb, long long qt, const long long* cache_strides,
-                                    void* stream) {
+static int kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int Hq, int H,
+                          int D, int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream) {
   if (!qkv || !k_cache || !v_cache || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 || D <= 0 || D % 8 ||
-      Tcap <= 0)
+      Tcap <= 0 || Hq < H || Hq % H || group_log2(Hq / H) < 0)
     return KFAMD_EINVAL;
   const long long* c = cache_strides;
   if (!al16(qkv) || !al16(k_cache) || !al16(v_cache)) return KFAMD_EALIGN;
@@ -714,18 +814,33 @@ extern "C" int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cach
   if ((n + 255) / 256 > 0x7fffffffll) return KFAMD_EINVAL;
   hipLaunchKernelGGL(kv_append, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      static_cast<const __bf16*>(qkv), static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos,
-                     B, T, H, D / 8, Tcap, qb, qt, c[0], c[1], c[2], c[3], c[4], c[5]);
+                     B, T, H, D / 8, Tcap, qb, qt, c[0], c[1], c[2], c[3], c[4], c[5], Hq);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
 
+extern "C" int kfamd_kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int H,
+                                    int D, int Tcap, long long qb, long long qt, const long long* cache_strides,
+                                    void* stream) {
+  return kv_append_bf16(qkv, k_cache, v_cache, pos, B, T, H, H, D, Tcap, qb, qt, cache_strides, stream);
+}
+
+// The same for a grouped-query layer: the activation is [B][T][(Hq + 2 Hkv) D], q: Hq D | k: Hkv D | v: Hkv D,
+// the caches hold the Hkv heads. Hq / Hkv in {1, 2, 4, 8, 16}, KFAMD_EINVAL otherwise.
+extern "C" int kfamd_kv_append_gqa_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T,
+                                        int Hq, int Hkv, int D, int Tcap, long long qb, long long qt,
+                                        const long long* cache_strides, void* stream) {
+  if (Hkv <= 0) return KFAMD_EINVAL;
+  return kv_append_bf16(qkv, k_cache, v_cache, pos, B, T, Hq, Hkv, D, Tcap, qb, qt, cache_strides, stream);
+}
+
 // The same rows quantised row by row into codes [B][H][Tcap][D] and scales [B][H][Tcap].
 // cache_strides = {kb, kh, kt, vb, vh, vt, ksb, ksh, vsb, vsh}.
-extern "C" int kfamd_kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
-                                   const int* pos, int B, int T, int H, int D, int Tcap, long long qb, long long qt,
-                                   const long long* cache_strides, void* stream) {
+static int kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale, const int* pos,
+                         int B, int T, int Hq, int H, int D, int Tcap, long long qb, long long qt,
+                         const long long* cache_strides, void* stream) {
   if (!qkv || !k_codes || !v_codes || !k_scale || !v_scale || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 ||
-      Tcap <= 0)
+      Tcap <= 0 || Hq < H || Hq % H || group_log2(Hq / H) < 0)
     return KFAMD_EINVAL;
   if (D != 64 && D != 128) return KFAMD_EINVAL;
   const long long* c = cache_strides;
@@ -742,10 +857,25 @@ extern "C" int kfamd_kv_append_fp8(const void* qkv, void* k_codes, void* v_codes
   uint8_t* vc = static_cast<uint8_t*>(v_codes);
   if (D == 64)
     hipLaunchKernelGGL(kv_append_fp8<64>, grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, qb, qt,
-                       c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
+                       c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq);
   else
     hipLaunchKernelGGL(kv_append_fp8<128>, grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, qb,
-                       qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
+                       qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
+extern "C" int kfamd_kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                   const int* pos, int B, int T, int H, int D, int Tcap, long long qb, long long qt,
+                                   const long long* cache_strides, void* stream) {
+  return kv_append_fp8(qkv, k_codes, v_codes, k_scale, v_scale, pos, B, T, H, H, D, Tcap, qb, qt, cache_strides,
+                       stream);
+}
+
+extern "C" int kfamd_kv_append_gqa_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                       const int* pos, int B, int T, int Hq, int Hkv, int D, int Tcap, long long qb,
+                                       long long qt, const long long* cache_strides, void* stream) {
+  if (Hkv <= 0) return KFAMD_EINVAL;
+  return kv_append_fp8(qkv, k_codes, v_codes, k_scale, v_scale, pos, B, T, Hq, Hkv, D, Tcap, qb, qt, cache_strides,
+                       stream);
 }

@@ -47,12 +47,26 @@
 // 2 * 256 * 128 and the workspace below 2 * 256 * 128 * (D + 2) * 4 bytes: 34.1 MB at D = 128, 17.3 MB
 // at D = 64.
 //
+// Grouped-query attention (attn_chunk_split<Fmt, D, true>, the kfamd_attn_chunk_gqa_* entry points): the grid's
+// h is a K / V head and the kernel tiles its T * G rows, flattened token-major (r = t * G + g, limit
+// lens[b] - T + r / G). 32 and 128 are multiples of every G in {1, 2, 4, 8, 16}, so a token's heads never
+// straddle a wave or a tile, and the limit is non-decreasing in r, so the tile's last row and the wave's
+// first row still give the highest and the lowest limit. The split count is the rule above with
+// tiles = ceil(T * G / 128) and H := Hkv, T * G <= 65535, the workspace B * Hkv * (T * G) * nsplit * (D + 2) * 4
+// bytes. The GQ = false instantiations are the kernels as they were; G = 1 launches them.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), scratch 0 for all:
-//   instantiation                        VGPRs   LDS bytes
-//   attn_chunk_split<Bf16Rows, 64>        124   32768
-//   attn_chunk_split<Bf16Rows, 128>       232   65536
-//   attn_chunk_split<Fp8Rows, 64>         184   34304
-//   attn_chunk_split<Fp8Rows, 128>        254   67072
+//   instantiation                               VGPRs   LDS bytes
+//   attn_chunk_split<Bf16Rows, 64, false>        124   32768
+//   attn_chunk_split<Bf16Rows, 128, false>       232   65536
+//   attn_chunk_split<Fp8Rows, 64, false>         184   34304
+//   attn_chunk_split<Fp8Rows, 128, false>        254   67072
+//   attn_chunk_split<Bf16Rows, 64, true>         126   32768
+//   attn_chunk_split<Bf16Rows, 128, true>        234   65536
+//   attn_chunk_split<Fp8Rows, 64, true>          185   34304
+//   attn_chunk_split<Fp8Rows, 128, true>         255   67072
+// The grouped limit is no affine function of the row, and with both kept through the key loop
+// <Fp8Rows, 128, true> spilled (256 VGPRs, 8 B scratch): the masked tiles compute the limit again instead.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -86,6 +100,7 @@ struct ChunkArgs {
   float* ws;
   int B, H, Tq, t_bound, nsplit, split_keys;  // split_keys: keys per split, a multiple of kSplitKeys
   float scale_log2;
+  int lg;  // GQ kernels only: log2 of the group size G. H is then Hkv and Tq the T * G flattened rows
   long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
 };
 
@@ -96,7 +111,11 @@ __device__ __forceinline__ Vec bload8(__amdgpu_buffer_rsrc_t r, int byte_off, in
 }
 
 // workspace: attn_kv.hip's, [B][H][Tq][nsplit][2] (m, l) then [B][H][Tq][nsplit][D] (o), fp32
-template <class Fmt, int D>
+// GQ (grouped-query attention): h is a K / V head and the Tq rows are its T * G (token, head-in-group) pairs
+// flattened token-major, r = t * G + g with G = 1 << lg: token r >> lg of query head (h << lg) + (r & (G - 1)),
+// limit len - T + (r >> lg). The limit is non-decreasing in r, so the tile's last row still has the tile's
+// highest limit and a wave's first row its lowest; 32 and 128 are multiples of G.
+template <class Fmt, int D, bool GQ>
 __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
@@ -113,13 +132,15 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int Tq = a.Tq, nsplit = a.nsplit;
+  const int lg = GQ ? a.lg : 0, gmask = (1 << lg) - 1;
+  const int T = Tq >> lg, Hq = a.H << lg, h0 = h << lg;  // tokens, query heads, the group's first query head
 
   int len = a.lens[b];
   len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
   const int q0 = tile * kTileRows, qw = q0 + 32 * w, qrow = qw + r;
   const int qlast = min(q0 + kTileRows, Tq) - 1;  // the tile's last row
   const int k0 = split * a.split_keys;
-  const int k1 = min(k0 + a.split_keys, len - Tq + qlast + 1);  // keys of this split that the last row sees: [k0, k1)
+  const int k1 = min(k0 + a.split_keys, len - T + (qlast >> lg) + 1);  // keys of this split that the last row sees: [k0, k1)
   const long long bh = (long long)b * a.H + h;
   const long long nrows = (long long)a.B * a.H * Tq;
   float* ws_o = a.ws + nrows * nsplit * 2;
@@ -132,24 +153,26 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
         ws_o[(row * nsplit + split) * D + d] = 0.f;
         if (d == 0) *reinterpret_cast<float2*>(a.ws + (row * nsplit + split) * 2) = make_float2(-INFINITY, 0.f);
       } else {
-        a.o[b * a.ob + rr * a.ot + h * a.oh + d] = (__bf16)0.f;
-        if (d == 0 && a.lse) a.lse[((long long)b * Tq + rr) * a.H + h] = -INFINITY;
+        a.o[b * a.ob + (rr >> lg) * a.ot + (h0 + (rr & gmask)) * a.oh + d] = (__bf16)0.f;
+        if (d == 0 && a.lse) a.lse[((long long)b * T + (rr >> lg)) * Hq + h0 + (rr & gmask)] = -INFINITY;
       }
     }
     return;
   }
 
   // this lane's row sees keys 0 .. lim; a padding row (>= Tq) and a row before the sequence's start see none
-  const int lim = qrow < Tq ? len - Tq + qrow : -1;
-  const bool wave_live = qw < Tq;                              // wave-uniform: the wave holds a real row
-  const int wave_lo = qw + 31 < Tq ? len - Tq + qw : -1;       // the wave's lowest limit
-  const int wave_hi = len - Tq + min(qw + 31, Tq - 1);         // and its highest
+  // GQ: the limit is no affine function of the row, and Fp8Rows at D = 128 has no VGPR to keep both through
+  // the key loop: the masked tiles (few: those that reach past the wave's lowest limit) compute it again
+  const int lim = qrow < Tq ? len - T + (qrow >> lg) : -1;
+  const bool wave_live = qw < Tq;                                   // wave-uniform: the wave holds a real row
+  const int wave_lo = qw + 31 < Tq ? len - T + (qw >> lg) : -1;     // the wave's lowest limit
+  const int wave_hi = len - T + (min(qw + 31, Tq - 1) >> lg);       // and its highest
 
   bf16x8 qf[KS];
 #pragma unroll
   for (int kk = 0; kk < KS; ++kk) {
     u32x4 x = {0u, 0u, 0u, 0u};
-    if (qrow < Tq) x = gload16(a.q + b * a.qb + qrow * a.qt + h * a.qh + kk * 16 + 8 * hh);
+    if (qrow < Tq) x = gload16(a.q + b * a.qb + (qrow >> lg) * a.qt + (h0 + (qrow & gmask)) * a.qh + kk * 16 + 8 * hh);
     qf[kk] = __builtin_bit_cast(bf16x8, x);
   }
 
@@ -247,12 +270,18 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
         for (int t = 0; t < 2; ++t) sacc[t] *= c;
       }
       if (key0 + FK - 1 > wave_lo) {  // the tile reaches past some row's limit
+        int mlim = lim;
+        if constexpr (GQ) {
+          int qr = qrow;
+          asm volatile("" : "+v"(qr));  // not hoisted out of the key loop
+          mlim = qr < Tq ? len - T + (qr >> lg) : -1;
+        }
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int key = key0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            sacc[t][e] = key > lim ? -INFINITY : sacc[t][e];
+            sacc[t][e] = key > mlim ? -INFINITY : sacc[t][e];
           }
       }
       float mx = -INFINITY;
@@ -336,6 +365,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
     for (int n = 0; n < ND; ++n) oacc[n] *= adj;
   }
   if (qrow >= Tq) return;
+  const int qtok = qrow >> lg, qhead = h0 + (qrow & gmask);  // where the row lives in o and lse
   const long long row = bh * Tq + qrow;
   if (nsplit > 1) {  // m = -inf, l = 0, o = 0 for a row with no key in this split
     float* po = ws_o + (row * nsplit + split) * D;
@@ -351,7 +381,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   } else {
     const bool any = lt > 0.f;  // a row before the sequence's start (lens[b] < Tq) sees no key
     const float inv = any ? 1.f / lt : 0.f;
-    __bf16* ob = a.o + b * a.ob + qrow * a.ot + h * a.oh;
+    __bf16* ob = a.o + b * a.ob + qtok * a.ot + qhead * a.oh;
 #pragma unroll
     for (int n = 0; n < ND; ++n)
 #pragma unroll
@@ -360,7 +390,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
                           pack2(oacc[n][4 * g + 2] * inv, oacc[n][4 * g + 3] * inv)};
         *reinterpret_cast<u32x2*>(ob + 32 * n + 8 * g + 4 * hh) = v2;
       }
-    if (hh == 0 && a.lse) a.lse[((long long)b * Tq + qrow) * a.H + h] = any ? (m + log2f(lt)) * kLn2 : -INFINITY;
+    if (hh == 0 && a.lse) a.lse[((long long)b * T + qtok) * Hq + qhead] = any ? (m + log2f(lt)) * kLn2 : -INFINITY;
   }
 }
 
@@ -379,13 +409,24 @@ bool chunk_shape_ok(int B, int H, int D, int Tq, int t_bound) {
          t_bound >= 1;
 }
 
+// the grouped forms: Hkv K / V heads, G in {1, 2, 4, 8, 16} query heads on each, T tokens, T * G <= 65535 rows
+bool chunk_gqa_ok(int B, int Hkv, int G, int D, int T, int t_bound) {
+  const int lg = kfkv::group_log2(G);
+  return lg >= 0 && T >= 1 && T <= (kMaxRows >> lg) && chunk_shape_ok(B, Hkv, D, T << lg, t_bound);
+}
+
 // The launcher behind kfamd_attn_chunk_bf16 / _fp8. st: q (b, t, h), k (b, h, t), v (b, h, t), o (b, t, h),
 // then for a scaled format k_scale (b, h), v_scale (b, h). Every KFAMD_EINVAL condition is tested before
-// any KFAMD_EALIGN one.
+// any KFAMD_EALIGN one. The grouped entry points pass G > 0: H is then Hkv, Tq the token count T, the q / o
+// strides' h runs over the Hkv * G query heads and the kernel tiles the T * G rows of a K / V head (the split
+// count and the workspace follow from Hkv and T * G); G = 1 there launches what the plain entry points launch.
 template <class Fmt>
 int attn_chunk(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens,
                void* o, float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
-               const long long* st, void* stream) {
+               const long long* st, void* stream, int G = 0) {
+  if (G > 0 && !chunk_gqa_ok(B, H, G, D, Tq, t_bound)) return KFAMD_EINVAL;
+  const int lg = G > 0 ? kfkv::group_log2(G) : 0;
+  Tq <<= lg;  // rows per (b, K / V head) from here on
   if (!q || !k || !v || !lens || !o || !st || !chunk_shape_ok(B, H, D, Tq, t_bound)) return KFAMD_EINVAL;
   if (Fmt::kScaled && (!ks || !vs)) return KFAMD_EINVAL;
   ChunkArgs a = {};
@@ -409,17 +450,19 @@ int attn_chunk(const void* q, const void* k, const void* v, const float* ks, con
   a.o = static_cast<__bf16*>(o);
   a.lse = lse;
   a.ws = static_cast<float*>(ws);
-  a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound;
+  a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound, a.lg = lg;
   const int chunks = (t_bound + kSplitKeys - 1) / kSplitKeys;
   a.split_keys = (chunks + a.nsplit - 1) / a.nsplit * kSplitKeys;
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)wgs, (unsigned)H, (unsigned)B);
-  if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128>), grid, dim3(kThreads), 0, s, a);
+  if (lg > 0 && D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true>), grid, dim3(kThreads), 0, s, a);
+  else if (lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true>), grid, dim3(kThreads), 0, s, a);
+  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false>), grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false>), grid, dim3(kThreads), 0, s, a);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && a.nsplit > 1)
-    e = kfkv::launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s);
+    e = kfkv::launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s, lg);
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
 
@@ -450,4 +493,30 @@ extern "C" int kfamd_attn_chunk_fp8(const void* q, const void* k_codes, const vo
                                     int D, int Tq, int t_bound, float scale, const long long* st, void* stream) {
   return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, H, D, Tq, t_bound,
                                    scale, st, stream);
+}
+
+// The grouped-query forms (contract: kfamd_kernels.h).
+extern "C" int kfamd_attn_chunk_gqa_nsplit(int B, int Hkv, int G, int T, int t_bound) {
+  return chunk_gqa_ok(B, Hkv, G, 64, T, t_bound) ? chunk_nsplit(B, Hkv, T * G, t_bound) : 0;
+}
+
+extern "C" long long kfamd_attn_chunk_gqa_workspace(int B, int Hkv, int G, int D, int T, int t_bound) {
+  return chunk_gqa_ok(B, Hkv, G, D, T, t_bound) ? kfamd_attn_chunk_workspace(B, Hkv, D, T * G, t_bound) : 0;
+}
+
+extern "C" int kfamd_attn_chunk_gqa_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                         void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T,
+                                         int t_bound, float scale, const long long* st, void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, t_bound,
+                                    scale, st, stream, G);
+}
+
+extern "C" int kfamd_attn_chunk_gqa_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                        const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                        int Hkv, int G, int D, int T, int t_bound, float scale, const long long* st,
+                                        void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound,
+                                   scale, st, stream, G);
 }

@@ -76,10 +76,16 @@ struct Fp8Rows {
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
+// Grouped-query attention: G query heads share one K / V head (query head h reads K / V head h / G). The
+// kernels take G in {1, 2, 4, 8, 16} as its log2; -1 for every other value.
+inline int group_log2(int G) { return G == 1 ? 0 : G == 2 ? 1 : G == 4 ? 2 : G == 8 ? 3 : G == 16 ? 4 : -1; }
+
 // attn_kv_combine<D> (attn_kv.hip) on stream s: the splits' (m, l, o[D]) fp32 records, workspace layout
 // [B][H][Tq][nsplit][2] then [B][H][Tq][nsplit][D], merged into bf16 rows o (strides ob, ot, oh) and the
-// optional lse [B][Tq][H]. D: 64 or 128; Tq <= 65535 (it is gridDim.z).
+// optional lse [B][Tq][H]. D: 64 or 128; Tq <= 65535 (it is gridDim.z). lg > 0: the grouped form
+// (attn_kv_combine_gqa<D>): H is Hkv, Tq the T * G flattened rows r = t * G + g with G = 1 << lg, o's h stride
+// runs over the Hkv * G query heads and lse is [B][T][Hkv * G].
 hipError_t launch_kv_combine(int D, const float* ws, __bf16* o, float* lse, int B, int H, int Tq, int nsplit,
-                             long long ob, long long ot, long long oh, hipStream_t s);
+                             long long ob, long long ot, long long oh, hipStream_t s, int lg = 0);
 
 }  // namespace kfkv

@@ -294,6 +294,47 @@ int kfamd_attn_chunk_fp8(const void* q, const void* k_codes, const void* v_codes
                          const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
                          int Tq, int t_bound, float scale, const long long* strides, void* stream);
 
+// ---- grouped-query attention over the KV cache (attn_kv.hip, attn_kv_mfma.hip) -----------------
+// Hkv K / V heads, G = Hq / Hkv query heads on each: query head h reads K / V head h / G (the Llama
+// convention). G in {1, 2, 4, 8, 16}; G = 1 launches exactly what the entry points above launch.
+//   q, o [B][T][Hq][D] and lse [B][T][Hq] as above, their h strides running over the Hq = Hkv * G query heads;
+//   the caches [B][Hkv][Tcap][D] and the FP8 scales [B][Hkv][Tcap]; the stride arrays of the extend / chunk
+//   entry points above. A step of T tokens is T * G rows per (b, K / V head), flattened token-major
+//   (r = t * G + g): row r is token r / G of query head hkv * G + r % G and attends keys
+//   0 .. lens[b] - T + r / G. lens, t_bound, the negative-limit rule (zeros, lse = -inf) and the rule that
+//   nothing at or beyond lens[b] is used are unchanged.
+//   kfamd_attn_extend_gqa_*: T * G <= 16 rows (K / V streamed once per 8 rows); single-token decode is T = 1
+//     with t strides of 0. Workspace: kfamd_attn_extend_gqa_workspace = decode's for Hkv heads times T * G.
+//   kfamd_attn_chunk_gqa_*: T * G <= 65535 rows on the MFMA tiles of 128 rows; the split count is
+//     kfamd_attn_chunk_nsplit's rule with tiles = ceil(T * G / 128) and H := Hkv, the workspace
+//     B * Hkv * (T * G) * nsplit * (D + 2) * 4 bytes (16 with one split).
+//   kfamd_kv_append_gqa_*: the fused QKV activation is [B][T][(Hq + 2 Hkv) D], q: Hq D | k: Hkv D | v: Hkv D
+//     (element strides qb, qt); the Hkv K and V heads go to the caches as in kfamd_kv_append_bf16 / _fp8.
+// Return codes as above; KFAMD_EINVAL (before any KFAMD_EALIGN) also for G outside {1, 2, 4, 8, 16} (Hq no
+// such multiple of Hkv), T * G > 16 in the extend form and T * G > 65535 in the chunk form. The workspace
+// and nsplit queries return 0 for a rejected shape.
+long long kfamd_attn_extend_gqa_workspace(int B, int Hkv, int G, int D, int T, int t_bound);
+int kfamd_attn_extend_gqa_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                               float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound, float scale,
+                               const long long* strides, void* stream);
+int kfamd_attn_extend_gqa_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                              const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                              int G, int D, int T, int t_bound, float scale, const long long* strides, void* stream);
+int kfamd_attn_chunk_gqa_nsplit(int B, int Hkv, int G, int T, int t_bound);
+long long kfamd_attn_chunk_gqa_workspace(int B, int Hkv, int G, int D, int T, int t_bound);
+int kfamd_attn_chunk_gqa_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                              float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound, float scale,
+                              const long long* strides, void* stream);
+int kfamd_attn_chunk_gqa_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                             const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                             int G, int D, int T, int t_bound, float scale, const long long* strides, void* stream);
+int kfamd_kv_append_gqa_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int Hq,
+                             int Hkv, int D, int Tcap, long long qb, long long qt, const long long* cache_strides,
+                             void* stream);
+int kfamd_kv_append_gqa_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                            const int* pos, int B, int T, int Hq, int Hkv, int D, int Tcap, long long qb, long long qt,
+                            const long long* cache_strides, void* stream);
+
 // Weight-streaming NT GEMM for 1 <= M <= 16 (gemm_skinny_bf16.hip): C[M][N] = act(alpha * A[M][K] .
 // W[N][K]^T + bias[N]) (+ R[M][N]); K % 8 == 0, A / W rows 16-B aligned, any N, epilogue semantics of
 // kfamd_gemm_nt_bf16. KFAMD_EINVAL: M outside 1..16 (or K % 8); KFAMD_EALIGN: alignment.

@@ -41,12 +41,13 @@ HIP_FLAGS = [
 ]
 
 
-def _run(cmd: list[str], cwd: Path | None = None) -> None:
+def _run(cmd: list[str], cwd: Path | None = None) -> str:
     proc = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True)
     if proc.returncode != 0:
         raise RuntimeError(
             f"command failed ({proc.returncode}): {' '.join(cmd)}\n{proc.stdout}\n{proc.stderr}"
         )
+    return proc.stderr
 
 
 def _newer(target: Path, sources: list[Path]) -> bool:
@@ -77,6 +78,23 @@ def build_diag_kernels() -> Path:
 # D = 64 backward level (profiles/r5n_attn_ab, tools/attn_ab.py)
 TU_FLAGS = {"attention_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
+# translation units whose kernels must not spill: several KV-cache attention instantiations sit at the VGPR
+# budget (attn_chunk_split<Fp8Rows, 128, true>: 255 of 256), and a spill there costs time without failing any
+# test. The compiler's resource remarks are read at build time; a kernel with scratch fails the build.
+NO_SCRATCH_TUS = ("attn_kv.hip", "attn_kv_mfma.hip")
+
+
+def check_no_scratch(src: Path, remarks: str) -> None:
+    import re
+    sizes = [int(n) for n in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", remarks)]
+    if not sizes:
+        raise RuntimeError(f"{src.name}: no kernel-resource-usage remarks from the compiler (scratch not checked)")
+    if any(sizes):
+        names = re.findall(r"Function Name: (\S+)", remarks)
+        bad = [n for n, b in zip(names, sizes) if b] if len(names) == len(sizes) else []
+        raise RuntimeError(f"{src.name}: kernels with scratch (register spills), bytes/lane {sorted(set(sizes) - {0})}: "
+                           f"{bad[:4]}")
+
 
 def build_kernels(force: bool = False, jobs: int = 8) -> Path:
     """Compile kernels/*.hip and kernels/tu/*.hip (one template variant per translation unit, so the
@@ -100,7 +118,15 @@ def build_kernels(force: bool = False, jobs: int = 8) -> Path:
         if force or not _newer(obj, deps) or (info and hash_changed):
             extra = [f'-DKFAMD_SRC_HASH="{src_hash}"'] if info else []
             extra += TU_FLAGS.get(src.name, [])
-            _run([HIPCC, *HIP_FLAGS, *extra, "-I", str(KERNEL_DIR), "-c", str(src), "-o", str(obj)])
+            no_scratch = src.name in NO_SCRATCH_TUS
+            extra += ["-Rpass-analysis=kernel-resource-usage"] if no_scratch else []
+            remarks = _run([HIPCC, *HIP_FLAGS, *extra, "-I", str(KERNEL_DIR), "-c", str(src), "-o", str(obj)])
+            if no_scratch:
+                try:
+                    check_no_scratch(src, remarks)
+                except RuntimeError:
+                    obj.unlink(missing_ok=True)  # not linked, and compiled (and checked) again next time
+                    raise
             check_object_kernels(src, obj)
         return obj
 

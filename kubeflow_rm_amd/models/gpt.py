@@ -20,6 +20,14 @@ attention — and can replay the step as one hipGraph (no tensor-parallel group;
 ``generate(sampler="fused")`` samples on ``ops.sample`` (top-k, top-p, a stop token; seeded uniforms, so the
 result does not depend on the device) and with ``graph=True`` replays step + sampler + token feedback as
 one hipGraph per token.
+
+Grouped-query attention: ``GPTConfig(n_kv_heads=Hkv)`` with ``Hkv`` dividing ``n_heads`` gives every group of
+``G = n_heads // Hkv`` query heads one K / V head (query head h reads K / V head ``h // G``); the fused QKV
+projection then has ``(n_heads + 2 * Hkv) * head_dim`` features, ``q | k | v``. The KV cache holds the ``Hkv``
+heads (1 / G of the bytes) and the decode / extend / chunk kernels stream K / V once per group. Training and
+``prefill`` run the flash kernel on K / V expanded to ``n_heads`` heads (a materialised copy; autograd sums dK / dV
+over the group); a GQA-native flash forward / backward, tensor-parallel K / V head sharding, group sizes outside
+{1, 2, 4, 8, 16} on a GPU, and RoPE and the other Llama-architecture pieces are not built.
 """
 from __future__ import annotations
 
@@ -43,10 +51,19 @@ class GPTConfig:
     max_seq: int = 2048
     dropout: float = 0.0
     dtype: torch.dtype = torch.bfloat16
+    n_kv_heads: int | None = None  # K / V heads (grouped-query attention); None: n_heads
+
+    def __post_init__(self):
+        if self.n_kv_heads is not None and (self.n_kv_heads < 1 or self.n_heads % self.n_kv_heads):
+            raise ValueError(f"n_kv_heads={self.n_kv_heads} must divide n_heads={self.n_heads}")
 
     @property
     def head_dim(self) -> int:
         return self.d_model // self.n_heads
+
+    @property
+    def kv_heads(self) -> int:
+        return self.n_heads if self.n_kv_heads is None else self.n_kv_heads
 
 
 CONFIGS = {
@@ -108,12 +125,20 @@ class Block(torch.nn.Module):
         tp = tpl._world(tp_group)
         if cfg.n_heads % tp:
             raise ValueError(f"n_heads={cfg.n_heads} not divisible by tp={tp}")
+        if tp > 1 and cfg.kv_heads != cfg.n_heads:
+            raise NotImplementedError("grouped-query attention (n_kv_heads < n_heads) with a tensor-parallel group of "
+                                      "more than one rank: sharding the K / V heads is not built")
         self.cfg, self.tp_group = cfg, tp_group
         self.local_heads = cfg.n_heads // tp
+        # K / V heads of this rank; fewer than local_heads: grouped-query attention (single rank only)
+        self.local_kv_heads = self.local_heads if cfg.kv_heads == cfg.n_heads else cfg.kv_heads
         seed = 1000 * (layer + 1)
         self.ln1 = LayerNorm(cfg.d_model, cfg.dtype, device)
-        # fused QKV, column-parallel: each rank owns local_heads of q, k and v
-        self.qkv = tpl.ColumnParallelLinear(cfg.d_model, 3 * cfg.d_model, group=tp_group, dtype=cfg.dtype, device=device,
+        # fused QKV, column-parallel: each rank owns local_heads of q, k and v. Grouped-query attention: q | k | v
+        # with kv_heads heads of k and of v ((n_heads + 2 kv_heads) * head_dim features; 3 * d_model without it)
+        qkv_out = (3 * cfg.d_model if cfg.kv_heads == cfg.n_heads  # seeded as a (3 d_model, d_model) matrix, as ever
+                   else (cfg.n_heads + 2 * cfg.kv_heads) * cfg.head_dim)
+        self.qkv = tpl.ColumnParallelLinear(cfg.d_model, qkv_out, group=tp_group, dtype=cfg.dtype, device=device,
                                             seed=seed + 1)
         if tp > 1:
             # the canonical full QKV weight is [q_all; k_all; v_all]; this rank's column shard must
@@ -126,9 +151,31 @@ class Block(torch.nn.Module):
                                             device=device, seed=seed + 3)
         self.fc2 = tpl.RowParallelLinear(cfg.d_ff, cfg.d_model, group=tp_group, dtype=cfg.dtype, device=device, seed=seed + 4)
 
+    def _attention_gqa(self, x, residual):
+        """Grouped-query attention of the training forward. The fused ``ops.attn_block`` node (and
+        ``ops.attention_qkv``) assume a ``[3 h hd]`` activation and are bypassed: q and the K / V heads, each
+        repeated over its group (a materialised copy), go through ``ops.flash_attention`` on the native flash
+        kernel, and autograd's backward of the expansion sums dK / dV over the group."""
+        B, T, _ = x.shape
+        h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
+        G = h // hkv
+        qkv = self.qkv(x)
+        q = qkv[..., :h * hd].view(B, T, h, hd)
+        k, v = qkv[..., h * hd:].view(B, T, 2, hkv, hd).unbind(2)
+        k = k.unsqueeze(3).expand(B, T, hkv, G, hd).reshape(B, T, h, hd)
+        v = v.unsqueeze(3).expand(B, T, hkv, G, hd).reshape(B, T, h, hd)
+        q, k, v = (t.transpose(1, 2) for t in (q, k, v))  # [B, h, T, hd] views
+        if ops.native_enabled() and ops.attention_supported(qkv, hd):
+            y = ops.flash_attention(q, k, v, causal=True)
+        else:
+            y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
+
     def attention(self, x, residual=None):
         B, T, _ = x.shape
         h, hd = self.local_heads, self.cfg.head_dim
+        if self.local_kv_heads != h:
+            return self._attention_gqa(x, residual)
         # the fused single-rank path whenever the TP layers would issue no collective; a forced-distributed
         # run at world size 1 (KFAMD_FORCE_DIST) takes the TP layers and their RCCL all-reduces (ADVICE r5)
         if x.is_cuda and ops.native_enabled() and ops.attention_supported(x, hd) and not tpl._collective(self.tp_group):
@@ -280,7 +327,7 @@ class GPT(torch.nn.Module):
         c = self.cfg
         if capacity > c.max_seq:
             raise ValueError(f"cache capacity {capacity} exceeds max_seq {c.max_seq}")
-        return ops.KVCache(c.n_layers, B, self.blocks[0].local_heads, c.head_dim, capacity,
+        return ops.KVCache(c.n_layers, B, self.blocks[0].local_kv_heads, c.head_dim, capacity,
                            device=device if device is not None else self.tok.device,
                            dtype=kv_dtype if kv_dtype is not None else c.dtype)
 
@@ -315,21 +362,25 @@ class GPT(torch.nn.Module):
         c = self.cfg
         x = F.embedding(idx, self.tok) + self.pos[:T]
         for li, blk in enumerate(self.blocks):
-            h, hd = blk.local_heads, c.head_dim
+            h, hkv, hd = blk.local_heads, blk.local_kv_heads, c.head_dim
             if native:
                 x2 = x.reshape(B * T, c.d_model)
                 y = ops.layer_norm_fwd(x2, blk.ln1.weight, blk.ln1.bias)[0]
-                qkv = ops.gemm_nt(y, blk.qkv.weight, bias=blk.qkv.bias).view(B, T, 3 * h * hd)
-                ops.kv_append(qkv, cache, li)
-                a = ops.attention_qkv(qkv, h, hd, causal=True).view(B * T, h * hd)
+                qkv = ops.gemm_nt(y, blk.qkv.weight, bias=blk.qkv.bias).view(B, T, (h + 2 * hkv) * hd)
+                ops.kv_append(qkv, cache, li, q_heads=h)
+                if hkv == h:
+                    a = ops.attention_qkv(qkv, h, hd, causal=True).view(B * T, h * hd)
+                else:  # the flash kernel on K / V expanded to h heads (a copy)
+                    q, k, v = self._split_gqa(qkv, h, hkv, hd)
+                    a = ops.flash_attention(q, k, v, causal=True).transpose(1, 2).reshape(B * T, h * hd)
                 x2 = ops.gemm_nt(a, blk.proj.weight, bias=blk.proj.bias, residual=x2)
                 y = ops.layer_norm_fwd(x2, blk.ln2.weight, blk.ln2.bias)[0]
                 y = ops.gemm_nt(y, blk.fc1.weight, bias=blk.fc1.bias, act=blk.fc1.act)
                 x = ops.gemm_nt(y, blk.fc2.weight, bias=blk.fc2.bias, residual=x2).view(B, T, c.d_model)
             else:
                 qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
-                ops.kv_append(qkv, cache, li)
-                q, k, v = qkv.view(B, T, 3, h, hd).permute(2, 0, 3, 1, 4)
+                ops.kv_append(qkv, cache, li, q_heads=h)
+                q, k, v = self._split_gqa(qkv, h, hkv, hd)
                 a = F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
                 x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
                 y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
@@ -340,6 +391,17 @@ class GPT(torch.nn.Module):
             last = ops.layer_norm_fwd(last.contiguous(), self.ln_f.weight, self.ln_f.bias)[0]
             return ops.gemm_nt(last, self.tok)  # M = B rows: auto routes it as the parent commit did
         return F.linear(self.ln_f(last), self.tok)
+
+    @staticmethod
+    def _split_gqa(qkv, h: int, hkv: int, hd: int):
+        """q, k, v ``[B, h, T, hd]`` of a fused activation ``[B, T, (h + 2 hkv) hd]``: views when hkv == h, else
+        K / V with every head repeated over its group (materialised)."""
+        B, T = qkv.shape[:2]
+        q = qkv[..., :h * hd].view(B, T, h, hd).transpose(1, 2)
+        k, v = qkv[..., h * hd:].view(B, T, 2, hkv, hd).unbind(2)
+        if hkv != h:
+            k, v = (t.repeat_interleave(h // hkv, dim=2) for t in (k, v))
+        return q, k.transpose(1, 2), v.transpose(1, 2)
 
     def _skinny(self, x, w, bias=None, act="none", residual=None):
         # decode linears: the weight-streaming kernel wherever it beat the "auto" route in
@@ -412,18 +474,18 @@ class GPT(torch.nn.Module):
             h, hd = blk.local_heads, c.head_dim
             if native:
                 y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
-                qkv = self._skinny(y, wsel(li, "qkv"), blk.qkv.bias)  # [B, 3 * h * hd]
-                ops.kv_append(qkv.view(B, 1, 3 * h * hd), cache, li)
+                qkv = self._skinny(y, wsel(li, "qkv"), blk.qkv.bias)  # [B, (h + 2 * hkv) * hd]
+                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h)
                 a = torch.empty(B, h * hd, device=x.device, dtype=x.dtype)
-                ops.attention_decode(qkv.view(B, 3, h, hd)[:, 0], cache, li, out=a.view(B, h, hd), **att)
+                ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, out=a.view(B, h, hd), **att)
                 x = self._skinny(a, wsel(li, "proj"), blk.proj.bias, residual=x)
                 y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
                 y = self._skinny(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
                 x = self._skinny(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
-                ops.kv_append(qkv.view(B, 1, -1), cache, li)  # torch ops: CPU tensors / torch_reference()
-                a = ops.attention_decode(qkv.view(B, 3, h, hd)[:, 0], cache, li, **att).reshape(B, h * hd)
+                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h)  # torch ops: CPU tensors / torch_reference()
+                a = ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, **att).reshape(B, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
                 y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
                 x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
@@ -441,6 +503,8 @@ class GPT(torch.nn.Module):
         ``ops.attention_extend`` (K / V read once per 8 new rows; the weight-streaming GEMM while
         B * T <= 16); longer inputs run in chunks of 16. Like ``decode_step`` it reads the position
         from the device-side ``cache.lens`` only, so a fixed T <= 16 can be captured into a hipGraph.
+        A grouped-query model (``n_kv_heads < n_heads``, G query heads per K / V head) steps ``16 // G`` tokens
+        at a time on this path: ``ops.attention_extend`` takes 16 rows per K / V head, and a token is G of them.
 
         ``weights`` (``decode_weights()``): a chunk whose linears take the weight-streaming route, B * T <= 16
         rows, reads the 8-bit weights; the LM head does by its own row count (B with ``last_only``). Chunks
@@ -462,6 +526,8 @@ class GPT(torch.nn.Module):
         self._check_cache(cache, B, T)
         native = self._native_decode(self.tok)
         R = ops.decode.MAX_EXTEND_ROWS
+        if chunk is None and native:  # the kernel takes 16 ROWS per K / V head: 16 // G tokens of a grouped-query model
+            R = max(R // (self.blocks[0].local_heads // self.blocks[0].local_kv_heads), 1)  # G > 16: the op raises
         if chunk is not None:
             if isinstance(chunk, bool) or not isinstance(chunk, int) or not R < chunk <= cache.capacity:
                 raise ValueError(f"extend(chunk=...): an int in {R + 1} .. the cache's capacity ({cache.capacity}) "
@@ -496,18 +562,18 @@ class GPT(torch.nn.Module):
             h, hd = blk.local_heads, c.head_dim
             if native:
                 y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
-                qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, 3 * h * hd)
-                ops.kv_append(qkv, cache, li)
+                qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, -1)
+                ops.kv_append(qkv, cache, li, q_heads=h)
                 a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
-                attend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, out=a.view(B, T, h, hd), **att)
+                attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, out=a.view(B, T, h, hd), **att)
                 x = lin(a.view(B * T, h * hd), wsel(li, "proj"), blk.proj.bias, residual=x)
                 y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
                 y = lin(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
                 x = lin(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
-                ops.kv_append(qkv, cache, li)  # torch ops: CPU tensors / torch_reference()
-                a = attend(qkv.view(B, T, 3, h, hd)[:, :, 0], cache, li, **att).reshape(B, T, h * hd)
+                ops.kv_append(qkv, cache, li, q_heads=h)  # torch ops: CPU tensors / torch_reference()
+                a = attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, **att).reshape(B, T, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
                 y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
                 x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
@@ -745,7 +811,9 @@ class GPT(torch.nn.Module):
     def flops_per_token(self, seq: int) -> float:
         """Training FLOPs/token (fwd+bwd = 3x fwd): dense matmuls + attention scores."""
         c = self.cfg
-        dense = 2 * (4 * c.d_model * c.d_model + 2 * c.d_model * c.d_ff) * c.n_layers + 2 * c.d_model * c.vocab_size
+        kv = 2 * c.kv_heads * c.head_dim  # the K and V projections' features (2 * d_model without grouping)
+        dense = (2 * ((2 * c.d_model + kv) * c.d_model + 2 * c.d_model * c.d_ff) * c.n_layers
+                 + 2 * c.d_model * c.vocab_size)
         attn = 2 * 2 * seq * c.d_model * c.n_layers
         return 3.0 * (dense + attn)
 

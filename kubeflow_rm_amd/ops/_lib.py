@@ -109,6 +109,21 @@ _SIGNATURES = {
                                       c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_attn_chunk_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                      c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_gqa_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_extend_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_gqa_nsplit": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_chunk_gqa_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_chunk_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
+                                         ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_gemm_nt_skinny_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
                                           c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_bf16_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,

@@ -33,6 +33,19 @@ attention kernels multiply the scales in (``(q . codes_k[j]) * k_scale[j]``, ``p
 write a dequantised tensor. The three functions dispatch on the cache's dtype; everything else about the
 cache (``lens``, ``t_bound``, ``advance``, ``rewind``, the workspaces) is the same. ``KVCache.nbytes`` is
 what a cache holds in device memory.
+
+Grouped-query attention: the cache's ``H`` counts K / V heads; ``attention_decode`` / ``attention_extend`` /
+``attention_chunk`` take a ``q`` of ``Hq = G * cache.H`` heads and infer G from the shapes: query head ``h`` reads
+K / V head ``h // G`` (the Llama convention). ``kv_append(qkv, cache, layer, q_heads=Hq)`` reads a fused activation
+``[B, T, (Hq + 2 * cache.H) * D]`` laid out ``q: Hq * D | k: H * D | v: H * D``. On a GPU G is one of ``GROUP_SIZES``
+(any other ratio raises ``ValueError``) and the kernels see ``T * G`` rows per (batch, K / V head): token-major,
+row ``t * G + g`` with the limit of token ``t``, so K / V are streamed once for the whole group. ``attention_decode``
+with G > 1 is ``attention_extend`` at T = 1; ``attention_extend`` takes ``T * G <= MAX_EXTEND_ROWS`` rows and, for
+G > 1, runs the extend kernel's row slots below ``GQA_MFMA_MIN_ROWS`` rows and ``attention_chunk``'s MFMA kernel from
+there on (faster from 8 rows: profiles/gqa; the results then agree with the VALU form within the kernels' bounds,
+not bit for bit). The CPU /
+``ops.torch_reference()`` forms take any divisor and expand K / V with ``repeat_interleave(G, dim=1)``. Not built:
+G outside ``GROUP_SIZES`` on a GPU.
 """
 from __future__ import annotations
 
@@ -48,7 +61,20 @@ HEAD_DIMS = (64, 128)
 FP8 = torch.float8_e4m3fn  # the 8-bit cache's code type (OCP e4m3fn: finite maximum 448, code 0x7E)
 FP8_MAX = 448.0
 CACHE_DTYPES = (torch.bfloat16, FP8)  # what the kernels read
-MAX_EXTEND_ROWS = 16  # query rows per attention_extend call
+MAX_EXTEND_ROWS = 16  # query ROWS per attention_extend call and (batch, K / V head): T * G of them, T tokens at G = 1
+GROUP_SIZES = (1, 2, 4, 8, 16)  # query heads per K / V head the kernels take
+# attention_decode / attention_extend with G > 1 query heads per K / V head: from this many rows (T * G) per K / V
+# head on they run the MFMA form (attention_chunk's kernel) instead of the VALU form; None: never. G = 1 never
+# moves. Measured (profiles/gqa; tools/decode_bench.py --steps gqa; D = 128, 8 x 16 query heads, 2048 / 4096 keys,
+# bf16 and FP8): at 8 rows the MFMA form is 1.5 - 2.0x faster, at 16 rows 2.5 - 3.7x, every case beyond the
+# blocks' spread; below 8 rows the forms were not compared and the VALU form stays.
+GQA_MFMA_MIN_ROWS: int | None = 8
+
+
+def _gqa_mfma(T: int, G: int) -> bool:
+    return G > 1 and GQA_MFMA_MIN_ROWS is not None and T * G >= GQA_MFMA_MIN_ROWS
+
+
 _split_keys: int | None = None
 
 
@@ -80,6 +106,22 @@ def _ll(*vals) -> "ctypes.Array":
     return (ctypes.c_longlong * len(vals))(*(int(v) for v in vals))
 
 
+def _group(what: str, q_heads: int, cache: "KVCache", native: bool) -> int:
+    """G = q_heads / cache.H of a call; on the kernels' path one of GROUP_SIZES."""
+    G, rem = divmod(int(q_heads), cache.H)
+    if rem or G < 1:
+        raise ValueError(f"{what}: the query head count must be a multiple of the cache's {cache.H} K / V heads, "
+                         f"got {q_heads}")
+    if native and G not in GROUP_SIZES:
+        raise ValueError(f"{what}: {G} query heads per K / V head; one of {GROUP_SIZES} expected on a GPU")
+    return G
+
+
+def _expand_kv(k, v, G: int):
+    """K, V ``[B, Hkv, ...]`` with every head repeated G times: what the torch reference attends."""
+    return (k, v) if G == 1 else (k.repeat_interleave(G, dim=1), v.repeat_interleave(G, dim=1))
+
+
 def _entry(name: str, cache: "KVCache", layer: int):
     """The entry point ``name`` for the cache's dtype: (function, the scale tensors an FP8 cache adds to the
     pointers and strides, the tag of its error messages)."""
@@ -105,7 +147,9 @@ def dequantize_rows(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 
 class KVCache:
-    """Per-layer K / V ``[B, H, capacity, D]``, device ``lens`` (int32 [B]), host ``t_bound``.
+    """Per-layer K / V ``[B, H, capacity, D]``, device ``lens`` (int32 [B]), host ``t_bound``. ``H`` is the
+    number of K / V heads: a grouped-query model's cache holds ``n_kv_heads`` and the attention functions take a
+    ``q`` of ``G * H`` heads.
     ``dtype=torch.float8_e4m3fn``: ``k`` / ``v`` hold codes and ``k_scale`` / ``v_scale`` ``[B, H, capacity]``
     fp32 the per-row scales (``None`` for every other dtype)."""
 
@@ -188,8 +232,8 @@ class KVCache:
         self._bound = 0
 
     def _extend_ws(self) -> torch.Tensor:
-        """attention_extend's split workspace: MAX_EXTEND_ROWS times decode's, allocated on first use
-        (outside any capture) and kept."""
+        """attention_extend's split workspace: MAX_EXTEND_ROWS times decode's (rows of a K / V head, whatever
+        the group size), allocated on first use (outside any capture) and kept."""
         if self.extend_workspace is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("attention_extend: run one step before capturing (the workspace is allocated "
@@ -198,11 +242,14 @@ class KVCache:
             self.extend_workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
         return self.extend_workspace
 
-    def _chunk_ws(self, T: int) -> torch.Tensor:
-        """attention_chunk's split workspace for T query rows: ``kfamd_attn_chunk_workspace`` at the capacity
-        (the split count does not fall when t_bound grows, so it serves every t_bound), allocated on first
-        use and replaced by a larger one when a later T needs more, never inside a capture."""
-        nbytes = int(_lib.lib().kfamd_attn_chunk_workspace(self.B, self.H, self.D, T, self.capacity))
+    def _chunk_ws(self, T: int, G: int = 1) -> torch.Tensor:
+        """attention_chunk's split workspace for T tokens of G query heads per K / V head:
+        ``kfamd_attn_chunk_gqa_workspace`` at the capacity (the split count does not fall when t_bound grows, so
+        it serves every t_bound), allocated on first use and replaced by a larger one when a later call needs
+        more, never inside a capture."""
+        L = _lib.lib()
+        nbytes = int(L.kfamd_attn_chunk_workspace(self.B, self.H, self.D, T, self.capacity) if G == 1 else
+                     L.kfamd_attn_chunk_gqa_workspace(self.B, self.H, G, self.D, T, self.capacity))
         if self.chunk_workspace is None or self.chunk_workspace.numel() < nbytes:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError(f"attention_chunk: run one step of T = {T} rows before capturing (the workspace "
@@ -211,19 +258,23 @@ class KVCache:
         return self.chunk_workspace
 
 
-def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
+def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None = None) -> None:
     """K, V rows of the fused QKV activation ``[B, T, 3*H*D]`` -> cache rows ``lens[b] .. lens[b]+T-1``
-    (rows at or beyond the capacity are dropped). ``lens`` is not advanced."""
+    (rows at or beyond the capacity are dropped). ``lens`` is not advanced. ``q_heads=Hq`` (default: the
+    cache's H): a grouped-query layer's activation ``[B, T, (Hq + 2*H)*D]``, ``q: Hq*D | k: H*D | v: H*D``."""
     B, H, D = cache.B, cache.H, cache.D
-    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != 3 * H * D:
-        raise ValueError(f"kv_append: qkv [B={B}, T, {3 * H * D}] expected, got {tuple(qkv.shape)}")
+    Hq = H if q_heads is None else int(q_heads)
+    G = _group("kv_append", Hq, cache, _native(qkv))
+    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != (Hq + 2 * H) * D:
+        raise ValueError(f"kv_append: qkv [B={B}, T, {(Hq + 2 * H) * D}] expected, got {tuple(qkv.shape)}")
     T = qkv.shape[1]
     k, v = cache.k[layer], cache.v[layer]
+    if not _native(qkv):  # [B, T, 3, H, D]: slot 0 the last H query heads (unused), slots 1 and 2 k and v
+        x = qkv[:, :, (Hq - H) * D:].reshape(B, T, 3, H, D)
     if cache.fp8 and not _native(qkv):
-        _kv_append_fp8_torch(qkv.reshape(B, T, 3, H, D), cache, layer)
+        _kv_append_fp8_torch(x, cache, layer)
         return
     if not _native(qkv):
-        x = qkv.reshape(B, T, 3, H, D)
         rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=qkv.device).unsqueeze(0)  # [B, T]
         if cache._bound + T <= cache.capacity:  # no row can fall off the end: one index_put per tensor
             bidx = torch.arange(B, device=qkv.device).unsqueeze(1).expand(B, T)
@@ -239,11 +290,11 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int) -> None:
         raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
     if cache.fp8 and D not in HEAD_DIMS:
         raise ValueError(f"kv_append: head dim in {HEAD_DIMS} expected for an FP8 cache on a GPU, got {D}")
-    fn, scales, tag = _entry("kfamd_kv_append", cache, layer)
-    rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(), B, T, H,
-            D, cache.capacity, qkv.stride(0), qkv.stride(1),
+    fn, scales, tag = _entry("kfamd_kv_append" if G == 1 else "kfamd_kv_append_gqa", cache, layer)
+    rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(), B, T,
+            *((H,) if G == 1 else (Hq, H)), D, cache.capacity, qkv.stride(0), qkv.stride(1),
             _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
-    _lib.check(rc, f"kv_append[{tag}B={B} T={T} H={H} D={D}]")
+    _lib.check(rc, f"kv_append[{tag}B={B} T={T} Hq={Hq} H={H} D={D}]")
 
 
 def _kv_append_fp8_torch(x, cache: KVCache, layer: int) -> None:
@@ -286,10 +337,15 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     """softmax(scale * q k^T) v for one query row per head: q ``[B, H, D]`` (any b / h strides, e.g. a
     view of the fused QKV output), keys ``0 .. lens[b]-1`` of ``cache`` layer ``layer``. ``out``:
     optional ``[B, H, D]`` view to write (e.g. of a ``[B, 1, H*D]`` buffer). ``lens`` / ``t_bound``
-    default to the cache's."""
-    B, H, D = cache.B, cache.H, cache.D
-    if tuple(q.shape) != (B, H, D):
-        raise ValueError(f"attention_decode: q [{B}, {H}, {D}] expected, got {tuple(q.shape)}")
+    default to the cache's. Grouped-query attention: ``H = G * cache.H`` query heads, head h on K / V head
+    ``h // G``; on a GPU G > 1 runs the group's G rows as ``attention_extend`` does at T = 1: the extend kernel's
+    row slots for G < ``GQA_MFMA_MIN_ROWS``, the MFMA kernel for G = 8 and 16 (K / V streamed once per group; the
+    extend / chunk workspace, allocated on first use and never inside a capture)."""
+    B, D = cache.B, cache.D
+    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != D:
+        raise ValueError(f"attention_decode: q [{B}, G * {cache.H}, {D}] expected, got {tuple(q.shape)}")
+    H = q.shape[1]
+    G = _group("attention_decode", H, cache, _native(q))
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     lens = cache.lens if lens is None else lens
     t_bound = cache.t_bound if t_bound is None else int(t_bound)
@@ -298,6 +354,7 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         if cache.fp8:  # the visible rows, dequantised; then the reference code as it is
             k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1),
                                        q.dtype if q.is_cuda else torch.float32)
+        k, v = _expand_kv(k, v, G)
         o = _attention_decode_torch(q, k, v, lens, scale).to(q.dtype)
         if out is not None:
             out.copy_(o)
@@ -319,7 +376,20 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
         out = torch.empty(B, H, D, device=q.device, dtype=q.dtype)
     elif tuple(out.shape) != (B, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
         raise ValueError(f"attention_decode: out must be a bf16 GPU [{B}, {H}, {D}] view with a contiguous head dim")
+    if _gqa_mfma(1, G):  # the group's G rows on an MFMA tile
+        res = attention_chunk(q.unsqueeze(1), cache, layer, scale=scale, out=out.unsqueeze(1), lens=lens,
+                              t_bound=t_bound, return_lse=return_lse)
+        return (out, res[1].squeeze(1)) if return_lse else out
     lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
+    if G > 1:  # the group's G rows on the extend kernel's row slots: T = 1, no t stride
+        fn, scales, tag = _entry("kfamd_attn_extend_gqa", cache, layer)
+        rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(),
+                out.data_ptr(), lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, cache.H,
+                G, D, 1, t_bound, scale,
+                _ll(q.stride(0), 0, q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), 0, out.stride(1),
+                    *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
+        _lib.check(rc, f"attention_decode[{tag}B={B} H={H} G={G} D={D} t_bound={t_bound}]")
+        return (out, lse) if return_lse else out
     fn, scales, tag = _entry("kfamd_attn_decode", cache, layer)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
             lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
@@ -352,11 +422,14 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     layer ``layer``. ``lens[b]`` counts the keys INCLUDING the T new rows; row i attends keys
     ``0 .. lens[b] - T + i`` (a row whose limit is negative gives zeros, lse = -inf). ``out``: optional
     ``[B, T, H, D]`` view to write. ``lens`` / ``t_bound`` default to the cache's. K and V are read once
-    per 8 query rows (``kernels/attn_kv.hip``)."""
-    B, H, D = cache.B, cache.H, cache.D
-    if q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (H, D):
-        raise ValueError(f"attention_extend: q [{B}, T, {H}, {D}] expected, got {tuple(q.shape)}")
-    T = q.shape[1]
+    per 8 query rows (``kernels/attn_kv.hip``). Grouped-query attention: ``H = G * cache.H`` query heads; the
+    rows of a K / V head are then the ``T * G`` (token, head-in-group) pairs, and the GPU limit is
+    ``T * G <= MAX_EXTEND_ROWS``; with G > 1, ``GQA_MFMA_MIN_ROWS`` rows or more run ``attention_chunk``'s kernel."""
+    B, D = cache.B, cache.D
+    if q.dim() != 4 or q.shape[0] != B or q.shape[3] != D:
+        raise ValueError(f"attention_extend: q [{B}, T, G * {cache.H}, {D}] expected, got {tuple(q.shape)}")
+    T, H = q.shape[1], q.shape[2]
+    G = _group("attention_extend", H, cache, _native(q))
     if T < 1:
         raise ValueError("attention_extend: at least one query row expected")
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
@@ -366,14 +439,15 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     if not _native(q):
         if cache.fp8:
             k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), torch.float32)
-        o, lse = _attention_extend_torch(q, k, v, lens, scale)
+        o, lse = _attention_extend_torch(q, *_expand_kv(k, v, G), lens, scale)
         o = o.to(q.dtype)
         if out is not None:
             out.copy_(o)
             o = out
         return (o, lse) if return_lse else o
-    if T > MAX_EXTEND_ROWS:
-        raise ValueError(f"attention_extend: 1 <= T <= {MAX_EXTEND_ROWS} query rows expected on a GPU, got {T}")
+    if T * G > MAX_EXTEND_ROWS:
+        raise ValueError(f"attention_extend: 1 <= T * G <= {MAX_EXTEND_ROWS} query rows per K / V head expected on a "
+                         f"GPU, got T = {T}, G = {G}")
     if D not in HEAD_DIMS:
         raise ValueError(f"attention_extend: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
     if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
@@ -387,10 +461,14 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     elif tuple(out.shape) != (B, T, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
         raise ValueError(f"attention_extend: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
                          "head dim")
+    if _gqa_mfma(T, G):
+        return attention_chunk(q, cache, layer, scale=scale, out=out, lens=lens, t_bound=t_bound,
+                               return_lse=return_lse)
     lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry("kfamd_attn_extend", cache, layer)
+    fn, scales, tag = _entry("kfamd_attn_extend" if G == 1 else "kfamd_attn_extend_gqa", cache, layer)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, H, D, T, t_bound, scale,
+            lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B,
+            *((H,) if G == 1 else (cache.H, G)), D, T, t_bound, scale,
             _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
                 *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
     _lib.check(rc, f"attention_extend[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")
@@ -407,11 +485,14 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     ``return_lse`` as there. On a GPU it always runs the MFMA kernel (``kernels/attn_kv_mfma.hip``: 128-row
     query tiles, K / V read once per tile and split, P rounded to bf16 for the P.V product), whatever T is:
     for T <= 16 it agrees with ``attention_extend`` within the kernels' bounds, not bit for bit. On CPU
-    tensors and under ``ops.torch_reference()`` it is the same torch code as ``attention_extend``."""
-    B, H, D = cache.B, cache.H, cache.D
-    if q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (H, D):
-        raise ValueError(f"attention_chunk: q [{B}, T, {H}, {D}] expected, got {tuple(q.shape)}")
-    T = q.shape[1]
+    tensors and under ``ops.torch_reference()`` it is the same torch code as ``attention_extend``. Grouped-query
+    attention: ``H = G * cache.H`` query heads; the kernel tiles the ``T * G`` rows of a K / V head
+    (``T * G <= 65535``)."""
+    B, D = cache.B, cache.D
+    if q.dim() != 4 or q.shape[0] != B or q.shape[3] != D:
+        raise ValueError(f"attention_chunk: q [{B}, T, G * {cache.H}, {D}] expected, got {tuple(q.shape)}")
+    T, H = q.shape[1], q.shape[2]
+    G = _group("attention_chunk", H, cache, _native(q))
     if T < 1:
         raise ValueError("attention_chunk: at least one query row expected")
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
@@ -421,7 +502,7 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     if not _native(q):
         if cache.fp8:
             k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), torch.float32)
-        o, lse = _attention_extend_torch(q, k, v, lens, scale)
+        o, lse = _attention_extend_torch(q, *_expand_kv(k, v, G), lens, scale)
         o = o.to(q.dtype)
         if out is not None:
             out.copy_(o)
@@ -444,9 +525,12 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
         raise ValueError(f"attention_chunk: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
                          "head dim")
     lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry("kfamd_attn_chunk", cache, layer)
+    if G > 1 and T * G > 65535:
+        raise ValueError(f"attention_chunk: T * G <= 65535 query rows per K / V head expected, got T = {T}, G = {G}")
+    fn, scales, tag = _entry("kfamd_attn_chunk" if G == 1 else "kfamd_attn_chunk_gqa", cache, layer)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache._chunk_ws(T).data_ptr(), B, H, D, T, t_bound, scale,
+            lse.data_ptr() if lse is not None else None, cache._chunk_ws(T, G).data_ptr(), B,
+            *((H,) if G == 1 else (cache.H, G)), D, T, t_bound, scale,
             _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
                 *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
     _lib.check(rc, f"attention_chunk[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")

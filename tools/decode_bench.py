@@ -45,6 +45,13 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         (the flash kernel, causal) on T rows with no prior keys. Model: gpt-small and gpt-1b, B = 1, a
         512-token turn on a cache of 1536: extend(chunk=128 / 256 / 512) against extend without chunk, eager.
         Medians of 7 interleaved blocks with min and max.
+  gqa   (not in the default list) grouped-query attention. Kernel: D = 128, capacity 4096, B = 8 x 16 query
+        heads, 2048 and 4096 keys, bf16 and FP8 caches of 16 / G K / V heads (rotated past the last-level cache):
+        ops.attention_decode at G in {1, 2, 4, 8, 16} interleaved in one process (time against G = 1 and
+        against the K / V bytes), and at T * G in {8, 16} rows the VALU form (attn_extend_split) against the
+        MFMA form (ops.attention_chunk) on the same cache: what ops.decode.GQA_MFMA_MIN_ROWS is set from.
+        Model: the gpt-1b shape with n_kv_heads in {16, 4, 2} (random weights), B in {1, 16}, position about
+        2048, bf16 and FP8 caches, eager and graphed, interleaved runs: ms/token and KVCache.nbytes.
 """
 from __future__ import annotations
 
@@ -62,7 +69,9 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
-                "chunk": 900}
+                "chunk": 900, "gqa": 1000}
+GQA_GS = (1, 2, 4, 8, 16)
+GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
 CHUNK_TS = (16, 32, 64, 128, 256, 512)
 KV8_TS = (4, 8)
 EXTEND_TS = (1, 2, 4, 8, 16)
@@ -767,7 +776,131 @@ def step_sample(quick: bool):
     return result
 
 
-STEPS = {"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+def _gqa_caches(B, Hq, Hkv, D, cap, quick: bool):
+    """A bf16 and an FP8 cache of Hkv heads, full of random rows (the grouped append), with enough layers that
+    a rotation through them exceeds the 256 MiB last-level cache (at most 32)."""
+    import torch
+    from kubeflow_rm_amd import ops
+    ncopy = 1 if quick else max(2, min(32, -(-(512 << 20) // (2 * B * Hkv * cap * D * 2))))
+    caches = {"bf16": ops.KVCache(ncopy, B, Hkv, D, cap, device="cuda"),
+              "fp8": ops.KVCache(ncopy, B, Hkv, D, cap, device="cuda", dtype=torch.float8_e4m3fn)}
+    for layer in range(ncopy):
+        for c in caches.values():
+            c.reset()
+        for t0 in range(0, cap, 512):
+            qkv = torch.randn(B, min(512, cap - t0), (Hq + 2 * Hkv) * D, device="cuda").to(torch.bfloat16)
+            for c in caches.values():
+                ops.kv_append(qkv, c, layer, q_heads=Hq)
+                c.advance(qkv.shape[1])
+    return caches, ncopy
+
+
+def _gqa_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.ops import decode
+    rows = {"decode": [], "forms": []}
+    B, Hq, D, cap = 8, 16, 128, 4096
+    blocks = 5 if quick else 7
+    caches, ncopy = {}, {}
+    for G in GQA_GS:
+        caches[G], ncopy[G] = _gqa_caches(B, Hq, Hq // G, D, cap, quick)
+    q = torch.randn(B, Hq, D, device="cuda").to(torch.bfloat16)
+    out = torch.empty(B, Hq, D, device="cuda", dtype=torch.bfloat16)
+    routed = decode.GQA_MFMA_MIN_ROWS
+
+    def valu(fn, *a, **kw):  # the VALU form whatever the routing says
+        decode.GQA_MFMA_MIN_ROWS = None
+        try:
+            return fn(*a, **kw)
+        finally:
+            decode.GQA_MFMA_MIN_ROWS = routed
+
+    for n in (2048, 4096):
+        for kind in ("bf16", "fp8"):
+            for G in GQA_GS:
+                caches[G][kind].set_lens([n] * B)
+            # decode as routed (what a model step runs), every G interleaved with G = 1
+            fns = {f"G{G}": (lambda i, G=G: ops.attention_decode(q, caches[G][kind], i % ncopy[G], out=out, t_bound=n))
+                   for G in GQA_GS}
+            r = _time_blocks(fns, blocks=blocks, iters=20)
+            row = {"op": "decode", "kind": kind, "B": B, "Hq": Hq, "D": D, "len": n, "cache_copies": dict(ncopy)}
+            for G in GQA_GS:
+                t = r[f"G{G}"]
+                kv = 2 * B * (Hq // G) * n * (D * 2 if kind == "bf16" else D + 4)
+                row[f"G{G}"] = {**t, "KV_GBps": kv / t["median_us"] / 1e3,
+                                "G1_over_this": r["G1"]["median_us"] / t["median_us"],
+                                "separated_from_G1": G > 1 and _sep({"min": t["min_us"], "max": t["max_us"]},
+                                                                    {"min": r["G1"]["min_us"],
+                                                                     "max": r["G1"]["max_us"]})}
+            rows["decode"].append(row)
+            print(json.dumps(row), flush=True)
+            # the two forms at 8 and 16 rows per K / V head
+            for G, T in GQA_FORMS:
+                c, nc = caches[G][kind], ncopy[G]
+                c.set_lens([n] * B)
+                qe = torch.randn(B, T, Hq, D, device="cuda").to(torch.bfloat16)
+                oe = torch.empty(B, T, Hq, D, device="cuda", dtype=torch.bfloat16)
+                fns = {"valu": (lambda i: valu(ops.attention_extend, qe, c, i % nc, out=oe, t_bound=n)),
+                       "mfma": (lambda i: ops.attention_chunk(qe, c, i % nc, out=oe, t_bound=n))}
+                r = _time_blocks(fns, blocks=blocks, iters=20)
+                row = {"op": "forms", "kind": kind, "G": G, "T": T, "rows": G * T, "B": B, "Hq": Hq, "D": D, "len": n,
+                       **r, "valu_over_mfma": r["valu"]["median_us"] / r["mfma"]["median_us"],
+                       "separated": _sep({"min": r["valu"]["min_us"], "max": r["valu"]["max_us"]},
+                                         {"min": r["mfma"]["min_us"], "max": r["mfma"]["max_us"]})}
+                rows["forms"].append(row)
+                print(json.dumps(row), flush=True)
+    return rows
+
+
+def _gqa_model_rows(quick: bool):
+    import dataclasses
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    rows = []
+    prompt, new = 2048 - 64, 64
+    base = CONFIGS["gpt-small" if quick else "gpt-1b"]
+    kvs = (base.n_heads, 4, 2)
+    models = {kv: GPT(dataclasses.replace(base, n_kv_heads=kv), device="cuda").eval() for kv in kvs}
+    kinds = {"bf16": None, "fp8": torch.float8_e4m3fn}
+    for B in (1, 16):
+        idx = torch.randint(0, base.vocab_size, (B, prompt), device="cuda")
+        toks = torch.randint(0, base.vocab_size, (new, B), device="cuda")
+        nbytes = {}
+
+        def run(kv, kind, mode):
+            model = models[kv]
+            cache = model.new_cache(B, prompt + new, kv_dtype=kinds[kind])
+            model.prefill(idx, cache)
+            step = (lambda t: model.decode_step(t, cache)) if mode != "graph" else model.graphed_decode_step(cache)
+            step(toks[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(1, new):
+                step(toks[i])
+            torch.cuda.synchronize()
+            nbytes[f"kv{kv}_{kind}"] = cache.nbytes
+            return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+        keys = [(kv, kind, mode) for kv in kvs for kind in kinds for mode in ("eager", "graph")]
+        res = {k: [] for k in keys}
+        for _ in range(3):  # interleaved
+            for k in keys:
+                res[k].append(run(*k))
+        row = {"model": f"{'gpt-small' if quick else 'gpt-1b'} shape", "n_heads": base.n_heads, "B": B, "prompt": prompt,
+               "new": new, "cache_nbytes": dict(nbytes)}
+        for (kv, kind, mode), v in res.items():
+            row[f"kv{kv}_{kind}_{mode}"] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def step_gqa(quick: bool):
+    return {"kernel": _gqa_kernel_rows(quick), "model": _gqa_model_rows(quick)}
+
+
+STEPS = {"gqa": step_gqa, "chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
