@@ -335,6 +335,28 @@ int kfamd_kv_append_gqa_fp8(const void* qkv, void* k_codes, void* v_codes, float
                             const int* pos, int B, int T, int Hq, int Hkv, int D, int Tcap, long long qb, long long qt,
                             const long long* cache_strides, void* stream);
 
+// ---- rotary position embeddings (rope_bf16.hip) -----------------------------------------------------
+// table: fp32 [max_pos][D] contiguous, row p = cos(p f_i) | sin(p f_i), i < D/2 (built on the host). The
+// rotation is rotate-half: y[i] = x[i] c - x[i + D/2] s, y[i + D/2] = x[i + D/2] c + x[i] s, in fp32 without
+// FMA contraction, rounded once to bf16. The activation is [B][T][(Hq + 2 Hkv) D], q | k | v (element strides
+// qb, qt); D = 64 / 128.
+// kfamd_rope_qkv_bf16: rotates the q and k head rows IN PLACE, v untouched. Row (b, t) is at position
+//   (pos ? pos[b] : 0) + t (pos: device int32 [B] or null); a row at or beyond max_pos is left as it is.
+//   inverse != 0: the inverse rotation (s -> -s), the backward of the forward map.
+// kfamd_kv_append_rope_bf16 / _fp8: kfamd_kv_append_gqa_bf16 / _fp8 of a rotary layer in one launch: position
+//   lens[b] + t, q and k rotated in place, the rotated K row and the V row written to cache row lens[b] + t
+//   (FP8: the bf16-rounded rotated K is what is quantised). Rows at or beyond Tcap are neither appended nor
+//   rotated. KFAMD_EINVAL also for max_pos < Tcap. Hq / Hkv in {1, 2, 4, 8, 16}.
+// KFAMD_EALIGN: the activation, the caches or the table not 16-B aligned.
+int kfamd_rope_qkv_bf16(void* qkv, const float* table, const int* pos, int max_pos, int B, int T, int Hq, int Hkv, int D,
+                        long long qb, long long qt, int inverse, void* stream);
+int kfamd_kv_append_rope_bf16(void* qkv, void* k_cache, void* v_cache, const int* lens, const float* table, int max_pos,
+                              int B, int T, int Hq, int Hkv, int D, int Tcap, long long qb, long long qt,
+                              const long long* cache_strides, void* stream);
+int kfamd_kv_append_rope_fp8(void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale, const int* lens,
+                             const float* table, int max_pos, int B, int T, int Hq, int Hkv, int D, int Tcap,
+                             long long qb, long long qt, const long long* cache_strides, void* stream);
+
 // Weight-streaming NT GEMM for 1 <= M <= 16 (gemm_skinny_bf16.hip): C[M][N] = act(alpha * A[M][K] .
 // W[N][K]^T + bias[N]) (+ R[M][N]); K % 8 == 0, A / W rows 16-B aligned, any N, epilogue semantics of
 // kfamd_gemm_nt_bf16. KFAMD_EINVAL: M outside 1..16 (or K % 8); KFAMD_EALIGN: alignment.

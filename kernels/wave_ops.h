@@ -65,13 +65,13 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-// max over the same groups (order-independent)
+// max over the same groups (order-independent); also over aligned groups of 4 lanes, the quad steps alone
 template <int N>
 __device__ __forceinline__ float group_max(float v) {
-  static_assert(N == 8 || N == 16, "group_max: 8 or 16 lanes");
+  static_assert(N == 4 || N == 8 || N == 16, "group_max: 4, 8 or 16 lanes");
   v = fmaxf(v, dpp_mov<dpp::kQuadXor1>(v));
   v = fmaxf(v, dpp_mov<dpp::kQuadXor2>(v));
-  v = fmaxf(v, dpp_mov<dpp::kRowHalfMirror>(v));
+  if constexpr (N >= 8) v = fmaxf(v, dpp_mov<dpp::kRowHalfMirror>(v));
   if constexpr (N == 16) v = fmaxf(v, dpp_mov<dpp::kRowMirror>(v));
   return v;
 }

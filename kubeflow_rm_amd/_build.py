@@ -81,7 +81,7 @@ TU_FLAGS = {"attention_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 # translation units whose kernels must not spill: several KV-cache attention instantiations sit at the VGPR
 # budget (attn_chunk_split<Fp8Rows, 128, true>: 255 of 256), and a spill there costs time without failing any
 # test. The compiler's resource remarks are read at build time; a kernel with scratch fails the build.
-NO_SCRATCH_TUS = ("attn_kv.hip", "attn_kv_mfma.hip")
+NO_SCRATCH_TUS = ("attn_kv.hip", "attn_kv_mfma.hip", "rope_bf16.hip")
 
 
 def check_no_scratch(src: Path, remarks: str) -> None:

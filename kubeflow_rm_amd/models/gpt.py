@@ -26,8 +26,18 @@ Grouped-query attention: ``GPTConfig(n_kv_heads=Hkv)`` with ``Hkv`` dividing ``n
 projection then has ``(n_heads + 2 * Hkv) * head_dim`` features, ``q | k | v``. The KV cache holds the ``Hkv``
 heads (1 / G of the bytes) and the decode / extend / chunk kernels stream K / V once per group. Training and
 ``prefill`` run the flash kernel on K / V expanded to ``n_heads`` heads (a materialised copy; autograd sums dK / dV
-over the group); a GQA-native flash forward / backward, tensor-parallel K / V head sharding, group sizes outside
-{1, 2, 4, 8, 16} on a GPU, and RoPE and the other Llama-architecture pieces are not built.
+over the group); a GQA-native flash forward / backward, tensor-parallel K / V head sharding and group sizes outside
+{1, 2, 4, 8, 16} on a GPU are not built.
+
+Rotary position embeddings: ``GPTConfig(pos="rope", rope_theta=...)`` drops the learned position table (no ``pos``
+parameter, nothing of it in ``state_dict()``) and rotates q and k instead (rotate-half over the whole head dim; the
+rule is the docstring of ``ops/rope.py``), from one non-persistent fp32 buffer ``rope_table [max_seq, head_dim]``.
+Training rotates inside ``ops.attn_block(rope=...)`` on the fused path and with ``ops.rope_qkv`` on the others;
+``prefill`` / ``decode_step`` / ``extend`` rotate inside their one ``ops.kv_append(..., rope=...)`` per layer, at
+positions read from the device-side ``cache.lens``: K is stored rotated, the step stays capturable and launches
+no more kernels than with learned positions. ``pos="learned"`` (the default) is the model as it was. Not built:
+RMSNorm blocks, SwiGLU, partial rotary, scaled rotary (NTK / YaRN), and a rotation fused into the flash kernel's
+Q / K loads.
 """
 from __future__ import annotations
 
@@ -52,8 +62,14 @@ class GPTConfig:
     dropout: float = 0.0
     dtype: torch.dtype = torch.bfloat16
     n_kv_heads: int | None = None  # K / V heads (grouped-query attention); None: n_heads
+    pos: str = "learned"  # "learned": a [max_seq, d_model] table added to the embedding; "rope": rotary q / k
+    rope_theta: float = 10000.0  # the rotary base (pos="rope")
 
     def __post_init__(self):
+        if self.pos not in ("learned", "rope"):
+            raise ValueError(f'pos={self.pos!r}: "learned" or "rope" expected')
+        if self.pos == "rope" and (self.d_model // self.n_heads) % 2:
+            raise ValueError(f"pos=\"rope\" needs an even head dim, got {self.d_model // self.n_heads}")
         if self.n_kv_heads is not None and (self.n_kv_heads < 1 or self.n_heads % self.n_kv_heads):
             raise ValueError(f"n_kv_heads={self.n_kv_heads} must divide n_heads={self.n_heads}")
 
@@ -151,7 +167,7 @@ class Block(torch.nn.Module):
                                             device=device, seed=seed + 3)
         self.fc2 = tpl.RowParallelLinear(cfg.d_ff, cfg.d_model, group=tp_group, dtype=cfg.dtype, device=device, seed=seed + 4)
 
-    def _attention_gqa(self, x, residual):
+    def _attention_gqa(self, x, residual, rope=None):
         """Grouped-query attention of the training forward. The fused ``ops.attn_block`` node (and
         ``ops.attention_qkv``) assume a ``[3 h hd]`` activation and are bypassed: q and the K / V heads, each
         repeated over its group (a materialised copy), go through ``ops.flash_attention`` on the native flash
@@ -160,6 +176,8 @@ class Block(torch.nn.Module):
         h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
         G = h // hkv
         qkv = self.qkv(x)
+        if rope is not None:
+            qkv = ops.rope_qkv(qkv, rope, h, hkv)
         q = qkv[..., :h * hd].view(B, T, h, hd)
         k, v = qkv[..., h * hd:].view(B, T, 2, hkv, hd).unbind(2)
         k = k.unsqueeze(3).expand(B, T, hkv, G, hd).reshape(B, T, h, hd)
@@ -171,19 +189,23 @@ class Block(torch.nn.Module):
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
 
-    def attention(self, x, residual=None):
+    def attention(self, x, residual=None, rope=None):
+        """``rope``: the model's rotary table (``GPTConfig(pos="rope")``): q and k are rotated right after the QKV
+        projection, inside ``ops.attn_block`` on the fused path, by ``ops.rope_qkv`` on the others."""
         B, T, _ = x.shape
         h, hd = self.local_heads, self.cfg.head_dim
         if self.local_kv_heads != h:
-            return self._attention_gqa(x, residual)
+            return self._attention_gqa(x, residual, rope)
         # the fused single-rank path whenever the TP layers would issue no collective; a forced-distributed
         # run at world size 1 (KFAMD_FORCE_DIST) takes the TP layers and their RCCL all-reduces (ADVICE r5)
         if x.is_cuda and ops.native_enabled() and ops.attention_supported(x, hd) and not tpl._collective(self.tp_group):
             # one autograd node on the HIP path (ops.attn_block): its backward runs the QKV and
             # output-projection weight gradients as one GEMM launch
             return ops.attn_block(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, h, hd,
-                                  residual=residual)
+                                  residual=residual, rope=rope)
         qkv = self.qkv(x)  # [B, T, 3 * h * hd] — the column shard is [q_h | k_h | v_h] per rank
+        if rope is not None:  # per head: a tensor-parallel shard rotates its own heads
+            qkv = ops.rope_qkv(qkv, rope, h, h)
         if ops.native_enabled() and ops.attention_supported(qkv, hd):
             y = ops.attention_qkv(qkv.contiguous(), h, hd, causal=True)  # [B, T, h * hd]
             return self.proj(y, residual=residual)
@@ -199,11 +221,11 @@ class Block(torch.nn.Module):
                            residual=residual)
         return self.fc2(self.fc1(h), residual=residual)
 
-    def forward(self, x):
+    def forward(self, x, rope=None):
         # both residual adds ride in the output projections' GEMM epilogues (without TP); the
         # residual gradient joins the LayerNorm backward's dx store (LayerNorm.with_residual)
         h, r = self.ln1.with_residual(x)
-        x = self.attention(h, residual=r)
+        x = self.attention(h, residual=r, rope=rope)
         h, r = self.ln2.with_residual(x)
         return self.mlp(h, r)
 
@@ -297,15 +319,23 @@ class GPT(torch.nn.Module):
         emb = torch.randn(cfg.vocab_size, cfg.d_model, generator=g) * 0.02
         pos = torch.randn(cfg.max_seq, cfg.d_model, generator=g) * 0.01
         self.tok = torch.nn.Parameter(emb.to(dtype=cfg.dtype, device=device))
-        self.pos = torch.nn.Parameter(pos.to(dtype=cfg.dtype, device=device))
+        if cfg.pos == "rope":  # no position parameter; one fp32 table [max_seq, head_dim], not in the state dict
+            self.register_parameter("pos", None)
+            self.register_buffer("rope_table", ops.rope_table(cfg.max_seq, cfg.head_dim, cfg.rope_theta, device),
+                                 persistent=False)
+        else:
+            self.pos = torch.nn.Parameter(pos.to(dtype=cfg.dtype, device=device))
+            self.register_buffer("rope_table", None, persistent=False)
         self.blocks = torch.nn.ModuleList([Block(cfg, i, tp_group, device) for i in range(cfg.n_layers)])
         self.ln_f = LayerNorm(cfg.d_model, cfg.dtype, device)
 
     def forward(self, idx, targets=None):
         B, T = idx.shape
-        x = F.embedding(idx, self.tok) + self.pos[:T]
+        x = F.embedding(idx, self.tok)
+        if self.pos is not None:
+            x = x + self.pos[:T]
         for blk in self.blocks:
-            x = blk(x)
+            x = blk(x, self.rope_table)
         x = self.ln_f(x)
         logits = tpl._linear(x, self.tok)  # tied output head [B, T, vocab]
         if targets is None:
@@ -360,14 +390,17 @@ class GPT(torch.nn.Module):
             raise ValueError("prefill expects an empty cache (continuing a cache takes decode_step)")
         native = self._native_decode(self.tok)
         c = self.cfg
-        x = F.embedding(idx, self.tok) + self.pos[:T]
+        x = F.embedding(idx, self.tok)
+        if self.pos is not None:
+            x = x + self.pos[:T]
+        rope = self.rope_table  # rotary: kv_append rotates q and k of qkv in place, the attention below reads them
         for li, blk in enumerate(self.blocks):
             h, hkv, hd = blk.local_heads, blk.local_kv_heads, c.head_dim
             if native:
                 x2 = x.reshape(B * T, c.d_model)
                 y = ops.layer_norm_fwd(x2, blk.ln1.weight, blk.ln1.bias)[0]
                 qkv = ops.gemm_nt(y, blk.qkv.weight, bias=blk.qkv.bias).view(B, T, (h + 2 * hkv) * hd)
-                ops.kv_append(qkv, cache, li, q_heads=h)
+                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
                 if hkv == h:
                     a = ops.attention_qkv(qkv, h, hd, causal=True).view(B * T, h * hd)
                 else:  # the flash kernel on K / V expanded to h heads (a copy)
@@ -379,7 +412,7 @@ class GPT(torch.nn.Module):
                 x = ops.gemm_nt(y, blk.fc2.weight, bias=blk.fc2.bias, residual=x2).view(B, T, c.d_model)
             else:
                 qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
-                ops.kv_append(qkv, cache, li, q_heads=h)
+                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
                 q, k, v = self._split_gqa(qkv, h, hkv, hd)
                 a = F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
                 x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
@@ -467,7 +500,10 @@ class GPT(torch.nn.Module):
         c = self.cfg
         wsel = self._weight_selector(weights, B)
         head_w = self._head_weight(weights, B)
-        x = F.embedding(tok, self.tok) + F.embedding(cache.lens, self.pos)  # [B, d_model]
+        x = F.embedding(tok, self.tok)  # [B, d_model]
+        if self.pos is not None:
+            x = x + F.embedding(cache.lens, self.pos)
+        rope = self.rope_table  # rotary: the append rotates q and k in place at position cache.lens, on the device
         # the step's attention sees the row it appends: lens + 1, computed on the device
         att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1)}
         for li, blk in enumerate(self.blocks):
@@ -475,7 +511,7 @@ class GPT(torch.nn.Module):
             if native:
                 y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
                 qkv = self._skinny(y, wsel(li, "qkv"), blk.qkv.bias)  # [B, (h + 2 * hkv) * hd]
-                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h)
+                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h, rope=rope)
                 a = torch.empty(B, h * hd, device=x.device, dtype=x.dtype)
                 ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, out=a.view(B, h, hd), **att)
                 x = self._skinny(a, wsel(li, "proj"), blk.proj.bias, residual=x)
@@ -484,7 +520,7 @@ class GPT(torch.nn.Module):
                 x = self._skinny(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
-                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h)  # torch ops: CPU tensors / torch_reference()
+                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h, rope=rope)  # torch ops: CPU / torch_reference()
                 a = ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, **att).reshape(B, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
                 y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
@@ -550,8 +586,11 @@ class GPT(torch.nn.Module):
         B, T = idx.shape
         attend = ops.attention_chunk if mfma else ops.attention_extend
         c = self.cfg
-        pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
-        x = F.embedding(idx, self.tok) + F.embedding(pos, self.pos)  # [B, T, d_model]
+        x = F.embedding(idx, self.tok)  # [B, T, d_model]
+        if self.pos is not None:
+            pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
+            x = x + F.embedding(pos, self.pos)
+        rope = self.rope_table
         # the step's attention sees the rows it appends: lens + T, computed on the device
         att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T)}
         lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
@@ -563,7 +602,7 @@ class GPT(torch.nn.Module):
             if native:
                 y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
                 qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, -1)
-                ops.kv_append(qkv, cache, li, q_heads=h)
+                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
                 a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
                 attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, out=a.view(B, T, h, hd), **att)
                 x = lin(a.view(B * T, h * hd), wsel(li, "proj"), blk.proj.bias, residual=x)
@@ -572,7 +611,7 @@ class GPT(torch.nn.Module):
                 x = lin(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
-                ops.kv_append(qkv, cache, li, q_heads=h)  # torch ops: CPU tensors / torch_reference()
+                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)  # torch ops: CPU tensors / torch_reference()
                 a = attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, **att).reshape(B, T, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
                 y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")

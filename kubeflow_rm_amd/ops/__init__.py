@@ -10,6 +10,7 @@ from .allreduce import OneShotAllReduce  # noqa: F401
 from .graph import GraphedCallable  # noqa: F401
 from .decode import KVCache, attention_chunk, attention_decode, attention_extend, kv_append  # noqa: F401
 from . import decode  # noqa: F401
+from .rope import rope_qkv, rope_table  # noqa: F401
 from .sample import sample  # noqa: F401  (the function shadows its module: import names from ops.sample directly)
 
 

@@ -124,6 +124,11 @@ _SIGNATURES = {
                                          ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
                                         c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_rope_qkv_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll, c_int, c_vp]),
+    "kfamd_kv_append_rope_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_rope_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_gemm_nt_skinny_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
                                           c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_bf16_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,

@@ -126,28 +126,34 @@ class _AttnBlock(torch.autograd.Function):
     backward, the QKV dgrad, and then both weight gradients in ONE launch (gemm.wgrad_pair: 192 + 64
     tiles at gpt-1b, where apart the QKV wgrad filled 75 % of the CUs and the projection's ran
     split-K). The forward is the separate layers' (gemm_nt with bias, _fwd, gemm_nt with bias and
-    residual)."""
+    residual). ``rope`` (a rotary table, ops/rope.py): qkv is rotated in place right after its GEMM, and dqkv
+    inverse-rotated in place right after the attention backward, before the bias gradient, the dgrad and the
+    weight-gradient pair read it."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wproj, bproj, h, hd, causal, scale, residual):
+    def forward(ctx, x, wqkv, bqkv, wproj, bproj, h, hd, causal, scale, residual, rope=None):
         from .gemm import gemm_nt
+        from .rope import rotate_native_
         B, T, D = x.shape
         x2 = x.reshape(B * T, D)
         if x2.stride(-1) != 1 or x2.stride(0) != D:
             x2 = x2.contiguous()
         qkv = gemm_nt(x2, wqkv, bias=bqkv).view(B, T, 3, h, hd)
+        if rope is not None:
+            rotate_native_(qkv.view(B, T, 3 * h * hd), rope, h, h)
         o = torch.empty(B, T, h, hd, device=x.device, dtype=x.dtype)
         lse = _fwd(*(_bhtd(qkv[:, :, i]) for i in range(3)), _bhtd(o), causal, scale)
         o2 = o.view(B * T, h * hd)
         res = residual.reshape(B * T, wproj.shape[0]).contiguous() if residual is not None else None
         out = gemm_nt(o2, wproj, bias=bproj, residual=res)
         ctx.save_for_backward(x2, wqkv, bqkv, wproj, bproj, qkv, o, lse)
-        ctx.dims, ctx.causal, ctx.scale = (B, T, D, h, hd), causal, scale
+        ctx.dims, ctx.causal, ctx.scale, ctx.rope = (B, T, D, h, hd), causal, scale, rope
         return out.view(B, T, wproj.shape[0])
 
     @staticmethod
     def backward(ctx, gy):
         from .gemm import act_grad, mm, wgrad_pair
+        from .rope import rotate_native_
         x2, wqkv, bqkv, wproj, bproj, qkv, o, lse = ctx.saved_tensors
         B, T, D, h, hd = ctx.dims
         ni = ctx.needs_input_grad
@@ -167,6 +173,8 @@ class _AttnBlock(torch.autograd.Function):
         dqkv = torch.empty(B, T, 3, h, hd, device=qkv.device, dtype=qkv.dtype)
         _bwd(*(_bhtd(qkv[:, :, i]) for i in range(3)), _bhtd(o), _bhtd(do), lse,
              *(_bhtd(dqkv[:, :, i]) for i in range(3)), ctx.causal, ctx.scale)
+        if ctx.rope is not None:  # the gradient of the rotated q, k -> of the projection's output
+            rotate_native_(dqkv.view(B, T, 3 * h * hd), ctx.rope, h, h, inverse=True)
         dqkv2 = dqkv.view(B * T, 3 * h * hd)
         gbq = bias_grad(dqkv2, bqkv, bqkv is not None and ni[2])
         dx = mm(dqkv2, wqkv).view(B, T, D) if ni[0] else None
@@ -177,20 +185,24 @@ class _AttnBlock(torch.autograd.Function):
         else:
             gwq = mm(dqkv2, x2, trans_a=True) if ni[1] else None
             gwp = mm(gy2, o2, trans_a=True) if ni[3] else None
-        return dx, gwq, gbq, gwp, gbp, None, None, None, None, (gy if ni[9] else None)
+        return dx, gwq, gbq, gwp, gbp, None, None, None, None, (gy if ni[9] else None), None
 
 
 def attn_block(x: torch.Tensor, wqkv: torch.Tensor, bqkv: torch.Tensor | None, wproj: torch.Tensor,
                bproj: torch.Tensor | None, h: int, hd: int, residual: torch.Tensor | None = None,
-               causal: bool = True, scale: float | None = None) -> torch.Tensor:
+               causal: bool = True, scale: float | None = None, rope: torch.Tensor | None = None) -> torch.Tensor:
     """A transformer block's attention half on the HIP kernels: ``proj(attn(qkv(x))) (+ residual)``,
-    x ``[B, T, D]``, wqkv ``[3 h hd, D]`` (q | k | v rows, heads inside each), wproj ``[D_out, h hd]``."""
+    x ``[B, T, D]``, wqkv ``[3 h hd, D]`` (q | k | v rows, heads inside each), wproj ``[D_out, h hd]``.
+    ``rope``: an ``ops.rope_table`` ``[max_pos >= T, hd]``; q and k are rotated (positions 0 .. T - 1) between the
+    QKV projection and the attention, in place in both directions (``ops.rope_qkv``'s kernel)."""
     if x.dim() != 3 or wqkv.shape[0] != 3 * h * hd or wproj.shape[1] != h * hd:
         raise ValueError("attn_block: x [B, T, D], wqkv [3 h hd, D], wproj [D_out, h hd] expected")
     if not supported(x, hd):
         raise ValueError(f"attn_block: bf16 CUDA input with head dim in {HEAD_DIMS} expected")
+    if rope is not None and (rope.dim() != 2 or rope.shape[1] != hd or rope.shape[0] < x.shape[1]):
+        raise ValueError(f"attn_block: rope [max_pos >= {x.shape[1]}, {hd}] expected, got {tuple(rope.shape)}")
     return _AttnBlock.apply(x, wqkv, bqkv, wproj, bproj, h, hd, causal,
-                            scale if scale is not None else 1.0 / math.sqrt(hd), residual)
+                            scale if scale is not None else 1.0 / math.sqrt(hd), residual, rope)
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,

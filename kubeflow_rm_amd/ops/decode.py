@@ -46,6 +46,12 @@ there on (faster from 8 rows: profiles/gqa; the results then agree with the VALU
 not bit for bit). The CPU /
 ``ops.torch_reference()`` forms take any divisor and expand K / V with ``repeat_interleave(G, dim=1)``. Not built:
 G outside ``GROUP_SIZES`` on a GPU.
+
+Rotary position embeddings: ``kv_append(..., rope=table)`` (``ops.rope_table``; the rule is ``ops/rope.py``'s) is the
+append of a rotary layer. It rotates the q and k slices of ``qkv`` in place at positions ``lens[b] + t``, read on the
+device, and stores the rotated K (``kernels/rope_bf16.hip``: one launch, bf16 and FP8 caches); the attention call
+after it reads the rotated q slice of the same buffer. The attention kernels know nothing of it: the cache simply
+holds rotated keys.
 """
 from __future__ import annotations
 
@@ -258,10 +264,17 @@ class KVCache:
         return self.chunk_workspace
 
 
-def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None = None) -> None:
+def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None = None,
+              rope: torch.Tensor | None = None) -> None:
     """K, V rows of the fused QKV activation ``[B, T, 3*H*D]`` -> cache rows ``lens[b] .. lens[b]+T-1``
     (rows at or beyond the capacity are dropped). ``lens`` is not advanced. ``q_heads=Hq`` (default: the
-    cache's H): a grouped-query layer's activation ``[B, T, (Hq + 2*H)*D]``, ``q: Hq*D | k: H*D | v: H*D``."""
+    cache's H): a grouped-query layer's activation ``[B, T, (Hq + 2*H)*D]``, ``q: Hq*D | k: H*D | v: H*D``.
+
+    ``rope=table`` (``ops.rope_table``, fp32 ``[max_pos >= capacity, D]``): the append of a rotary layer. The q and k
+    slices of ``qkv`` are rotated IN PLACE for positions ``lens[b] + t`` (the rule of ``ops/rope.py``), and the
+    rotated K row and the V row are stored; an FP8 cache quantises the rotated K as rounded to the activation's
+    dtype. Rows at or beyond the capacity are neither appended nor rotated. On a GPU it is one launch
+    (``kfamd_kv_append_rope_*``); on the torch path rotate, then the append below. ``rope=None``: no rotation."""
     B, H, D = cache.B, cache.H, cache.D
     Hq = H if q_heads is None else int(q_heads)
     G = _group("kv_append", Hq, cache, _native(qkv))
@@ -269,6 +282,15 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None
         raise ValueError(f"kv_append: qkv [B={B}, T, {(Hq + 2 * H) * D}] expected, got {tuple(qkv.shape)}")
     T = qkv.shape[1]
     k, v = cache.k[layer], cache.v[layer]
+    if rope is not None:
+        if rope.dim() != 2 or rope.shape[1] != D or rope.shape[0] < cache.capacity or rope.dtype != torch.float32:
+            raise ValueError(f"kv_append: rope must be an fp32 [max_pos >= {cache.capacity}, {D}] table, got "
+                             f"{tuple(rope.shape)} {rope.dtype}")
+        if _native(qkv):
+            _kv_append_rope_native(qkv, cache, layer, Hq, rope)
+            return
+        from .rope import rotate_torch  # rows at or beyond the capacity have no table row here: left as they are
+        qkv.copy_(rotate_torch(qkv, rope[:cache.capacity], Hq, H, positions=cache.lens))
     if not _native(qkv):  # [B, T, 3, H, D]: slot 0 the last H query heads (unused), slots 1 and 2 k and v
         x = qkv[:, :, (Hq - H) * D:].reshape(B, T, 3, H, D)
     if cache.fp8 and not _native(qkv):
@@ -295,6 +317,24 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None
             *((H,) if G == 1 else (Hq, H)), D, cache.capacity, qkv.stride(0), qkv.stride(1),
             _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
     _lib.check(rc, f"kv_append[{tag}B={B} T={T} Hq={Hq} H={H} D={D}]")
+
+
+def _kv_append_rope_native(qkv, cache: KVCache, layer: int, Hq: int, rope: torch.Tensor) -> None:
+    """The fused rotate-and-append launch (``kernels/rope_bf16.hip``); the grouped signature covers G = 1."""
+    B, H, D, T = cache.B, cache.H, cache.D, qkv.shape[1]
+    k, v = cache.k[layer], cache.v[layer]
+    if qkv.dtype != torch.bfloat16 or qkv.stride(2) != 1:
+        raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
+    if D not in HEAD_DIMS or k.dtype not in CACHE_DTYPES:
+        raise ValueError(f"kv_append(rope=...): head dim in {HEAD_DIMS} and a bf16 or float8_e4m3fn cache expected on "
+                         f"a GPU, got {D}, {k.dtype}")
+    if not rope.is_cuda or rope.device != qkv.device or not rope.is_contiguous():
+        raise ValueError("kv_append: rope must be a contiguous table on the activation's device")
+    fn, scales, tag = _entry("kfamd_kv_append_rope", cache, layer)
+    rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(),
+            rope.data_ptr(), rope.shape[0], B, T, Hq, H, D, cache.capacity, qkv.stride(0), qkv.stride(1),
+            _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
+    _lib.check(rc, f"kv_append[rope {tag}B={B} T={T} Hq={Hq} H={H} D={D}]")
 
 
 def _kv_append_fp8_torch(x, cache: KVCache, layer: int) -> None:

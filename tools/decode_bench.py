@@ -52,6 +52,12 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         MFMA form (ops.attention_chunk) on the same cache: what ops.decode.GQA_MFMA_MIN_ROWS is set from.
         Model: the gpt-1b shape with n_kv_heads in {16, 4, 2} (random weights), B in {1, 16}, position about
         2048, bf16 and FP8 caches, eager and graphed, interleaved runs: ms/token and KVCache.nbytes.
+  rope  (not in the default list) rotary position embeddings. Append: ops.kv_append(rope=table) (one launch)
+        against kv_append alone and against rope_qkv + kv_append (two launches), the gpt-1b layer (B = 8, 16
+        heads, D = 128), T in {1, 2048}, bf16 and FP8 caches, 7 interleaved blocks. Decode: gpt-1b with
+        pos="rope" against pos="learned" in one process, B in {1, 16}, position about 2048, graphed and eager,
+        7 interleaved runs: ms/token. Train: forward + backward of 4 x 2048 tokens (no optimiser), rotary
+        against learned, 7 interleaved blocks.
 """
 from __future__ import annotations
 
@@ -69,7 +75,7 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
-                "chunk": 900, "gqa": 1000}
+                "chunk": 900, "gqa": 1000, "rope": 600}
 GQA_GS = (1, 2, 4, 8, 16)
 GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
 CHUNK_TS = (16, 32, 64, 128, 256, 512)
@@ -900,7 +906,114 @@ def step_gqa(quick: bool):
     return {"kernel": _gqa_kernel_rows(quick), "model": _gqa_model_rows(quick)}
 
 
-STEPS = {"gqa": step_gqa, "chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+def _rope_append_rows(quick: bool):
+    """(a) the fused rotate-and-append against kv_append alone and against kv_append + a separate rope_qkv launch."""
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    B, H, D, cap, ncopy = 8, 16, 128, 4096, 2  # the gpt-1b layer
+    table = ops.rope_table(cap, D, device="cuda")
+    for kind, dt in (("bf16", torch.bfloat16), ("fp8", torch.float8_e4m3fn)):
+        cache = ops.KVCache(ncopy, B, H, D, cap, device="cuda", dtype=dt)
+        for T in (1, 2048):
+            qkv = torch.randn(B, T, 3 * H * D, device="cuda").to(torch.bfloat16)
+            cache.set_lens([cap - T] * B)  # lens is not advanced by the append: every call writes the same rows
+
+            def two(i):
+                ops.rope_qkv(qkv, table, H, H, cache.lens)
+                ops.kv_append(qkv, cache, i % ncopy)
+
+            fns = {"append": lambda i: ops.kv_append(qkv, cache, i % ncopy),
+                   "fused": lambda i: ops.kv_append(qkv, cache, i % ncopy, rope=table),
+                   "rope_then_append": two}
+            r = _time_blocks(fns, blocks=5 if quick else 7, iters=20)
+            row = {"op": "kv_append", "cache": kind, "B": B, "H": H, "D": D, "T": T, **r,
+                   "fused_over_append": r["fused"]["median_us"] / r["append"]["median_us"],
+                   "two_launches_over_fused": r["rope_then_append"]["median_us"] / r["fused"]["median_us"]}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def _rope_models(quick: bool):
+    import dataclasses
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    base = CONFIGS["gpt-small" if quick else "gpt-1b"]
+    return base, {p: GPT(dataclasses.replace(base, pos=p), device="cuda") for p in ("learned", "rope")}
+
+
+def _rope_decode_rows(quick: bool, base, models):
+    """(b) graphed (and eager) decode, ms/token around position 2048: pos="rope" against pos="learned"."""
+    import torch
+    rows = []
+    prompt, new = 2048 - 64, 64
+    for B in (1, 16):
+        idx = torch.randint(0, base.vocab_size, (B, prompt), device="cuda")
+        toks = torch.randint(0, base.vocab_size, (new, B), device="cuda")
+
+        def run(p, mode):
+            model = models[p].eval()
+            cache = model.new_cache(B, prompt + new)
+            model.prefill(idx, cache)
+            step = (lambda t: model.decode_step(t, cache)) if mode != "graph" else model.graphed_decode_step(cache)
+            step(toks[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(1, new):
+                step(toks[i])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+        keys = [(p, mode) for mode in ("graph", "eager") for p in ("learned", "rope")]
+        res = {k: [] for k in keys}
+        for _ in range(3 if quick else 7):  # interleaved
+            for k in keys:
+                res[k].append(run(*k))
+        row = {"model": f"{'gpt-small' if quick else 'gpt-1b'}", "B": B, "prompt": prompt, "new": new}
+        for (p, mode), v in res.items():
+            row[f"{p}_{mode}"] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+        for mode in ("graph", "eager"):
+            a, b = row[f"rope_{mode}"], row[f"learned_{mode}"]
+            row[f"rope_over_learned_{mode}"] = a["ms_per_token"] / b["ms_per_token"]
+            row[f"separated_{mode}"] = a["max"] < b["min"] or b["max"] < a["min"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def _rope_train_rows(quick: bool, base, models):
+    """(c) the training step's forward + backward (no optimiser), 4 x 2048 tokens: rotary against learned."""
+    import torch
+    Bt, T = (2, 512) if quick else (4, 2048)
+    idx = torch.randint(0, base.vocab_size, (Bt, T), device="cuda")
+    tgt = torch.randint(0, base.vocab_size, (Bt, T), device="cuda")
+
+    def fb(p):
+        def f(i):
+            m = models[p].train()
+            _, loss = m(idx, tgt)
+            loss.backward()
+            for q in m.parameters():
+                q.grad = None
+        return f
+
+    r = _time_blocks({p: fb(p) for p in ("learned", "rope")}, blocks=5 if quick else 7, iters=3)
+    row = {"model": f"{'gpt-small' if quick else 'gpt-1b'}", "B": Bt, "T": T, "what": "forward + backward", **r,
+           "rope_minus_learned_us": r["rope"]["median_us"] - r["learned"]["median_us"],
+           "separated": r["rope"]["max_us"] < r["learned"]["min_us"] or r["learned"]["max_us"] < r["rope"]["min_us"]}
+    print(json.dumps(row), flush=True)
+    return [row]
+
+
+def step_rope(quick: bool):
+    out = {"append": _rope_append_rows(quick)}
+    base, models = _rope_models(quick)
+    out["decode"] = _rope_decode_rows(quick, base, models)
+    out["train"] = _rope_train_rows(quick, base, models)
+    return out
+
+
+STEPS = {"rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
