@@ -32,6 +32,21 @@
 // The MFMA form's time hardly depends on M, the VALU form's FMA count grows with it. The VALU
 // instantiations for 2..8 activation rows are therefore reached only through the forced path: they are
 // kept so that this measurement can be repeated, not for production use.
+//
+// Gated form (GLU template parameter, kfamd_gemm_nt_skinny_bf16_glu*): the same kernels with a SwiGLU epilogue
+// over interleaved (gate, up) weight rows, see glu_store. Its cut-overs are its own, from tools/decode_bench.py
+// --steps glu (profiles/glu/README.md; K = 2048, medians of 7 interleaved blocks, us per call from Python,
+// weights rotated past the last-level cache), N = 2F at F = 5504 / 8192:
+//   M = 1: VALU at 2 rows (one pair) per wave 12.5 / 14.6, at 4 rows 14.4 / 19.2; MFMA TILES 1 / 2 / 4: 13.3 /
+//     15.4 / 14.8 and 16.5 / 19.6 / 17.9. Hence M = 1 takes the VALU form at 2 rows per wave at every N up to
+//     16384 (kGluValuMaxN: nothing wider was measured), where the ungated kernel takes 4 rows from N = 8192.
+//   M = 2: VALU 2 rows 14.1 / 16.8 against MFMA TILES 1 13.8 / 16.9: level, MFMA keeps it. M = 4: VALU 15.8 /
+//     20.3, MFMA TILES 1 / 2 / 4 14.6 / 15.5 / 15.0 and 18.1 / 19.4 / 17.8. M = 8: 16.3 / 15.8 / 15.3 and 21.0 /
+//     20.2 / 17.8. M = 16: 20.1 / 17.1 / 15.3 and 25.9 / 22.7 / 17.9.
+//   Hence from N = 8192 (kGluWideN) the MFMA form runs TILES = 1 at M <= 4 and TILES = 4 above (the ungated
+//   thresholds would give 2 at N = 11008: 17.1 against 15.3 at M = 16); narrower N was not measured and keeps the
+//   ungated thresholds. The two-launch form (this GEMM ungated to [M, 2F], then swiglu_bf16.hip) took 19.4 - 20.9 us
+//   at every one of these points: the gated launch (13.0 - 18.2) wins at each, by 2 to 7 us.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kfamd_kernels.h"
@@ -44,6 +59,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kValuMaxM = 1;
+// the gated form's own cut-overs (the GLU table in the header comment)
+constexpr int kGluValuMaxM = 1;
+constexpr int kGluValuMaxN = 16384;  // inclusive: 2 x 8192, the widest gated shape measured
+constexpr int kGluWideN = 8192;      // from here the MFMA tile count follows M, below it the ungated thresholds
 constexpr int kValuMaxN = 16384;  // the 32000-row LM head streams faster on the MFMA form even at M = 1
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -86,8 +105,20 @@ __device__ __forceinline__ void epilogue_store(const SkinnyArgs& a, int m, int n
   a.C[m * a.ldc + n] = (__bf16)v;
 }
 
+// GLU (the gated form, kfamd_gemm_nt_skinny_bf16_glu*): weight rows n (even) and n + 1 are gate and up of output
+// column n / 2 (ops/swiglu.py states the rule): C[m][n / 2] = silu(z[n]) * z[n + 1], z = alpha * acc + bias, all
+// in fp32, rounded once. No activation code, no residual; a.N is the weight's row count 2F.
+__device__ __forceinline__ void glu_store(const SkinnyArgs& a, int m, int n, float accg, float accu) {
+  float g = accg * a.alpha, u = accu * a.alpha;
+  if (a.bias) {
+    g += (float)a.bias[n];
+    u += (float)a.bias[n + 1];
+  }
+  a.C[m * a.ldc + (n >> 1)] = (__bf16)(g / (1.f + __expf(-g)) * u);
+}
+
 // ---- VALU form -------------------------------------------------------------------------------
-template <int MR, int ROWS>
+template <int MR, int ROWS, bool GLU = false>
 __global__ __launch_bounds__(256) void skinny_valu(SkinnyArgs a) {
   constexpr int U = 2;  // 16-B pieces per row in flight per lane
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -136,17 +167,29 @@ __global__ __launch_bounds__(256) void skinny_valu(SkinnyArgs a) {
       }
     }
   }
+  if constexpr (GLU) {
+    // ROWS is even and so is n0: the wave's rows are ROWS / 2 whole (gate, up) pairs; N is even, so a pair
+    // is wholly inside or wholly outside N
 #pragma unroll
-  for (int r = 0; r < ROWS; ++r)
+    for (int r = 0; r < ROWS; r += 2)
 #pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const float s = kfw::wave_sum(acc[r][m]);
-      if (lane == 0 && n0 + r < a.N && m < a.M) epilogue_store(a, m, n0 + r, s);
-    }
+      for (int m = 0; m < MR; ++m) {
+        const float sg = kfw::wave_sum(acc[r][m]), su = kfw::wave_sum(acc[r + 1][m]);
+        if (lane == 0 && n0 + r < a.N && m < a.M) glu_store(a, m, n0 + r, sg, su);
+      }
+  } else {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int m = 0; m < MR; ++m) {
+        const float s = kfw::wave_sum(acc[r][m]);
+        if (lane == 0 && n0 + r < a.N && m < a.M) epilogue_store(a, m, n0 + r, s);
+      }
+  }
 }
 
 // ---- MFMA form -------------------------------------------------------------------------------
-template <int TILES>
+template <int TILES, bool GLU = false>
 __global__ __launch_bounds__(256) void skinny_mfma(SkinnyArgs a) {
   constexpr int U = 4;  // K chunks (64 elements) in flight per wave
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -210,40 +253,71 @@ __global__ __launch_bounds__(256) void skinny_mfma(SkinnyArgs a) {
       red[wave][row >> 3][t][row & 7][m] = (row < 8) ? acc_e[t][i] : acc_o[t][i];
     }
   __syncthreads();
-  for (int e = threadIdx.x; e < TILES * 128; e += 256) {
-    const int wr = e & 7, mm = (e >> 3) & 15, t = e >> 7;
-    const int n = n0 + t * 8 + wr;
-    if (mm >= a.M || n >= a.N) continue;
-    float s = 0.f;
+  if constexpr (GLU) {
+    // an 8-row tile is 4 (gate, up) pairs: a thread sums the waves' partials of both rows of one pair, in the
+    // ungated epilogue's order, then gates
+    for (int e = threadIdx.x; e < TILES * 64; e += 256) {
+      const int pr = e & 3, mm = (e >> 2) & 15, t = e >> 6;
+      const int n = n0 + t * 8 + 2 * pr;
+      if (mm >= a.M || n >= a.N) continue;
+      float sg = 0.f, su = 0.f;
 #pragma unroll
-    for (int wv = 0; wv < 4; ++wv) s += red[wv][0][t][wr][mm] + red[wv][1][t][wr][mm];
-    epilogue_store(a, mm, n, s);
+      for (int wv = 0; wv < 4; ++wv) {
+        sg += red[wv][0][t][2 * pr][mm] + red[wv][1][t][2 * pr][mm];
+        su += red[wv][0][t][2 * pr + 1][mm] + red[wv][1][t][2 * pr + 1][mm];
+      }
+      glu_store(a, mm, n, sg, su);
+    }
+  } else {
+    for (int e = threadIdx.x; e < TILES * 128; e += 256) {
+      const int wr = e & 7, mm = (e >> 3) & 15, t = e >> 7;
+      const int n = n0 + t * 8 + wr;
+      if (mm >= a.M || n >= a.N) continue;
+      float s = 0.f;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) s += red[wv][0][t][wr][mm] + red[wv][1][t][wr][mm];
+      epilogue_store(a, mm, n, s);
+    }
   }
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <int ROWS>
+template <int ROWS, bool GLU>
 void launch_valu(const SkinnyArgs& a, int mr, hipStream_t s) {
   const dim3 grid((unsigned)((a.N + 4 * ROWS - 1) / (4 * ROWS))), block(256);
   switch (mr) {
-    case 1: hipLaunchKernelGGL((skinny_valu<1, ROWS>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((skinny_valu<2, ROWS>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((skinny_valu<4, ROWS>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((skinny_valu<8, ROWS>), grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((skinny_valu<1, ROWS, GLU>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((skinny_valu<2, ROWS, GLU>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((skinny_valu<4, ROWS, GLU>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((skinny_valu<8, ROWS, GLU>), grid, block, 0, s, a); break;
   }
 }
 
-}  // namespace
+template <int TILES, bool GLU>
+void launch_mfma(const SkinnyArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((skinny_mfma<TILES, GLU>), dim3((unsigned)((a.N + 8 * TILES - 1) / (8 * TILES))), dim3(256), 0, s,
+                     a);
+}
 
-// path: 0 = by M (kValuMaxM), 1 = VALU (M <= 8), 2 = MFMA
-extern "C" int kfamd_gemm_nt_skinny_bf16_path(int path, const void* A, const void* W, void* C, const void* bias,
-                                              const void* R, int M, int N, int K, long long lda, long long ldw,
-                                              long long ldc, long long ldr, float alpha, int act, void* stream) {
+// tiles: 0 = by N; else the MFMA form's TILES (1, 2, 4) or the VALU form's weight rows per wave (2, 4; 8 activation
+// rows always take 2). The ungated entry points pass 0.
+template <bool GLU>
+int skinny_launch(int path, int tiles, const void* A, const void* W, void* C, const void* bias, const void* R, int M,
+                  int N, int K, long long lda, long long ldw, long long ldc, long long ldr, float alpha, int act,
+                  void* stream) {
   if (!A || !W || !C || M < 1 || M > 16 || N < 1 || K < 8 || K % 8) return KFAMD_EINVAL;
-  if (act < KFAMD_ACT_NONE || act > KFAMD_ACT_SILU || (R && act != KFAMD_ACT_NONE)) return KFAMD_EINVAL;
-  if (lda < K || ldw < K || ldc < N || (R && ldr < N)) return KFAMD_EINVAL;
+  if (GLU) {
+    if ((N & 1) || ldc < N / 2) return KFAMD_EINVAL;
+  } else {
+    if (act < KFAMD_ACT_NONE || act > KFAMD_ACT_SILU || (R && act != KFAMD_ACT_NONE)) return KFAMD_EINVAL;
+    if (ldc < N || (R && ldr < N)) return KFAMD_EINVAL;
+  }
+  if (lda < K || ldw < K) return KFAMD_EINVAL;
   if (path < 0 || path > 2 || (path == 1 && M > 8)) return KFAMD_EINVAL;
+  const bool valu = path == 1 || (path == 0 && (GLU ? M <= kGluValuMaxM && N <= kGluValuMaxN
+                                                     : M <= kValuMaxM && N < kValuMaxN));
+  if (tiles != 0 && (valu ? (tiles != 2 && tiles != 4) : (tiles != 1 && tiles != 2 && tiles != 4))) return KFAMD_EINVAL;
   if (!al16(A) || !al16(W) || (lda & 7) || (ldw & 7)) return KFAMD_EALIGN;
   SkinnyArgs a;
   a.A = static_cast<const __bf16*>(A);
@@ -256,23 +330,55 @@ extern "C" int kfamd_gemm_nt_skinny_bf16_path(int path, const void* A, const voi
   a.alpha = alpha;
   a.act = act;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool valu = path == 1 || (path == 0 && M <= kValuMaxM && N < kValuMaxN);
   if (valu) {
     const int mr = M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8));
     // weight rows per wave: 2 keeps N = 2048 at 256 workgroups; 4 shares the activation pieces wider
-    if (N >= 8192 && mr <= 4) launch_valu<4>(a, mr, s);
-    else launch_valu<2>(a, mr, s);
+    // (gated: 2 at every N, one pair per wave: 4 rows lost at every measured M and N)
+    const int rows = mr > 4 ? 2 : (tiles ? tiles : (N >= 8192 && !GLU ? 4 : 2));
+    if (rows == 4) launch_valu<4, GLU>(a, mr, s);
+    else launch_valu<2, GLU>(a, mr, s);
   } else {
-    if (N >= 16384) hipLaunchKernelGGL(skinny_mfma<4>, dim3((unsigned)((N + 31) / 32)), dim3(256), 0, s, a);
-    else if (N >= 4096) hipLaunchKernelGGL(skinny_mfma<2>, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(skinny_mfma<1>, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, s, a);
+    const int t = tiles ? tiles
+                        : (GLU && N >= kGluWideN ? (M <= 4 ? 1 : 4) : (N >= 16384 ? 4 : (N >= 4096 ? 2 : 1)));
+    if (t == 4) launch_mfma<4, GLU>(a, s);
+    else if (t == 2) launch_mfma<2, GLU>(a, s);
+    else launch_mfma<1, GLU>(a, s);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
+}  // namespace
+
+// path: 0 = by M (kValuMaxM), 1 = VALU (M <= 8), 2 = MFMA
+extern "C" int kfamd_gemm_nt_skinny_bf16_path(int path, const void* A, const void* W, void* C, const void* bias,
+                                              const void* R, int M, int N, int K, long long lda, long long ldw,
+                                              long long ldc, long long ldr, float alpha, int act, void* stream) {
+  return skinny_launch<false>(path, 0, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, alpha, act, stream);
 }
 
 extern "C" int kfamd_gemm_nt_skinny_bf16(const void* A, const void* W, void* C, const void* bias, const void* R, int M,
                                          int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
                                          float alpha, int act, void* stream) {
   return kfamd_gemm_nt_skinny_bf16_path(0, A, W, C, bias, R, M, N, K, lda, ldw, ldc, ldr, alpha, act, stream);
+}
+
+// ---- gated (SwiGLU) entry points: W [N = 2F][K] interleaved (row 2j gate, 2j + 1 up), C [M][F] ----------------
+extern "C" int kfamd_gemm_nt_skinny_bf16_glu_tiles(int path, int tiles, const void* A, const void* W, void* C,
+                                                   const void* bias, int M, int N, int K, long long lda, long long ldw,
+                                                   long long ldc, float alpha, void* stream) {
+  return skinny_launch<true>(path, tiles, A, W, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, alpha, KFAMD_ACT_NONE,
+                             stream);
+}
+
+extern "C" int kfamd_gemm_nt_skinny_bf16_glu_path(int path, const void* A, const void* W, void* C, const void* bias,
+                                                  int M, int N, int K, long long lda, long long ldw, long long ldc,
+                                                  float alpha, void* stream) {
+  return kfamd_gemm_nt_skinny_bf16_glu_tiles(path, 0, A, W, C, bias, M, N, K, lda, ldw, ldc, alpha, stream);
+}
+
+extern "C" int kfamd_gemm_nt_skinny_bf16_glu(const void* A, const void* W, void* C, const void* bias, int M, int N,
+                                             int K, long long lda, long long ldw, long long ldc, float alpha,
+                                             void* stream) {
+  return kfamd_gemm_nt_skinny_bf16_glu_tiles(0, 0, A, W, C, bias, M, N, K, lda, ldw, ldc, alpha, stream);
 }

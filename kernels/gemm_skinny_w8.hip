@@ -45,6 +45,18 @@
 // from there, the bf16 kernel's thresholds. VALU weight rows per wave: 2 below N = 8192, 4 from there (M <= 4):
 // 8192x2048 M = 4 12.6 / 11.6 at 2 / 4 rows, 2048x8192 M = 2 10.6 / 13.4.
 //
+// Gated form (GLU template parameter, kfamd_gemm_nt_skinny_w8_glu*): the same kernels with a SwiGLU epilogue over
+// interleaved (gate, up) rows, see glu_store. Measured with tools/decode_bench.py --steps glu
+// (profiles/glu/README.md; K = 2048, N = 2F at F = 5504 / 8192, medians of 7 interleaved blocks, us per call from
+// Python): every form and tile count sits on the launch floor, 11.7 - 12.5 us, at M <= 2 (MFMA TILES = 1 at F =
+// 8192 13.0 - 13.5); the VALU form leaves it at M = 4 for F = 8192 (16.4 against MFMA 12.5) and at M = 8 (23.7 /
+// 29.8 against 12.0 / 12.5); MFMA TILES = 1 loses from M = 8 (13.2 / 16.4) and TILES = 2 at M = 16 (13.7 / 17.4
+// against TILES = 4 11.8 / 12.3). So the gated form keeps the ungated cut-overs (kGluValuMaxM = kValuMaxM, the same
+// thresholds on N) with one exception: the ungated thresholds give N = 11008 TILES = 2, which at M = 16 is that
+// 13.7 (13.6 - 13.8) against 11.8 (11.7 - 11.9), so from N = 8192 (kGluWideN) more than 8 activation rows take
+// TILES = 4 (level at M = 8: 11.9 / 11.8). The two-launch form (the ungated GEMM to [M, 2F], then swiglu_bf16.hip)
+// took 18.3 - 19.5 us at every point: the gated launch (11.7 - 12.7) wins each by about 7 us.
+//
 // Registers (gfx950 compile, -Rpass-analysis=kernel-resource-usage; 0 scratch bytes in every
 // instantiation; VGPRs / AGPRs): skinny_w8_mfma<1> 90 / 8, <2> 107 / 24, <4> 77 / 44 (U = 2);
 // skinny_w8_valu<MR, ROWS>: <1,2> 72 / 0, <2,2> 92 / 0, <4,2> 130 / 0, <8,2> 120 / 0 (U = 1), <1,4> 138 / 0,
@@ -62,6 +74,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kValuMaxM = 2;
+// the gated form's own cut-overs (the GLU paragraph of the header comment)
+constexpr int kGluValuMaxM = 2;
+constexpr int kGluWideN = 8192;  // from here more than 8 activation rows take TILES = 4 (ungated: from N = 16384)
 constexpr int kValuMaxN = 16384;  // the 32000-row LM head streams faster on the MFMA form at every M
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -125,8 +140,19 @@ __device__ __forceinline__ void epilogue_store(const W8Args& a, int m, int n, fl
   a.C[m * a.ldc + n] = (__bf16)v;
 }
 
+// GLU (the gated form, kfamd_gemm_nt_skinny_w8_glu*): as in gemm_skinny_bf16.hip, weight rows n (even) and n + 1
+// are gate and up of output column n / 2; each row's scale is applied before its bias, as in the ungated epilogue.
+__device__ __forceinline__ void glu_store(const W8Args& a, int m, int n, float accg, float accu) {
+  float g = accg * (a.alpha * a.wscale[n]), u = accu * (a.alpha * a.wscale[n + 1]);
+  if (a.bias) {
+    g += (float)a.bias[n];
+    u += (float)a.bias[n + 1];
+  }
+  a.C[m * a.ldc + (n >> 1)] = (__bf16)(g / (1.f + __expf(-g)) * u);
+}
+
 // ---- VALU form -------------------------------------------------------------------------------
-template <int MR, int ROWS>
+template <int MR, int ROWS, bool GLU = false>
 __global__ __launch_bounds__(256) void skinny_w8_valu(W8Args a) {
   constexpr int U = MR >= 8 ? 1 : 2;  // 16-B pieces per row in flight per lane (16 * MR activation bytes each)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -181,17 +207,29 @@ __global__ __launch_bounds__(256) void skinny_w8_valu(W8Args a) {
       }
     }
   }
+  if constexpr (GLU) {
+    // ROWS and n0 are even: the wave's rows are ROWS / 2 whole (gate, up) pairs, and with N even a pair is
+    // wholly inside or wholly outside N
 #pragma unroll
-  for (int r = 0; r < ROWS; ++r)
+    for (int r = 0; r < ROWS; r += 2)
 #pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const float s = kfw::wave_sum(acc[r][m]);
-      if (lane == 0 && n0 + r < a.N && m < a.M) epilogue_store(a, m, n0 + r, s);
-    }
+      for (int m = 0; m < MR; ++m) {
+        const float sg = kfw::wave_sum(acc[r][m]), su = kfw::wave_sum(acc[r + 1][m]);
+        if (lane == 0 && n0 + r < a.N && m < a.M) glu_store(a, m, n0 + r, sg, su);
+      }
+  } else {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int m = 0; m < MR; ++m) {
+        const float s = kfw::wave_sum(acc[r][m]);
+        if (lane == 0 && n0 + r < a.N && m < a.M) epilogue_store(a, m, n0 + r, s);
+      }
+  }
 }
 
 // ---- MFMA form -------------------------------------------------------------------------------
-template <int TILES>
+template <int TILES, bool GLU = false>
 __global__ __launch_bounds__(256) void skinny_w8_mfma(W8Args a) {
   constexpr int U = TILES >= 4 ? 2 : 4;  // K chunks (128 elements) in flight per wave
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -262,48 +300,67 @@ __global__ __launch_bounds__(256) void skinny_w8_mfma(W8Args a) {
       red[wave][row >> 3][t][row & 7][m] = (row < 8) ? acc_e[t][i] : acc_o[t][i];
     }
   __syncthreads();
-  for (int e = threadIdx.x; e < TILES * 128; e += 256) {
-    const int wr = e & 7, mm = (e >> 3) & 15, t = e >> 7;
-    const int n = n0 + t * 8 + wr;
-    if (mm >= a.M || n >= a.N) continue;
-    float s = 0.f;
+  if constexpr (GLU) {
+    // an 8-row tile is 4 (gate, up) pairs: a thread sums the waves' partials of both rows of one pair, in the
+    // ungated epilogue's order, then gates
+    for (int e = threadIdx.x; e < TILES * 64; e += 256) {
+      const int pr = e & 3, mm = (e >> 2) & 15, t = e >> 6;
+      const int n = n0 + t * 8 + 2 * pr;
+      if (mm >= a.M || n >= a.N) continue;
+      float sg = 0.f, su = 0.f;
 #pragma unroll
-    for (int wv = 0; wv < 4; ++wv) s += red[wv][0][t][wr][mm] + red[wv][1][t][wr][mm];
-    epilogue_store(a, mm, n, s);
+      for (int wv = 0; wv < 4; ++wv) {
+        sg += red[wv][0][t][2 * pr][mm] + red[wv][1][t][2 * pr][mm];
+        su += red[wv][0][t][2 * pr + 1][mm] + red[wv][1][t][2 * pr + 1][mm];
+      }
+      glu_store(a, mm, n, sg, su);
+    }
+  } else {
+    for (int e = threadIdx.x; e < TILES * 128; e += 256) {
+      const int wr = e & 7, mm = (e >> 3) & 15, t = e >> 7;
+      const int n = n0 + t * 8 + wr;
+      if (mm >= a.M || n >= a.N) continue;
+      float s = 0.f;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) s += red[wv][0][t][wr][mm] + red[wv][1][t][wr][mm];
+      epilogue_store(a, mm, n, s);
+    }
   }
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <int ROWS>
+template <int ROWS, bool GLU>
 void launch_valu(const W8Args& a, int mr, hipStream_t s) {
   const dim3 grid((unsigned)((a.N + 4 * ROWS - 1) / (4 * ROWS))), block(256);
   switch (mr) {
-    case 1: hipLaunchKernelGGL((skinny_w8_valu<1, ROWS>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((skinny_w8_valu<2, ROWS>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((skinny_w8_valu<4, ROWS>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((skinny_w8_valu<8, 2>), dim3((unsigned)((a.N + 7) / 8)), block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((skinny_w8_valu<1, ROWS, GLU>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((skinny_w8_valu<2, ROWS, GLU>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((skinny_w8_valu<4, ROWS, GLU>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((skinny_w8_valu<8, 2, GLU>), dim3((unsigned)((a.N + 7) / 8)), block, 0, s, a); break;
   }
 }
 
-template <int TILES>
+template <int TILES, bool GLU>
 void launch_mfma(const W8Args& a, hipStream_t s) {
-  hipLaunchKernelGGL(skinny_w8_mfma<TILES>, dim3((unsigned)((a.N + 8 * TILES - 1) / (8 * TILES))), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((skinny_w8_mfma<TILES, GLU>), dim3((unsigned)((a.N + 8 * TILES - 1) / (8 * TILES))), dim3(256), 0,
+                     s, a);
 }
 
-}  // namespace
-
-// path: 0 = by M and N (kValuMaxM, kValuMaxN), 1 = VALU (M <= 8), 2 = MFMA. tiles: 0 = by N; else the MFMA form's TILES
-// (1, 2, 4) or the VALU form's weight rows per wave (2, 4; 8 activation rows always take 2).
-extern "C" int kfamd_gemm_nt_skinny_w8_tiles(int path, int tiles, const void* A, const void* codes,
-                                             const float* wscale, void* C, const void* bias, const void* R, int M,
-                                             int N, int K, long long lda, long long ldw, long long ldc,
-                                             long long ldr, float alpha, int act, void* stream) {
+template <bool GLU>
+int w8_launch(int path, int tiles, const void* A, const void* codes, const float* wscale, void* C, const void* bias,
+              const void* R, int M, int N, int K, long long lda, long long ldw, long long ldc, long long ldr,
+              float alpha, int act, void* stream) {
   if (!A || !codes || !wscale || !C || M < 1 || M > 16 || N < 1 || K < 16 || K % 16) return KFAMD_EINVAL;
-  if (act < KFAMD_ACT_NONE || act > KFAMD_ACT_SILU || (R && act != KFAMD_ACT_NONE)) return KFAMD_EINVAL;
-  if (lda < K || ldw < K || ldc < N || (R && ldr < N)) return KFAMD_EINVAL;
+  if (GLU) {
+    if ((N & 1) || ldc < N / 2) return KFAMD_EINVAL;
+  } else {
+    if (act < KFAMD_ACT_NONE || act > KFAMD_ACT_SILU || (R && act != KFAMD_ACT_NONE)) return KFAMD_EINVAL;
+    if (ldc < N || (R && ldr < N)) return KFAMD_EINVAL;
+  }
+  if (lda < K || ldw < K) return KFAMD_EINVAL;
   if (path < 0 || path > 2 || (path == 1 && M > 8)) return KFAMD_EINVAL;
-  const bool valu = path == 1 || (path == 0 && M <= kValuMaxM && N < kValuMaxN);
+  const bool valu = path == 1 || (path == 0 && M <= (GLU ? kGluValuMaxM : kValuMaxM) && N < kValuMaxN);
   if (tiles != 0 && (valu ? (tiles != 2 && tiles != 4) : (tiles != 1 && tiles != 2 && tiles != 4))) return KFAMD_EINVAL;
   if (!al16(A) || !al16(codes) || (lda & 7) || (ldw & 15)) return KFAMD_EALIGN;
   W8Args a;
@@ -322,16 +379,27 @@ extern "C" int kfamd_gemm_nt_skinny_w8_tiles(int path, int tiles, const void* A,
     const int mr = M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8));
     // weight rows per wave: 2 keeps N = 2048 at 256 workgroups; 4 shares the activation pieces wider
     const int rows = tiles ? tiles : (N >= 8192 && mr <= 4 ? 4 : 2);
-    if (rows == 4) launch_valu<4>(a, mr, s);
-    else launch_valu<2>(a, mr, s);
+    if (rows == 4) launch_valu<4, GLU>(a, mr, s);
+    else launch_valu<2, GLU>(a, mr, s);
   } else {
-    const int t = tiles ? tiles : (N >= 16384 ? 4 : (N >= 4096 ? 2 : 1));
-    if (t == 4) launch_mfma<4>(a, s);
-    else if (t == 2) launch_mfma<2>(a, s);
-    else launch_mfma<1>(a, s);
+    const int t = tiles ? tiles : (N >= 16384 || (GLU && N >= kGluWideN && M > 8) ? 4 : (N >= 4096 ? 2 : 1));
+    if (t == 4) launch_mfma<4, GLU>(a, s);
+    else if (t == 2) launch_mfma<2, GLU>(a, s);
+    else launch_mfma<1, GLU>(a, s);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
+}  // namespace
+
+// path: 0 = by M and N (kValuMaxM, kValuMaxN), 1 = VALU (M <= 8), 2 = MFMA. tiles: 0 = by N; else the MFMA form's TILES
+// (1, 2, 4) or the VALU form's weight rows per wave (2, 4; 8 activation rows always take 2).
+extern "C" int kfamd_gemm_nt_skinny_w8_tiles(int path, int tiles, const void* A, const void* codes,
+                                             const float* wscale, void* C, const void* bias, const void* R, int M,
+                                             int N, int K, long long lda, long long ldw, long long ldc,
+                                             long long ldr, float alpha, int act, void* stream) {
+  return w8_launch<false>(path, tiles, A, codes, wscale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, alpha, act, stream);
 }
 
 extern "C" int kfamd_gemm_nt_skinny_w8_path(int path, const void* A, const void* codes, const float* wscale, void* C,
@@ -347,4 +415,25 @@ extern "C" int kfamd_gemm_nt_skinny_w8(const void* A, const void* codes, const f
                                        long long ldr, float alpha, int act, void* stream) {
   return kfamd_gemm_nt_skinny_w8_tiles(0, 0, A, codes, wscale, C, bias, R, M, N, K, lda, ldw, ldc, ldr, alpha, act,
                                        stream);
+}
+
+// ---- gated (SwiGLU) entry points: codes [N = 2F][K] interleaved (row 2j gate, 2j + 1 up), C [M][F] ------------
+extern "C" int kfamd_gemm_nt_skinny_w8_glu_tiles(int path, int tiles, const void* A, const void* codes,
+                                                 const float* wscale, void* C, const void* bias, int M, int N, int K,
+                                                 long long lda, long long ldw, long long ldc, float alpha,
+                                                 void* stream) {
+  return w8_launch<true>(path, tiles, A, codes, wscale, C, bias, nullptr, M, N, K, lda, ldw, ldc, 0, alpha,
+                         KFAMD_ACT_NONE, stream);
+}
+
+extern "C" int kfamd_gemm_nt_skinny_w8_glu_path(int path, const void* A, const void* codes, const float* wscale,
+                                                void* C, const void* bias, int M, int N, int K, long long lda,
+                                                long long ldw, long long ldc, float alpha, void* stream) {
+  return kfamd_gemm_nt_skinny_w8_glu_tiles(path, 0, A, codes, wscale, C, bias, M, N, K, lda, ldw, ldc, alpha, stream);
+}
+
+extern "C" int kfamd_gemm_nt_skinny_w8_glu(const void* A, const void* codes, const float* wscale, void* C,
+                                           const void* bias, int M, int N, int K, long long lda, long long ldw,
+                                           long long ldc, float alpha, void* stream) {
+  return kfamd_gemm_nt_skinny_w8_glu_tiles(0, 0, A, codes, wscale, C, bias, M, N, K, lda, ldw, ldc, alpha, stream);
 }

@@ -385,6 +385,46 @@ int kfamd_gemm_nt_skinny_w8_tiles(int path, int tiles, const void* A, const void
                                   void* C, const void* bias, const void* R, int M, int N, int K, long long lda,
                                   long long ldw, long long ldc, long long ldr, float alpha, int act, void* stream);
 
+// ---- SwiGLU (the rule: kubeflow_rm_amd/ops/swiglu.py) ------------------------------------------------
+// A gated up-projection weight is W [N = 2F][K] with INTERLEAVED rows: row 2j is gate j, row 2j + 1 is up j
+// (bias [2F] and, on 8-bit weights, wscale [2F] in the same order). With z = alpha * A . W^T + bias (8-bit:
+// alpha * wscale[n] * (A . codes^T) + bias[n], the scale before the bias as above), the output is
+//   C[m][j] = silu(z[m][2j]) * z[m][2j + 1],  silu(v) = v / (1 + exp(-v)),  fp32, rounded once to bf16.
+// Gated weight-streaming GEMM, 1 <= M <= 16 (gemm_skinny_bf16.hip / gemm_skinny_w8.hip with GLU): C [M][F],
+// ldc >= F. No activation code and no residual. N is the WEIGHT's row count 2F and must be even (KFAMD_EINVAL);
+// the other shape / alignment rules, return codes, `path` (0 = by M and N, 1 = VALU with M <= 8, 2 = MFMA) and
+// `tiles` (0 = by N, else the MFMA form's 8-row tiles per workgroup 1 / 2 / 4 = 4 / 8 / 16 pairs, or the VALU
+// form's weight rows per wave 2 / 4 = 1 / 2 pairs) are the ungated kernels'.
+int kfamd_gemm_nt_skinny_bf16_glu(const void* A, const void* W, void* C, const void* bias, int M, int N, int K,
+                                  long long lda, long long ldw, long long ldc, float alpha, void* stream);
+int kfamd_gemm_nt_skinny_bf16_glu_path(int path, const void* A, const void* W, void* C, const void* bias, int M, int N,
+                                       int K, long long lda, long long ldw, long long ldc, float alpha, void* stream);
+int kfamd_gemm_nt_skinny_bf16_glu_tiles(int path, int tiles, const void* A, const void* W, void* C, const void* bias,
+                                        int M, int N, int K, long long lda, long long ldw, long long ldc, float alpha,
+                                        void* stream);
+int kfamd_gemm_nt_skinny_w8_glu(const void* A, const void* codes, const float* wscale, void* C, const void* bias, int M,
+                                int N, int K, long long lda, long long ldw, long long ldc, float alpha, void* stream);
+int kfamd_gemm_nt_skinny_w8_glu_path(int path, const void* A, const void* codes, const float* wscale, void* C,
+                                     const void* bias, int M, int N, int K, long long lda, long long ldw, long long ldc,
+                                     float alpha, void* stream);
+int kfamd_gemm_nt_skinny_w8_glu_tiles(int path, int tiles, const void* A, const void* codes, const float* wscale,
+                                      void* C, const void* bias, int M, int N, int K, long long lda, long long ldw,
+                                      long long ldc, float alpha, void* stream);
+// The gate as its own pass (swiglu_bf16.hip), any row count: z [rows][2F] (row stride ldz >= 2F) -> h [rows][F]
+// (ldh >= F); backward dh [rows][F] (lddh), z -> dz [rows][2F] (lddz): dz[2j] = dh u s (1 + g (1 - s)),
+// dz[2j + 1] = dh silu(g), s = 1 / (1 + exp(-g)). 16-B loads and stores when F % 8 == 0, every stride % 8 == 0
+// and the bases are 16-B aligned; a scalar path otherwise (never KFAMD_EALIGN). Padding between rows is not touched.
+int kfamd_swiglu_fwd_bf16(const void* z, void* h, long long rows, int F, long long ldz, long long ldh, void* stream);
+int kfamd_swiglu_bwd_bf16(const void* dh, const void* z, void* dz, long long rows, int F, long long lddh, long long ldz,
+                          long long lddz, void* stream);
+
+// RMSNorm backward (layernorm_bf16.hip, the LayerNorm backward's kernels with mean = 0, no c2 term, no dbeta):
+// dx = rstd * (gamma dy - xhat * mean(gamma dy xhat)) (+ dres, optional, not aliasing dx), dgamma = column sums of
+// dy * xhat (fp32, or bf16 when dgb_bf16; optional), xhat = x * rstd, rstd from kfamd_rmsnorm_fwd_bf16. workspace:
+// kfamd_layernorm_bwd_workspace bytes (required with dgamma).
+int kfamd_rmsnorm_bwd_bf16(const void* dy, const void* dres, const void* x, const void* gamma, const float* rstd,
+                           void* dx, void* dgamma, int dgb_bf16, float* workspace, int rows, int hidden, void* stream);
+
 // Token sampling (sample_bf16.hip): one token per row of bf16 logits [B][V] (row stride ld elements, the
 // vocabulary contiguous, 2-byte alignment only; 1 <= V <= 2^20; -inf allowed, NaN / an all -inf row out of
 // contract). Tokens are ordered by logit descending, equal logits by index ascending.

@@ -255,7 +255,9 @@ __global__ __launch_bounds__(256) void norm_fwd_block(const __bf16* __restrict__
 }
 
 // ---- backward: dx ---------------------------------------------------------------------------
-template <int VPL, int W = 8>  // W as in norm_fwd_wave
+// RMS (here and in the kernels below): the RMSNorm backward, i.e. the same structure with mean = 0 (`mean` is
+// not read), without the c2 term (no mean was subtracted) and without dbeta
+template <int VPL, int W = 8, bool RMS = false>  // W as in norm_fwd_wave
 __global__ __launch_bounds__(256) void ln_bwd_dx_wave(const __bf16* __restrict__ dy,
                                                      const __bf16* __restrict__ x,
                                                      const __bf16* __restrict__ gamma,
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_wave(const __bf16* __restrict__
   const vec_t* xr = reinterpret_cast<const vec_t*>(x + (long long)row * H);
   const vec_t* dyr = reinterpret_cast<const vec_t*>(dy + (long long)row * H);
   const vec_t* g8 = reinterpret_cast<const vec_t*>(gamma);
-  const float mu = mean[row], rs = rstd[row];
+  const float mu = RMS ? 0.f : mean[row], rs = rstd[row];
   vec_t* dxr = reinterpret_cast<vec_t*>(dx + (long long)row * H);
   // dres: the residual stream's own gradient, added in the store (one pass instead of an add kernel)
   const vec_t* rr = dres ? reinterpret_cast<const vec_t*>(dres + (long long)row * H) : nullptr;
@@ -287,10 +289,10 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_wave(const __bf16* __restrict__
         xh[j][e] = ((float)xv[e] - mu) * rs;
         gd[j][e] = (float)dv[e] * (float)gv[e];
         s1 += gd[j][e] * xh[j][e];
-        s2 += gd[j][e];
+        if (!RMS) s2 += gd[j][e];
       }
     }
-    const float c1 = wave_sum(s1) * (1.f / H), c2 = wave_sum(s2) * (1.f / H);
+    const float c1 = wave_sum(s1) * (1.f / H), c2 = RMS ? 0.f : wave_sum(s2) * (1.f / H);
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       vec_t o;
@@ -322,10 +324,10 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_wave(const __bf16* __restrict__
       for (int e = 0; e < W; ++e) {
         const float xh = ((float)xv[j][e] - mu) * rs, gd = (float)dv[j][e] * (float)gv[e];
         s1 += gd * xh;
-        s2 += gd;
+        if (!RMS) s2 += gd;
       }
     }
-    const float c1 = wave_sum(s1) * (1.f / H), c2 = wave_sum(s2) * (1.f / H);
+    const float c1 = wave_sum(s1) * (1.f / H), c2 = RMS ? 0.f : wave_sum(s2) * (1.f / H);
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       asm volatile("" : "+v"(xv[j]));  // widen again below rather than keep pass one's fp32 values
@@ -347,6 +349,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_wave(const __bf16* __restrict__
   }
 }
 
+template <bool RMS = false>
 __global__ __launch_bounds__(256) void ln_bwd_dx_block(const __bf16* __restrict__ dy,
                                                       const __bf16* __restrict__ x,
                                                       const __bf16* __restrict__ gamma,
@@ -356,17 +359,17 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_block(const __bf16* __restrict_
                                                       __bf16* __restrict__ dx, int hidden) {
   __shared__ float red[4];
   const long long row = blockIdx.x;
-  const float mu = mean[row], rs = rstd[row];
+  const float mu = RMS ? 0.f : mean[row], rs = rstd[row];
   const __bf16* xr = x + row * hidden;
   const __bf16* dyr = dy + row * hidden;
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < hidden; i += 256) {
     const float xh = ((float)xr[i] - mu) * rs, g = (float)dyr[i] * (float)gamma[i];
     s1 += g * xh;
-    s2 += g;
+    if (!RMS) s2 += g;
   }
   const float c1 = block_sum(s1, red) / hidden;
-  const float c2 = block_sum(s2, red) / hidden;
+  const float c2 = RMS ? 0.f : block_sum(s2, red) / hidden;
   __bf16* dxr = dx + row * hidden;
   for (int i = threadIdx.x; i < hidden; i += 256) {
     const float xh = ((float)xr[i] - mu) * rs, g = (float)dyr[i] * (float)gamma[i];
@@ -385,7 +388,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dx_block(const __bf16* __restrict_
 // 2 x VPL x W registers beside the row.
 constexpr int kFusedWaves = 8, kFusedBlocks = 256;
 
-template <int VPL, int W>
+template <int VPL, int W, bool RMS = false>
 __global__ __launch_bounds__(64 * kFusedWaves) void ln_bwd_fused(const __bf16* __restrict__ dy,
                                                                 const __bf16* __restrict__ x,
                                                                 const __bf16* __restrict__ gamma,
@@ -409,7 +412,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void ln_bwd_fused(const __bf16* _
   for (int row = r0 + wv; row < r1; row += kFusedWaves) {
     const vec_t* xr = reinterpret_cast<const vec_t*>(x + (long long)row * H);
     const vec_t* dyr = reinterpret_cast<const vec_t*>(dy + (long long)row * H);
-    const float mu = mean[row], rs = rstd[row];
+    const float mu = RMS ? 0.f : mean[row], rs = rstd[row];
     float xh[VPL][W], gd[VPL][W];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -421,12 +424,14 @@ __global__ __launch_bounds__(64 * kFusedWaves) void ln_bwd_fused(const __bf16* _
         xh[j][e] = ((float)xv[e] - mu) * rs;
         gd[j][e] = d * (float)gv[e];
         s1 += gd[j][e] * xh[j][e];
-        s2 += gd[j][e];
         ag[j][e] = fmaf(d, xh[j][e], ag[j][e]);
-        ab[j][e] += d;
+        if (!RMS) {
+          s2 += gd[j][e];
+          ab[j][e] += d;
+        }
       }
     }
-    const float c1 = wave_sum(s1) * (1.f / H), c2 = wave_sum(s2) * (1.f / H);
+    const float c1 = wave_sum(s1) * (1.f / H), c2 = RMS ? 0.f : wave_sum(s2) * (1.f / H);
     vec_t* dxr = reinterpret_cast<vec_t*>(dx + (long long)row * H);
     const vec_t* rr = dres ? reinterpret_cast<const vec_t*>(dres + (long long)row * H) : nullptr;
 #pragma unroll
@@ -444,7 +449,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void ln_bwd_fused(const __bf16* _
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
 #pragma unroll
-    for (int which = 0; which < 2; ++which) {
+    for (int which = 0; which < (RMS ? 1 : 2); ++which) {  // RMS: no dbeta partials (the finalize does not read them)
 #pragma unroll
       for (int e = 0; e < W; ++e) red[wv][lane * W + e] = which ? ab[j][e] : ag[j][e];
       __syncthreads();
@@ -464,6 +469,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void ln_bwd_fused(const __bf16* _
 // wave reads 64 consecutive bf16 (128 B) of one row per step; partials land in ws[chunk][col].
 constexpr int kColsPerBlock = 64, kRowLanes = 4, kRowsPerChunk = 64;
 
+template <bool RMS = false>
 __global__ __launch_bounds__(256) void ln_bwd_dgb_partial(const __bf16* __restrict__ dy,
                                                          const __bf16* __restrict__ x,
                                                          const float* __restrict__ mean,
@@ -478,7 +484,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dgb_partial(const __bf16* __restri
   if (c < hidden) {
     for (int r = r0 + rl; r < r1; r += kRowLanes) {
       const float d = (float)dy[(long long)r * hidden + c];
-      const float xh = ((float)x[(long long)r * hidden + c] - mean[r]) * rstd[r];
+      const float xh = ((float)x[(long long)r * hidden + c] - (RMS ? 0.f : mean[r])) * rstd[r];
       dg += d * xh;
       db += d;
     }
@@ -495,7 +501,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dgb_partial(const __bf16* __restri
     }
     const long long nch = gridDim.y;
     ws[(long long)chunk * hidden + c] = tg;
-    ws[(nch + chunk) * (long long)hidden + c] = tb;
+    if (!RMS) ws[(nch + chunk) * (long long)hidden + c] = tb;
   }
 }
 
@@ -514,7 +520,7 @@ __global__ __launch_bounds__(256) void ln_bwd_dgb_finalize(const float* __restri
 #pragma unroll 8
     for (int k = kl; k < nchunks; k += kRowLanes) {
       tg += ws[(long long)k * hidden + c];
-      tb += ws[(long long)(nchunks + k) * hidden + c];
+      if (dbeta) tb += ws[(long long)(nchunks + k) * hidden + c];  // absent for RMSNorm: those partials are not written
     }
   }
   sg[kl][cl] = tg;
@@ -647,10 +653,11 @@ extern "C" long long kfamd_layernorm_bwd_workspace(int rows, int hidden) {
 // dgamma / dbeta: fp32, or bf16 (the parameter dtype) when dgb_bf16; sums accumulate in fp32 either way.
 // dres (optional, same layout as dx): dx = dres + the LayerNorm input gradient — the pre-norm
 // residual stream's two gradient contributions summed in the dx store.
-extern "C" int kfamd_layernorm_bwd_bf16_v3(const void* dy, const void* dres, const void* x, const void* gamma,
-                                           const float* mean, const float* rstd, void* dx, void* dgamma, void* dbeta,
-                                           int dgb_bf16, float* workspace, int rows, int hidden, void* stream) {
-  if (!dy || !x || !gamma || !mean || !rstd || !dx || rows <= 0 || hidden <= 0) return KFAMD_EINVAL;
+namespace {
+template <bool RMS>
+int norm_bwd(const void* dy, const void* dres, const void* x, const void* gamma, const float* mean, const float* rstd,
+             void* dx, void* dgamma, void* dbeta, int dgb_bf16, float* workspace, int rows, int hidden, void* stream) {
+  if (!dy || !x || !gamma || (!RMS && !mean) || !rstd || !dx || rows <= 0 || hidden <= 0) return KFAMD_EINVAL;
   if (dres == dx) return KFAMD_EINVAL;
   if ((dgamma || dbeta) && !workspace) return KFAMD_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -676,7 +683,7 @@ extern "C" int kfamd_layernorm_bwd_bf16_v3(const void* dy, const void* dres, con
     const int key = vec ? vpl : 100 + v4;
     switch (key) {
 #define KFAMD_LN_FUSED(K, V, WW) \
-  case K: hipLaunchKernelGGL((ln_bwd_fused<V, WW>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, workspace, rows, rpb); break;
+  case K: hipLaunchKernelGGL((ln_bwd_fused<V, WW, RMS>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, workspace, rows, rpb); break;
       KFAMD_LN_FUSED(1, 1, 8) KFAMD_LN_FUSED(2, 2, 8) KFAMD_LN_FUSED(3, 3, 8) KFAMD_LN_FUSED(4, 4, 8)
       KFAMD_LN_FUSED(101, 1, 4) KFAMD_LN_FUSED(103, 3, 4) KFAMD_LN_FUSED(105, 5, 4)
 #undef KFAMD_LN_FUSED
@@ -691,30 +698,48 @@ extern "C" int kfamd_layernorm_bwd_bf16_v3(const void* dy, const void* dres, con
     dim3 grid((rows + 3) / 4), block(256);
     switch (vpl) {
 #define KFAMD_LN_BWD_CASE(V) \
-  case V: hipLaunchKernelGGL((ln_bwd_dx_wave<V>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
+  case V: hipLaunchKernelGGL((ln_bwd_dx_wave<V, 8, RMS>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
       KFAMD_FOR_EACH_VPL(KFAMD_LN_BWD_CASE)
 #undef KFAMD_LN_BWD_CASE
     }
   } else if (vec4) {
     dim3 grid((rows + 3) / 4), block(256);
     switch (v4) {
-      case 1: hipLaunchKernelGGL((ln_bwd_dx_wave<1, 4>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
-      case 3: hipLaunchKernelGGL((ln_bwd_dx_wave<3, 4>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
-      case 5: hipLaunchKernelGGL((ln_bwd_dx_wave<5, 4>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
+      case 1: hipLaunchKernelGGL((ln_bwd_dx_wave<1, 4, RMS>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
+      case 3: hipLaunchKernelGGL((ln_bwd_dx_wave<3, 4, RMS>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
+      case 5: hipLaunchKernelGGL((ln_bwd_dx_wave<5, 4, RMS>), grid, block, 0, s, dyp, xp, gp, mean, rstd, rp, dxp, rows); break;
     }
   } else {
-    hipLaunchKernelGGL(ln_bwd_dx_block, dim3(rows), dim3(256), 0, s, dyp, xp, gp, mean, rstd, rp, dxp, hidden);
+    hipLaunchKernelGGL(ln_bwd_dx_block<RMS>, dim3(rows), dim3(256), 0, s, dyp, xp, gp, mean, rstd, rp, dxp, hidden);
   }
   if (dgamma || dbeta) {
     const int nch = (rows + kRowsPerChunk - 1) / kRowsPerChunk;
     dim3 grid((hidden + kColsPerBlock - 1) / kColsPerBlock, nch);
-    hipLaunchKernelGGL(ln_bwd_dgb_partial, grid, dim3(256), 0, s, dyp, xp, mean, rstd, workspace, rows, hidden);
+    hipLaunchKernelGGL(ln_bwd_dgb_partial<RMS>, grid, dim3(256), 0, s, dyp, xp, mean, rstd, workspace, rows, hidden);
     const dim3 fg((hidden + kColsPerBlock - 1) / kColsPerBlock);
     if (dgb_bf16) hipLaunchKernelGGL(ln_bwd_dgb_finalize<true>, fg, dim3(256), 0, s, workspace, dgamma, dbeta, nch, hidden);
     else hipLaunchKernelGGL(ln_bwd_dgb_finalize<false>, fg, dim3(256), 0, s, workspace, dgamma, dbeta, nch, hidden);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+}  // namespace
+
+extern "C" int kfamd_layernorm_bwd_bf16_v3(const void* dy, const void* dres, const void* x, const void* gamma,
+                                           const float* mean, const float* rstd, void* dx, void* dgamma, void* dbeta,
+                                           int dgb_bf16, float* workspace, int rows, int hidden, void* stream) {
+  return norm_bwd<false>(dy, dres, x, gamma, mean, rstd, dx, dgamma, dbeta, dgb_bf16, workspace, rows, hidden, stream);
+}
+
+// RMSNorm backward from the forward's saved rstd: dx = rstd * (gamma dy - xhat * mean(gamma dy xhat)) (+ dres),
+// dgamma = sum over rows of dy * xhat, xhat = x * rstd. The launch policy is the LayerNorm backward's: the fused
+// one-pass kernel where ln_bwd_fused applies, else dx + the column partials; workspace from
+// kfamd_layernorm_bwd_workspace.
+extern "C" int kfamd_rmsnorm_bwd_bf16(const void* dy, const void* dres, const void* x, const void* gamma,
+                                      const float* rstd, void* dx, void* dgamma, int dgb_bf16, float* workspace,
+                                      int rows, int hidden, void* stream) {
+  return norm_bwd<true>(dy, dres, x, gamma, nullptr, rstd, dx, dgamma, nullptr, dgb_bf16, workspace, rows, hidden,
+                        stream);
 }
 
 extern "C" int kfamd_layernorm_bwd_bf16_v2(const void* dy, const void* x, const void* gamma, const float* mean,

@@ -36,12 +36,26 @@ Training rotates inside ``ops.attn_block(rope=...)`` on the fused path and with 
 ``prefill`` / ``decode_step`` / ``extend`` rotate inside their one ``ops.kv_append(..., rope=...)`` per layer, at
 positions read from the device-side ``cache.lens``: K is stored rotated, the step stays capturable and launches
 no more kernels than with learned positions. ``pos="learned"`` (the default) is the model as it was. Not built:
-RMSNorm blocks, SwiGLU, partial rotary, scaled rotary (NTK / YaRN), and a rotation fused into the flash kernel's
-Q / K loads.
+partial rotary, scaled rotary (NTK / YaRN), and a rotation fused into the flash kernel's Q / K loads.
+
+Llama-style blocks: ``GPTConfig(norm="rms", mlp="swiglu")``. ``norm="rms"`` makes ``ln1`` / ``ln2`` / ``ln_f`` RMSNorms
+(a ``weight`` only: no norm bias in ``state_dict()``; ``norm_eps`` defaults to the op's 1e-6) on
+``ops.rms_norm_residual`` / ``kfamd_rmsnorm_fwd_bf16``. ``mlp="swiglu"`` makes ``fc1`` a ``[2 * d_ff, d_model]``
+projection whose rows are interleaved gate / up (the rule is the docstring of ``ops/swiglu.py``;
+``ops.swiglu_interleave`` packs a checkpoint's two matrices) and the MLP ``fc2(silu(gate) * up)``: training and steps of
+more than 16 rows run ``linear -> ops.swiglu -> fc2``, the KV-cache steps of up to 16 rows run the gated
+weight-streaming GEMM (``ops.gemm_nt(act="swiglu")``), one launch as the GELU up-projection has, on the bf16 or the
+``decode_weights()`` copy of ``fc1`` (quantised row by row, so a pair keeps its two scales). Everything above (GQA,
+rotary, FP8 cache / weights, graphs, the fused sampler, drafting, chunked prefill, tensor parallelism: a contiguous
+column shard of ``fc1`` keeps whole pairs) takes the configured norm and MLP. The defaults ``norm="layer"``,
+``mlp="gelu"`` are the model as it was: same parameters, same state dict, same launches. Not built: bias-free linears
+(the biases stay, zero-initialised: a bias-free checkpoint loads with ``strict=False`` and leaves them at zero), GEGLU
+or any other gate, and a GLU epilogue in the large (more than 16 rows) GEMM.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from dataclasses import dataclass
 
 import torch
@@ -64,8 +78,17 @@ class GPTConfig:
     n_kv_heads: int | None = None  # K / V heads (grouped-query attention); None: n_heads
     pos: str = "learned"  # "learned": a [max_seq, d_model] table added to the embedding; "rope": rotary q / k
     rope_theta: float = 10000.0  # the rotary base (pos="rope")
+    norm: str = "layer"  # "layer": LayerNorm (weight + bias); "rms": RMSNorm (weight only)
+    mlp: str = "gelu"  # "gelu": fc2(gelu_tanh(fc1 x)); "swiglu": fc1 [2 d_ff, d_model] interleaved gate / up (ops/swiglu.py)
+    norm_eps: float | None = None  # None: the ops' defaults, 1e-5 (LayerNorm) / 1e-6 (RMSNorm)
 
     def __post_init__(self):
+        if self.norm not in ("layer", "rms"):
+            raise ValueError(f'norm={self.norm!r}: "layer" or "rms" expected')
+        if self.mlp not in ("gelu", "swiglu"):
+            raise ValueError(f'mlp={self.mlp!r}: "gelu" or "swiglu" expected')
+        if self.norm_eps is not None and not self.norm_eps > 0:
+            raise ValueError(f"norm_eps={self.norm_eps!r}: None or a positive number expected")
         if self.pos not in ("learned", "rope"):
             raise ValueError(f'pos={self.pos!r}: "learned" or "rope" expected')
         if self.pos == "rope" and (self.d_model // self.n_heads) % 2:
@@ -80,6 +103,10 @@ class GPTConfig:
     @property
     def kv_heads(self) -> int:
         return self.n_heads if self.n_kv_heads is None else self.n_kv_heads
+
+    @property
+    def eps(self) -> float:
+        return self.norm_eps if self.norm_eps is not None else (1e-6 if self.norm == "rms" else 1e-5)
 
 
 CONFIGS = {
@@ -107,13 +134,14 @@ def _cross_entropy(logits, targets):
 
 
 class LayerNorm(torch.nn.Module):
-    def __init__(self, d, dtype, device=None):
+    def __init__(self, d, dtype, device=None, eps: float = 1e-5):
         super().__init__()
+        self.eps = eps
         self.weight = torch.nn.Parameter(torch.ones(d, dtype=dtype, device=device))
         self.bias = torch.nn.Parameter(torch.zeros(d, dtype=dtype, device=device))
 
     def forward(self, x):
-        return _layer_norm(x, self.weight, self.bias)
+        return _layer_norm(x, self.weight, self.bias, self.eps)
 
     def with_residual(self, x):
         """(LayerNorm(x), r) with r = x for the block's residual add: on the HIP path the two gradient
@@ -121,8 +149,46 @@ class LayerNorm(torch.nn.Module):
         if x.is_cuda:
             from kubeflow_rm_amd import ops
             if ops.native_enabled():
-                return ops.layer_norm_residual(x, self.weight, self.bias)
+                return ops.layer_norm_residual(x, self.weight, self.bias, self.eps)
         return self(x), x
+
+    def fwd(self, x):
+        """The no-grad forward of the KV-cache steps on the HIP kernel (GPU, bf16)."""
+        return ops.layer_norm_fwd(x, self.weight, self.bias, self.eps)[0]
+
+
+def _rms_norm_torch(x, w, eps):
+    xf = x.float()
+    return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()).to(x.dtype)
+
+
+class RMSNorm(torch.nn.Module):
+    """``GPTConfig(norm="rms")``: y = x * rsqrt(mean(x^2) + eps) * weight. A ``weight`` only (no ``bias`` key in the
+    state dict); the same GPU / CPU pattern as ``LayerNorm``."""
+
+    def __init__(self, d, dtype, device=None, eps: float = 1e-6):
+        super().__init__()
+        self.eps = eps
+        self.weight = torch.nn.Parameter(torch.ones(d, dtype=dtype, device=device))
+
+    def forward(self, x):
+        if x.is_cuda and ops.native_enabled():
+            return ops.rms_norm(x, self.weight, self.eps)
+        return _rms_norm_torch(x, self.weight, self.eps)
+
+    def with_residual(self, x):
+        """(RMSNorm(x), r) with r = x for the block's residual add, as ``LayerNorm.with_residual``."""
+        if x.is_cuda and ops.native_enabled():
+            return ops.rms_norm_residual(x, self.weight, self.eps)
+        return self(x), x
+
+    def fwd(self, x):
+        return ops.rms_norm_fwd(x, self.weight, self.eps)[0]
+
+
+def Norm(cfg: "GPTConfig", device=None) -> torch.nn.Module:
+    """The configured norm over d_model (``ln1`` / ``ln2`` / ``ln_f``): ``LayerNorm`` or ``RMSNorm``."""
+    return (RMSNorm if cfg.norm == "rms" else LayerNorm)(cfg.d_model, cfg.dtype, device, cfg.eps)
 
 
 def _qkv_shard(cfg: GPTConfig, tp: int, rank: int, seed: int, device) -> torch.Tensor:
@@ -149,7 +215,7 @@ class Block(torch.nn.Module):
         # K / V heads of this rank; fewer than local_heads: grouped-query attention (single rank only)
         self.local_kv_heads = self.local_heads if cfg.kv_heads == cfg.n_heads else cfg.kv_heads
         seed = 1000 * (layer + 1)
-        self.ln1 = LayerNorm(cfg.d_model, cfg.dtype, device)
+        self.ln1 = Norm(cfg, device)
         # fused QKV, column-parallel: each rank owns local_heads of q, k and v. Grouped-query attention: q | k | v
         # with kv_heads heads of k and of v ((n_heads + 2 kv_heads) * head_dim features; 3 * d_model without it)
         qkv_out = (3 * cfg.d_model if cfg.kv_heads == cfg.n_heads  # seeded as a (3 d_model, d_model) matrix, as ever
@@ -162,9 +228,13 @@ class Block(torch.nn.Module):
             with torch.no_grad():
                 self.qkv.weight.copy_(_qkv_shard(cfg, tp, tpl._rank(tp_group), seed + 1, device))
         self.proj = tpl.RowParallelLinear(cfg.d_model, cfg.d_model, group=tp_group, dtype=cfg.dtype, device=device, seed=seed + 2)
-        self.ln2 = LayerNorm(cfg.d_model, cfg.dtype, device)
-        self.fc1 = tpl.ColumnParallelLinear(cfg.d_model, cfg.d_ff, act="gelu_tanh", group=tp_group, dtype=cfg.dtype,
-                                            device=device, seed=seed + 3)
+        self.ln2 = Norm(cfg, device)
+        # mlp="swiglu": 2 * d_ff features, interleaved gate / up rows (ops/swiglu.py), gated after the projection; a
+        # contiguous column shard keeps whole pairs, so the tensor-parallel layers need nothing beyond the width
+        self.swiglu = cfg.mlp == "swiglu"
+        self.fc1 = tpl.ColumnParallelLinear(cfg.d_model, (2 if self.swiglu else 1) * cfg.d_ff,
+                                            act="none" if self.swiglu else "gelu_tanh", group=tp_group,
+                                            dtype=cfg.dtype, device=device, seed=seed + 3)
         self.fc2 = tpl.RowParallelLinear(cfg.d_ff, cfg.d_model, group=tp_group, dtype=cfg.dtype, device=device, seed=seed + 4)
 
     def _attention_gqa(self, x, residual, rope=None):
@@ -214,6 +284,8 @@ class Block(torch.nn.Module):
         return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
 
     def mlp(self, h, residual):
+        if self.swiglu:  # linear -> gate (ops.swiglu: the elementwise kernels and their backward) -> fc2 (+ residual)
+            return self.fc2(ops.swiglu(self.fc1(h)), residual=residual)
         # without TP, fc1 + fc2 are one autograd node on the HIP path (ops.mlp): fc2's dgrad applies
         # fc1's gelu backward in its GEMM epilogue
         if h.is_cuda and ops.native_enabled() and not tpl._collective(self.tp_group):
@@ -252,15 +324,20 @@ def _sample(logits, temperature, top_k, generator):
 
 _LINEARS = ("qkv", "proj", "fc1", "fc2")
 
-
 class DecodeWeights:
     """8-bit copies of a ``GPT``'s projection weights for the KV-cache steps (``GPT.decode_weights``):
-    ``blocks[i]`` maps "qkv" / "proj" / "fc1" / "fc2" to an ``ops.QuantizedWeight``, ``head`` is the
+    ``blocks[i]`` maps "qkv" / "proj" / "fc1" / "fc2" to an ``ops.QuantizedWeight`` (to the model's own bf16 weight
+    for a matrix whose inner dimension is no multiple of 16, which the 8-bit kernel does not take), ``head`` is the
     quantised LM head (the tied embedding; the embedding gather itself keeps the model's ``tok``). The
-    biases are the model's own. Plain tensors: neither parameters nor buffers."""
+    biases are the model's own. ``unquantized`` names the matrices left in bf16 ("blocks.0.fc2", ...; empty when all
+    were quantised). Plain tensors: neither parameters nor buffers."""
 
     def __init__(self, blocks: list, head, key: tuple):
         self.blocks, self.head, self._key = blocks, head, key
+        self.unquantized = [f"blocks.{i}.{n}" for i, b in enumerate(blocks) for n in _LINEARS
+                            if not isinstance(b[n], ops.QuantizedWeight)]
+        if not isinstance(head, ops.QuantizedWeight):
+            self.unquantized.append("head")
 
     def matrices(self) -> list:
         return [b[n] for b in self.blocks for n in _LINEARS] + [self.head]
@@ -327,7 +404,7 @@ class GPT(torch.nn.Module):
             self.pos = torch.nn.Parameter(pos.to(dtype=cfg.dtype, device=device))
             self.register_buffer("rope_table", None, persistent=False)
         self.blocks = torch.nn.ModuleList([Block(cfg, i, tp_group, device) for i in range(cfg.n_layers)])
-        self.ln_f = LayerNorm(cfg.d_model, cfg.dtype, device)
+        self.ln_f = Norm(cfg, device)
 
     def forward(self, idx, targets=None):
         B, T = idx.shape
@@ -398,7 +475,7 @@ class GPT(torch.nn.Module):
             h, hkv, hd = blk.local_heads, blk.local_kv_heads, c.head_dim
             if native:
                 x2 = x.reshape(B * T, c.d_model)
-                y = ops.layer_norm_fwd(x2, blk.ln1.weight, blk.ln1.bias)[0]
+                y = blk.ln1.fwd(x2)
                 qkv = ops.gemm_nt(y, blk.qkv.weight, bias=blk.qkv.bias).view(B, T, (h + 2 * hkv) * hd)
                 ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
                 if hkv == h:
@@ -407,8 +484,7 @@ class GPT(torch.nn.Module):
                     q, k, v = self._split_gqa(qkv, h, hkv, hd)
                     a = ops.flash_attention(q, k, v, causal=True).transpose(1, 2).reshape(B * T, h * hd)
                 x2 = ops.gemm_nt(a, blk.proj.weight, bias=blk.proj.bias, residual=x2)
-                y = ops.layer_norm_fwd(x2, blk.ln2.weight, blk.ln2.bias)[0]
-                y = ops.gemm_nt(y, blk.fc1.weight, bias=blk.fc1.bias, act=blk.fc1.act)
+                y = self._fc1(self._auto, blk.ln2.fwd(x2), blk.fc1.weight, blk)  # "auto" like its other linears
                 x = ops.gemm_nt(y, blk.fc2.weight, bias=blk.fc2.bias, residual=x2).view(B, T, c.d_model)
             else:
                 qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
@@ -416,12 +492,12 @@ class GPT(torch.nn.Module):
                 q, k, v = self._split_gqa(qkv, h, hkv, hd)
                 a = F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
                 x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
-                y = F.gelu(F.linear(blk.ln2(x), blk.fc1.weight, blk.fc1.bias), approximate="tanh")
+                y = self._fc1_torch(blk.ln2(x), blk.fc1.weight, blk)
                 x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
         cache.advance(T)
         last = x[:, -1]  # the LM head of the last position only
         if native:
-            last = ops.layer_norm_fwd(last.contiguous(), self.ln_f.weight, self.ln_f.bias)[0]
+            last = self.ln_f.fwd(last.contiguous())
             return ops.gemm_nt(last, self.tok)  # M = B rows: auto routes it as the parent commit did
         return F.linear(self.ln_f(last), self.tok)
 
@@ -445,12 +521,33 @@ class GPT(torch.nn.Module):
         # more than 16 rows (extend with B * T > 16): the "auto" route, as prefill
         return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual)
 
+    def _fc1(self, lin, y, w, blk):
+        """The up-projection and its activation on the HIP kernels, ``lin`` being ``_skinny`` or ``_auto``. GELU: the
+        GEMM's epilogue on either route. SwiGLU: on the weight-streaming route the gated GEMM, one launch as GELU has
+        (it won or tied the two-launch form at every measured M, weight format and d_ff: profiles/glu/README.md);
+        on the "auto" route (more than 16 rows, and every prefill) the GEMM to [rows, 2 d_ff], then the elementwise
+        gate kernel."""
+        if not blk.swiglu:
+            return lin(y, w, blk.fc1.bias, act=blk.fc1.act)
+        if lin == self._skinny:
+            return lin(y, w, blk.fc1.bias, act="swiglu")
+        return ops.swiglu(lin(y, w, blk.fc1.bias))
+
+    @staticmethod
+    def _fc1_torch(y, w, blk):
+        """The same on torch ops (CPU tensors / ops.torch_reference())."""
+        z = _flinear(y, w, blk.fc1.bias)
+        return ops.swiglu(z) if blk.swiglu else F.gelu(z, approximate="tanh")
+
     # ---- 8-bit decode weights ---------------------------------------------------------------------
     def decode_weights(self, dtype: torch.dtype = torch.float8_e4m3fn) -> DecodeWeights:
         """8-bit copies (``ops.quantize_weight``: e4m3fn codes + one fp32 scale per output row) of every
         block's qkv / proj / fc1 / fc2 weight and of the LM head, for ``decode_step`` / ``extend`` /
         ``graphed_decode_step`` / ``generate``. With a tensor-parallel group that issues no collective the
-        local shards are quantised. The biases and the embedding gather keep the model's tensors.
+        local shards are quantised. The biases and the embedding gather keep the model's tensors. A matrix whose
+        inner dimension is no multiple of 16 (the 8-bit kernel's contract; e.g. fc2 with d_ff = 344) is not quantised:
+        its entry is the model's bf16 weight and its steps run the bf16 weight-streaming kernel; the call warns, and
+        the result's ``unquantized`` lists them.
 
         The copies are plain tensors, absent from ``state_dict()`` and from any optimiser. The result is
         memoised on the model, keyed by the source parameters' ``_version`` (and storage): a call after an
@@ -467,11 +564,18 @@ class GPT(torch.nn.Module):
             return memo
         old = memo.matrices() if memo is not None and len(memo._key) == len(key) else [None] * len(srcs)
         with torch.no_grad():
-            qs = [q if q is not None and memo._key[i] == key[i] else ops.quantize_weight(p.detach())
+            # the W8A16 kernel takes K % 16 == 0: a matrix off that grid (fc2 of a Llama-style d_ff such as 344 or
+            # 11008 / tp) stays the model's bf16 parameter, and its steps run the bf16 weight-streaming kernel
+            qs = [q if q is not None and memo._key[i] == key[i]
+                  else (ops.quantize_weight(p.detach()) if p.shape[1] % 16 == 0 else p.detach())
                   for i, (p, q) in enumerate(zip(srcs, old))]
         n = len(_LINEARS)
         blocks = [dict(zip(_LINEARS, qs[i * n:(i + 1) * n])) for i in range(len(self.blocks))]
         memo = DecodeWeights(blocks, qs[-1], key)
+        if memo.unquantized:  # once per (memoised) object: the caller asked for 8-bit weights and gets a mixed set
+            warnings.warn(f"decode_weights: {len(memo.unquantized)} matrices keep bf16 weights (inner dimension no "
+                          f"multiple of 16): {', '.join(memo.unquantized[:4])}"
+                          f"{', ...' if len(memo.unquantized) > 4 else ''}", stacklevel=2)
         self.__dict__["_decode_weights"] = memo  # not a parameter, buffer or submodule
         return memo
 
@@ -509,25 +613,24 @@ class GPT(torch.nn.Module):
         for li, blk in enumerate(self.blocks):
             h, hd = blk.local_heads, c.head_dim
             if native:
-                y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
+                y = blk.ln1.fwd(x)
                 qkv = self._skinny(y, wsel(li, "qkv"), blk.qkv.bias)  # [B, (h + 2 * hkv) * hd]
                 ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h, rope=rope)
                 a = torch.empty(B, h * hd, device=x.device, dtype=x.dtype)
                 ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, out=a.view(B, h, hd), **att)
                 x = self._skinny(a, wsel(li, "proj"), blk.proj.bias, residual=x)
-                y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
-                y = self._skinny(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
+                y = self._fc1(self._skinny, blk.ln2.fwd(x), wsel(li, "fc1"), blk)
                 x = self._skinny(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
                 ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h, rope=rope)  # torch ops: CPU / torch_reference()
                 a = ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, **att).reshape(B, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
-                y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
+                y = self._fc1_torch(blk.ln2(x), wsel(li, "fc1"), blk)
                 x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
         cache.advance(1)
         if native:
-            return self._skinny(ops.layer_norm_fwd(x, self.ln_f.weight, self.ln_f.bias)[0], head_w)
+            return self._skinny(self.ln_f.fwd(x), head_w)
         return _flinear(self.ln_f(x), head_w)
 
     @torch.no_grad()
@@ -600,21 +703,20 @@ class GPT(torch.nn.Module):
         for li, blk in enumerate(self.blocks):
             h, hd = blk.local_heads, c.head_dim
             if native:
-                y = ops.layer_norm_fwd(x, blk.ln1.weight, blk.ln1.bias)[0]
+                y = blk.ln1.fwd(x)
                 qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, -1)
                 ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
                 a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
                 attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, out=a.view(B, T, h, hd), **att)
                 x = lin(a.view(B * T, h * hd), wsel(li, "proj"), blk.proj.bias, residual=x)
-                y = ops.layer_norm_fwd(x, blk.ln2.weight, blk.ln2.bias)[0]
-                y = lin(y, wsel(li, "fc1"), blk.fc1.bias, act=blk.fc1.act)
+                y = self._fc1(lin, blk.ln2.fwd(x), wsel(li, "fc1"), blk)
                 x = lin(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
             else:
                 qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
                 ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)  # torch ops: CPU tensors / torch_reference()
                 a = attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, **att).reshape(B, T, h * hd)
                 x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
-                y = F.gelu(_flinear(blk.ln2(x), wsel(li, "fc1"), blk.fc1.bias), approximate="tanh")
+                y = self._fc1_torch(blk.ln2(x), wsel(li, "fc1"), blk)
                 x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
         cache.advance(T)
         if head == "none":
@@ -627,7 +729,7 @@ class GPT(torch.nn.Module):
             return _flinear(self.ln_f(x), head_w)
         rows = x.reshape(-1, c.d_model)
         head_lin = self._skinny if rows.shape[0] <= ops.gemm.SKINNY_MAX_M else self._auto
-        logits = head_lin(ops.layer_norm_fwd(rows, self.ln_f.weight, self.ln_f.bias)[0], head_w)
+        logits = head_lin(self.ln_f.fwd(rows), head_w)
         return logits.view(*x.shape[:-1], c.vocab_size)
 
     def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int, kv_dtype=None, tw=None,
@@ -851,7 +953,8 @@ class GPT(torch.nn.Module):
         """Training FLOPs/token (fwd+bwd = 3x fwd): dense matmuls + attention scores."""
         c = self.cfg
         kv = 2 * c.kv_heads * c.head_dim  # the K and V projections' features (2 * d_model without grouping)
-        dense = (2 * ((2 * c.d_model + kv) * c.d_model + 2 * c.d_model * c.d_ff) * c.n_layers
+        mlp = (3 if c.mlp == "swiglu" else 2) * c.d_model * c.d_ff  # gate, up and down / up and down
+        dense = (2 * ((2 * c.d_model + kv) * c.d_model + mlp) * c.n_layers
                  + 2 * c.d_model * c.vocab_size)
         attn = 2 * 2 * seq * c.d_model * c.n_layers
         return 3.0 * (dense + attn)

@@ -2,7 +2,7 @@
 from ._lib import NativeLibraryError, available, build_info, lib  # noqa: F401
 from .gemm import QuantizedWeight, quantize_weight  # noqa: F401
 from .gemm import act_grad, dgrad_act, flops, gemm_nt, gemm_nt_preact, linear, matmul, mlp, mm, wgrad_pair  # noqa: F401
-from .layernorm import layer_norm, layer_norm_fwd, layer_norm_residual, rms_norm, rms_norm_fwd  # noqa: F401
+from .layernorm import layer_norm, layer_norm_fwd, layer_norm_residual, rms_norm, rms_norm_fwd, rms_norm_residual  # noqa: F401
 from .xent import cross_entropy  # noqa: F401
 from .attention import attention_qkv, attn_block, flash_attention, split_heads  # noqa: F401
 from .attention import supported as attention_supported  # noqa: F401
@@ -11,6 +11,7 @@ from .graph import GraphedCallable  # noqa: F401
 from .decode import KVCache, attention_chunk, attention_decode, attention_extend, kv_append  # noqa: F401
 from . import decode  # noqa: F401
 from .rope import rope_qkv, rope_table  # noqa: F401
+from .swiglu import swiglu, swiglu_deinterleave, swiglu_interleave  # noqa: F401
 from .sample import sample  # noqa: F401  (the function shadows its module: import names from ops.sample directly)
 
 

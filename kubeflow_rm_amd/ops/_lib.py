@@ -139,6 +139,21 @@ _SIGNATURES = {
                                              c_ll, c_ll, c_float, c_int, c_vp]),
     "kfamd_gemm_nt_skinny_w8_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                               c_ll, c_ll, c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_bf16_glu": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_float,
+                                              c_vp]),
+    "kfamd_gemm_nt_skinny_bf16_glu_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                                   c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_bf16_glu_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll,
+                                                    c_ll, c_ll, c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_w8_glu": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                            c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_w8_glu_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,
+                                                 c_ll, c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_w8_glu_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll,
+                                                  c_ll, c_ll, c_float, c_vp]),
+    "kfamd_swiglu_fwd_bf16": (c_int, [c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_vp]),
+    "kfamd_swiglu_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_ll, c_vp]),
+    "kfamd_rmsnorm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "kfamd_sample_bf16": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_float, c_int,
                                   c_float, c_ll, c_vp]),
     "kfamd_build_info": (ctypes.c_char_p, []),

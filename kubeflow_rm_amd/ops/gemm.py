@@ -112,6 +112,76 @@ def _gemm_nt_w8(a, qw: QuantizedWeight, bias, residual, alpha, act, out, variant
     return out
 
 
+def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
+    """gemm_nt(act="swiglu"): the gated weight-streaming GEMM (ops/swiglu.py states the rule; w's rows are
+    interleaved gate / up, the output is [..., N / 2]) on a bf16 weight or a QuantizedWeight. Only the three skinny
+    variants: "swiglu" is not an activation code of any other GEMM and never reaches one. CPU tensors and
+    ops.torch_reference() compute the rule in torch, under the same argument checks."""
+    from .swiglu import swiglu_reference
+    quant = isinstance(w, QuantizedWeight)
+    if variant not in SKINNY_PATHS:
+        raise ValueError(f'gemm_nt(act="swiglu") runs the weight-streaming kernel only: variant in '
+                         f"{sorted(SKINNY_PATHS)} expected, got {variant!r}")
+    if residual is not None:
+        raise ValueError('gemm_nt(act="swiglu") takes no residual (it belongs to the down-projection)')
+    if len(w.shape) != 2:
+        raise ValueError(f'gemm_nt(act="swiglu"): a weight [2F, K] expected, got {tuple(w.shape)}')
+    N, K = w.shape
+    if N % 2:
+        raise ValueError(f'gemm_nt(act="swiglu"): an even number of weight rows (gate / up pairs) expected, got N={N}')
+    if a.shape[-1] != K:
+        raise ValueError(f"inner dims differ: a has K={a.shape[-1]}, the weight has K={K}")
+    out_shape = (*a.shape[:-1], N // 2)
+    if out is not None and (tuple(out.shape) != tuple(out_shape) or out.device != a.device or out.dtype != a.dtype):
+        raise ValueError(f"out must be a {a.dtype} {tuple(out_shape)} tensor on {a.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous [N] tensor")
+    M = a.numel() // K if K else 0
+    kq = 16 if quant else 8
+    if not 1 <= M <= SKINNY_MAX_M or K < kq or K % kq:
+        raise ValueError(f'gemm_nt(act="swiglu") variant={variant!r}: 1 <= M <= {SKINNY_MAX_M} and K % {kq} == 0 '
+                         f"expected, got M={M} K={K}")
+    from . import native_enabled
+    if not a.is_cuda or not native_enabled():
+        wf = w.dequantize() if quant else w.float()
+        z = float(alpha) * (a.float() @ wf.to(a.device).t())
+        if bias is not None:
+            z = z + bias.float()
+        h = swiglu_reference(z).to(a.dtype)
+        return h if out is None else out.copy_(h)
+    _check_operand(a, "a")
+    wt = w.codes if quant else w
+    if not quant:
+        _check_operand(w, "b")
+    if not wt.is_cuda or wt.device != a.device:
+        raise ValueError("gemm_nt: the weight must live on a's GPU")
+    a2 = a.reshape(-1, K) if a.dim() != 2 else a
+    if a2.stride(-1) != 1:
+        a2 = a2.contiguous()
+    if wt.stride(1) != 1 or (quant and not w.scale.is_contiguous()):
+        raise ValueError("gemm_nt: a weight with a unit inner stride (and a contiguous scale) expected")
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.bfloat16, device=a.device)
+    else:
+        _check_operand(out, "out")
+    c2 = out.view(M, N // 2)
+    if bias is not None:
+        _check_operand(bias, "bias")
+    bp = bias.data_ptr() if bias is not None else None
+    L = _lib.lib()
+    if quant:
+        rc = L.kfamd_gemm_nt_skinny_w8_glu_tiles(SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), wt.data_ptr(),
+                                                 w.scale.data_ptr(), c2.data_ptr(), bp, M, N, K, a2.stride(0),
+                                                 wt.stride(0), c2.stride(0), float(alpha), _stream_ptr(a))
+    else:
+        rc = L.kfamd_gemm_nt_skinny_bf16_glu_tiles(SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), wt.data_ptr(),
+                                                   c2.data_ptr(), bp, M, N, K, a2.stride(0), wt.stride(0), c2.stride(0),
+                                                   float(alpha), _stream_ptr(a))
+    _lib.check(rc, f"gemm_nt[skinny {'w8 ' if quant else ''}swiglu {M}x{N}x{K}]")
+    return out
+
+
 def _stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -201,7 +271,12 @@ def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight", *, bias: torch
             out: torch.Tensor | None = None, variant: str = "auto") -> torch.Tensor:
     """C = act(alpha * a @ b^T + bias) (+ residual). a: [..., M, K] or [B, M, K]; b: [N, K] or [B, N, K].
     ``b`` may be a ``QuantizedWeight`` with ``variant`` "skinny" / "skinny_valu" / "skinny_mfma" (M <= 16, K % 16 == 0):
-    the W8A16 weight-streaming kernel; every other variant or shape raises ``ValueError``."""
+    the W8A16 weight-streaming kernel; every other variant or shape raises ``ValueError``.
+    ``act="swiglu"`` (the three skinny variants only; ``b``'s rows interleaved gate / up, ``ops/swiglu.py``): C =
+    silu(z[..., 2j]) * z[..., 2j + 1] of z = alpha * a @ b^T + bias, shape ``[..., N / 2]``, in the GEMM's one launch;
+    a residual, an odd N or any other variant raises ``ValueError``."""
+    if act == "swiglu":
+        return _gemm_nt_swiglu(a, b, bias, residual, alpha, out, variant)
     if isinstance(b, QuantizedWeight):
         return _gemm_nt_w8(a, b, bias, residual, alpha, act, out, variant)
     _check_operand(a, "a")

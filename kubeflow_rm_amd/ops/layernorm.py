@@ -41,33 +41,71 @@ def rms_norm_fwd(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, save_
     return y.view(x.shape), rstd
 
 
+def _rms_backward(ctx, gy, gres=None):
+    """dx (+ gres) and dgamma on kfamd_rmsnorm_bwd_bf16, from the forward's saved fp32 rstd."""
+    x, gamma, rstd = ctx.saved_tensors
+    H = x.shape[-1]
+    if gy is None:  # only the residual output was used
+        return gres, None, None
+    x2 = x.reshape(-1, H).contiguous()
+    rows = x2.shape[0]
+    gy2 = gy.reshape(-1, H).contiguous().to(torch.bfloat16)
+    res = gres.reshape(-1, H).contiguous().to(torch.bfloat16) if gres is not None else None
+    dx = torch.empty_like(x2)
+    pbf16 = ctx.weight_dtype == torch.bfloat16
+    dgamma = torch.empty(H, dtype=torch.bfloat16 if pbf16 else torch.float32, device=x.device)
+    ws = torch.empty(_lib.lib().kfamd_layernorm_bwd_workspace(rows, H) // 4, dtype=torch.float32, device=x.device)
+    rc = _lib.lib().kfamd_rmsnorm_bwd_bf16(
+        gy2.data_ptr(), res.data_ptr() if res is not None else None, x2.data_ptr(), gamma.data_ptr(),
+        rstd.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), int(pbf16), ws.data_ptr(), rows, H, _stream_ptr(x))
+    _lib.check(rc, f"rmsnorm_bwd[{rows}x{H}]")
+    return dx.view(x.shape), dgamma.to(ctx.weight_dtype), None
+
+
+def _rms_forward(ctx, x, weight, eps):
+    # the kernels read gamma as bf16; an fp32 parameter is rounded once here and gets its gradient in fp32. What the
+    # backward reads is saved as a tensor: a bf16 parameter itself, so an in-place update before backward() is caught
+    gamma = weight.contiguous() if weight.dtype == torch.bfloat16 else weight.to(torch.bfloat16)
+    y, rstd = rms_norm_fwd(x, gamma, eps, save_stats=True)
+    ctx.save_for_backward(x, gamma, rstd)
+    ctx.weight_dtype = weight.dtype
+    return y
+
+
 class _RMSNorm(torch.autograd.Function):
-    """Forward on the HIP kernel (fp32 rstd saved); backward from the saved rstd:
+    """Forward and backward on the HIP kernels (fp32 rstd saved by the forward):
     dx = rstd * (w*dy - xhat * mean(w*dy*xhat)), dw = sum(dy * xhat), xhat = x * rstd."""
 
     @staticmethod
     def forward(ctx, x, weight, eps):
-        y, rstd = rms_norm_fwd(x, weight, eps, save_stats=True)
-        ctx.save_for_backward(x, weight, rstd)
-        return y
+        return _rms_forward(ctx, x, weight, eps)
 
     @staticmethod
     def backward(ctx, gy):
-        x, weight, rstd = ctx.saved_tensors
-        H = x.shape[-1]
-        xf = x.reshape(-1, H).float()
-        r = rstd.unsqueeze(-1)
-        xhat = xf * r
-        gyf = gy.reshape(-1, H).float()
-        gdy = gyf * weight.float()
-        dx = r * (gdy - xhat * (gdy * xhat).mean(-1, keepdim=True))
-        dw = (gyf * xhat).sum(0)
-        return dx.to(x.dtype).view(x.shape), dw.to(weight.dtype), None
+        return _rms_backward(ctx, gy)
+
+
+class _RMSNormResidual(torch.autograd.Function):
+    """(RMSNorm(x), x), as _LayerNormResidual: both outputs' gradients meet in the backward kernel's dx store."""
+
+    @staticmethod
+    def forward(ctx, x, weight, eps):
+        return _rms_forward(ctx, x, weight, eps), x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, gy, gres):
+        return _rms_backward(ctx, gy, gres)
 
 
 def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     """Autograd-aware RMSNorm over the last dim (bf16 I/O, fp32 statistics)."""
     return _RMSNorm.apply(x, weight, eps)
+
+
+def rms_norm_residual(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6):
+    """``(rms_norm(x), r)`` where ``r`` is ``x`` for the residual add, as ``layer_norm_residual``: use ``r`` (not
+    ``x``) as the residual and the two gradient contributions to ``x`` are summed inside the RMSNorm backward."""
+    return _RMSNormResidual.apply(x, weight, eps)
 
 
 def _ln_backward(ctx, gy, gres=None):

@@ -58,6 +58,14 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         pos="rope" against pos="learned" in one process, B in {1, 16}, position about 2048, graphed and eager,
         7 interleaved runs: ms/token. Train: forward + backward of 4 x 2048 tokens (no optimiser), rotary
         against learned, 7 interleaved blocks.
+  glu   (not in the default list) SwiGLU. Kernel: gemm_nt(act="swiglu") (one launch; "skinny", each arithmetic form
+        forced, and every tile count / rows-per-wave of each form forced) against the two-launch form, the ungated
+        weight-streaming GEMM to [M, 2F] then ops.swiglu, at M in {1, 2, 4, 8, 16}, d_model 2048, F in {8192, 5504},
+        bf16 and FP8 weights, weights rotated past the last-level cache, 7 interleaved blocks: us, min - max. Model:
+        a gpt-1b-sized norm="rms", mlp="swiglu", pos="rope", n_kv_heads=4 model (gpt-small-sized with --quick), the
+        gated GEMM against the two-launch MLP in the same model (its _fc1 shadowed by this tool), B in {1, 16}, position
+        about 2048, graphed and eager, 7 interleaved runs: ms/token. RMSNorm backward with dres at 8192 x 2048: the
+        kernel against the fp32 torch arithmetic it replaced.
 """
 from __future__ import annotations
 
@@ -75,7 +83,7 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
-                "chunk": 900, "gqa": 1000, "rope": 600}
+                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600}
 GQA_GS = (1, 2, 4, 8, 16)
 GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
 CHUNK_TS = (16, 32, 64, 128, 256, 512)
@@ -1013,7 +1021,141 @@ def step_rope(quick: bool):
     return out
 
 
-STEPS = {"rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+GLU_FS = (8192, 5504)
+
+
+def _glu_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.ops.gemm import _gemm_nt_swiglu
+    from kubeflow_rm_amd.ops.swiglu import swiglu_fwd
+    rows = []
+    K = 2048
+    for Fd in GLU_FS:
+        N = 2 * Fd
+        for fmt in ("bf16", "fp8"):
+            ncopy = 2 if quick else max(2, -(-(512 << 20) // (N * K * (2 if fmt == "bf16" else 1))))
+            ws = [torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16) for _ in range(ncopy)]
+            if fmt == "fp8":
+                ws = [ops.quantize_weight(w) for w in ws]
+            bias = torch.randn(N, device="cuda").to(torch.bfloat16)
+            for M in GEMM_MS:
+                a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+                out = torch.empty(M, Fd, device="cuda", dtype=torch.bfloat16)
+                z = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+
+                def glu(variant, tiles=0):
+                    return lambda i: _gemm_nt_swiglu(a, ws[i % ncopy], bias, None, 1.0, out, variant, tiles)
+
+                def two(i):
+                    ops.gemm_nt(a, ws[i % ncopy], bias=bias, out=z, variant="skinny")
+                    swiglu_fwd(z, out=out)
+
+                fns = {"two_launch": two, "glu": glu("skinny"), "glu_mfma": glu("skinny_mfma"),
+                       **{f"glu_mfma_t{t}": glu("skinny_mfma", t) for t in (1, 2, 4)}}
+                if M <= 8:
+                    fns.update({"glu_valu": glu("skinny_valu"), "glu_valu_r2": glu("skinny_valu", 2)})
+                    if M <= 4:  # 8 activation rows always take 2 weight rows per wave
+                        fns["glu_valu_r4"] = glu("skinny_valu", 4)
+                r = _time_blocks(fns, blocks=5 if quick else 7, iters=ncopy)
+                row = {"M": M, "F": Fd, "N": N, "K": K, "weights": fmt, "weight_copies": ncopy, **r}
+                row["two_launch_over_glu"] = r["two_launch"]["median_us"] / r["glu"]["median_us"]
+                row["separated"] = (r["glu"]["max_us"] < r["two_launch"]["min_us"]
+                                    or r["two_launch"]["max_us"] < r["glu"]["min_us"])
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            del ws
+            torch.cuda.empty_cache()
+    return rows
+
+
+def _glu_model_rows(quick: bool):
+    """Graphed (and eager) decode, ms/token around position 2048: the gated GEMM against the two-launch MLP."""
+    import dataclasses
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    from kubeflow_rm_amd import ops
+    name = "gpt-small" if quick else "gpt-1b"
+    # 4 K / V heads under gpt-1b's 16 query heads; gpt-small has 12, and groups of 3 are no kernel instantiation: 6
+    cfg = dataclasses.replace(CONFIGS[name], norm="rms", mlp="swiglu", pos="rope", n_kv_heads=6 if quick else 4)
+    model = GPT(cfg, device="cuda").eval()
+    rows = []
+    prompt, new = 2048 - 64, 64
+    for B in (1, 16):
+        idx = torch.randint(0, cfg.vocab_size, (B, prompt), device="cuda")
+        toks = torch.randint(0, cfg.vocab_size, (new, B), device="cuda")
+
+        def run(form, mode):
+            if form != "fused":  # shadow GPT._fc1 on this instance: ungated GEMM to [rows, 2 d_ff], then the gate kernel
+                model._fc1 = lambda lin, y, w, blk: ops.swiglu(lin(y, w, blk.fc1.bias))
+            try:
+                cache = model.new_cache(B, prompt + new)
+                model.prefill(idx, cache)
+                step = (lambda t: model.decode_step(t, cache)) if mode != "graph" else model.graphed_decode_step(cache)
+                step(toks[0])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(1, new):
+                    step(toks[i])
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3 / (new - 1)
+            finally:
+                model.__dict__.pop("_fc1", None)
+
+        keys = [(f, mode) for mode in ("graph", "eager") for f in ("two", "fused")]
+        res = {k: [] for k in keys}
+        for _ in range(3 if quick else 7):  # interleaved
+            for k in keys:
+                res[k].append(run(*k))
+        row = {"model": f"{name} rms / swiglu / rope / {cfg.n_kv_heads} kv heads", "B": B, "prompt": prompt, "new": new}
+        for (f, mode), v in res.items():
+            row[f"{f}_{mode}"] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+        for mode in ("graph", "eager"):
+            a, b = row[f"fused_{mode}"], row[f"two_{mode}"]
+            row[f"two_over_fused_{mode}"] = b["ms_per_token"] / a["ms_per_token"]
+            row[f"separated_{mode}"] = a["max"] < b["min"] or b["max"] < a["min"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def _glu_rmsnorm_rows(quick: bool):
+    """RMSNorm backward with the residual gradient, 8192 x 2048: the kernel against the torch arithmetic it replaced."""
+    import torch
+    from kubeflow_rm_amd import ops
+    rows_, H = (1024, 2048) if quick else (8192, 2048)
+    x = torch.randn(rows_, H, device="cuda").to(torch.bfloat16)
+    w = torch.ones(H, device="cuda", dtype=torch.bfloat16)
+    gy, gr = (torch.randn(rows_, H, device="cuda").to(torch.bfloat16) for _ in range(2))
+    _, rstd = ops.rms_norm_fwd(x, w, 1e-6, save_stats=True)
+
+    def torch_bwd(i):  # the previous _RMSNorm.backward, plus autograd's add of the residual gradient
+        r = rstd.unsqueeze(-1)
+        xhat = x.float() * r
+        gyf = gy.float()
+        gdy = gyf * w.float()
+        dx = (r * (gdy - xhat * (gdy * xhat).mean(-1, keepdim=True))).to(torch.bfloat16) + gr
+        return dx, (gyf * xhat).sum(0).to(torch.bfloat16)
+
+    xg, wg = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y, r = ops.rms_norm_residual(xg, wg, 1e-6)
+
+    def kernel_bwd(i):
+        torch.autograd.backward([y, r], [gy, gr], retain_graph=True)
+        xg.grad = wg.grad = None
+
+    t = _time_blocks({"torch": torch_bwd, "kernel": kernel_bwd}, blocks=5 if quick else 7, iters=10)
+    row = {"op": "rmsnorm backward + dres", "rows": rows_, "hidden": H, **t,
+           "torch_over_kernel": t["torch"]["median_us"] / t["kernel"]["median_us"]}
+    print(json.dumps(row), flush=True)
+    return [row]
+
+
+def step_glu(quick: bool):
+    return {"kernel": _glu_kernel_rows(quick), "rmsnorm_bwd": _glu_rmsnorm_rows(quick), "model": _glu_model_rows(quick)}
+
+
+STEPS = {"glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
