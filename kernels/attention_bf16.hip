@@ -36,6 +36,13 @@
 // Causal masking is key <= query. The forward's workgroups run heaviest query block first; the
 // backward's key blocks are heaviest first already (block 0 sees every query).
 //
+// Grouped-query attention (AttnShape::Hkv < H): K / V (and dK / dV) have Hkv heads and query head h
+// reads head h / G, G = H / Hkv, in place. The forward and dQ kernels change only their K / V base
+// offsets: grids, kernel choice, pairing and block_order stay in query heads, so a head computes
+// what it computes on expanded K / V, bit for bit. block_order gives an XCD consecutive heads, so a
+// group's K / V tiles meet in one L2 whenever G divides the heads per XCD (B H / 8). dK / dV sums a
+// group in fp32 inside attn_bwd_dkdv8 (GRP), see there and gqa_group_split.
+//
 // Counterpart in the reference: none (its notebook images ship the framework's own attention);
 // SURVEY §7.1C rules out Triton on the hot path.
 #include <hip/hip_runtime.h>
@@ -53,6 +60,9 @@ constexpr float kLog2e = 1.4426950408889634f;
 struct AttnShape {
   int B, H, T;
   float scale;
+  // grouped-query attention: Hkv K / V heads, G = H / Hkv query heads per K / V head (1: every head its own);
+  // GS: the query heads of a group that one dK / dV workgroup sweeps (a divisor of G; attn_bwd_dkdv8 GRP)
+  int Hkv, G, GS;
   // element strides (b, h, t) of q, k, v, o, do, dq, dk, dv
   long long s[8][3];
 };
@@ -310,8 +320,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
   const int T = a.T;
 
   const __bf16* qb = q + base_off(a, TQ, b, h);
-  const __bf16* kb = k + base_off(a, TK, b, h);
-  const __bf16* vb = v + base_off(a, TV, b, h);
+  const __bf16* kb = k + base_off(a, TK, b, h / a.G);  // grouped K / V heads: query head h reads head h / G
+  const __bf16* vb = v + base_off(a, TV, b, h / a.G);
   const long long qt = a.s[TQ][2], kt = a.s[TK][2], vt = a.s[TV][2];
 
   bf16x8 qf[KS];
@@ -612,8 +622,8 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
   if (KFATT_FWD_PRIO && wu >= 4) __builtin_amdgcn_s_setprio(1);
 
   const __bf16* qb = q + base_off(a, TQ, b, h);
-  const __bf16* kb = k + base_off(a, TK, b, h);
-  const __bf16* vb = v + base_off(a, TV, b, h);
+  const __bf16* kb = k + base_off(a, TK, b, h / a.G);  // grouped K / V heads: query head h reads head h / G
+  const __bf16* vb = v + base_off(a, TV, b, h / a.G);
   const long long qt = a.s[TQ][2], kt = a.s[TK][2], vt = a.s[TV][2];
   const auto rk = slice_rsrc(kb, 2LL * T * kt), rv = slice_rsrc(vb, 2LL * T * vt);
   const float c = a.scale * kLog2e;
@@ -952,8 +962,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
   const int q0 = qblk * FQ, qw = q0 + 32 * w, qrow = qw + r;
 
   const __bf16* qb = q + base_off(a, TQ, b, h);
-  const __bf16* kb = k + base_off(a, TK, b, h);
-  const __bf16* vb = v + base_off(a, TV, b, h);
+  const __bf16* kb = k + base_off(a, TK, b, h / a.G);  // grouped K / V heads: query head h reads head h / G
+  const __bf16* vb = v + base_off(a, TV, b, h / a.G);
   const __bf16* dob = dout + base_off(a, TDO, b, h);
   const long long qt = a.s[TQ][2], kt = a.s[TK][2], vt = a.s[TV][2], dot = a.s[TDO][2];
   const auto rq = slice_rsrc(qb, 2LL * T * qt), rdo = slice_rsrc(dob, 2LL * T * dot);
@@ -1183,12 +1193,26 @@ constexpr int BK = 128, BQ = 64, QS = BQ / 32;
 // barriers with each other's MFMAs (the 4-wave kernel runs one wave per SIMD at D = 128 and waits
 // half its cycles). K and V both sit in LDS (V rows are the dP product's B operand) to keep a wave
 // within 256 registers; the two halves' partial dK^T / dV^T are summed through LDS at the end.
+//
+// GRP (grouped-query attention, Hkv < H): the grid runs over K / V heads, nk * Hkv * B * (G / GS)
+// workgroups. A workgroup keeps its 128 keys' dK^T / dV^T in registers as above and sweeps the query
+// tiles of GS query heads of the group, head after head, as ONE flat tile sequence: the double buffer
+// keeps running across a head boundary, only the Q / dO / nl / nd descriptors of the staged tile switch
+// (SGPR quads rebuilt per staged tile: a few scalar instructions). GS = G: the group's sum is complete
+// in fp32 registers, rounded once and stored as bf16 with Hkv heads. GS < G: the G / GS workgroups
+// ("parts") of a (key block, K / V head) store their unscaled fp32 sums to `gpart`
+// ([dk, dv][part][B][Hkv][T][D]) and attn_bwd_gqa_reduce adds the parts in part order, scales, rounds
+// once and stores: no atomics on either route, both deterministic. GRP = false is the kernel as it was.
+// Registers (hipcc 7.2 remarks; no scratch anywhere): D = 128 causal / full 226 / 222 VGPRs ungrouped,
+// 227 / 228 GRP; D = 64 126 / 128 ungrouped, 124 / 128 GRP. GRP at D = 64 asks for 4 waves per SIMD
+// in its launch bounds: unforced, the non-causal kernel took 142 VGPRs and lost the second workgroup per CU.
 // ------------------------------------------------------------------------------------------------
-template <int D, bool CAUSAL>
-__global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
+template <int D, bool CAUSAL, bool GRP = false>
+__global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkdv8(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                          const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
                                                          const float* __restrict__ nl, const float* __restrict__ nd,
-                                                         __bf16* __restrict__ dk, __bf16* __restrict__ dv, AttnShape a) {
+                                                         __bf16* __restrict__ dk, __bf16* __restrict__ dv, AttnShape a,
+                                                         float* __restrict__ gpart) {
   constexpr int KS = D / 16;
   constexpr int ND = D / 32;
   constexpr int CH = D / 8;
@@ -1205,17 +1229,23 @@ __global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __b
 
   const int T = a.T;
   const int nk = (T + BK - 1) / BK;
-  const BlockId bo = block_order(blockIdx.x, nk, a.H * a.B, D == 64 ? 64 : 32);
+  // GRP: the part (which GS query heads of the group) outermost, so that with a grid per part that is a
+  // multiple of 8 the parts of one K / V head land on the same XCD (its K / V tiles in one L2)
+  const int HK = GRP ? a.Hkv : a.H;  // heads the grid runs over
+  const int nkv = nk * HK * a.B;
+  const int gp = GRP ? blockIdx.x / nkv : 0;
+  const BlockId bo = block_order(GRP ? blockIdx.x - gp * nkv : blockIdx.x, nk, HK * a.B, D == 64 ? 64 : 32);
   const int kblk = bo.rank;  // block 0 (all queries) first
-  const int bh = bo.bh, h = bh % a.H, b = bh / a.H;
+  const int bh = bo.bh, hk = bh % HK, b = bh / HK;  // hk: the head of K, V, dK, dV
+  const int h = GRP ? hk * a.G + gp * a.GS : hk;  // (the first of) this workgroup's query head(s)
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..7, uniform
   const int w = wv & 3, jh = wv >> 2;                       // key group, query half
   const int k0 = kblk * BK, kw = k0 + 32 * w, key = kw + r;
 
   const __bf16* qb = q + base_off(a, TQ, b, h);
-  const __bf16* kb = k + base_off(a, TK, b, h);
-  const __bf16* vb = v + base_off(a, TV, b, h);
+  const __bf16* kb = k + base_off(a, TK, b, hk);
+  const __bf16* vb = v + base_off(a, TV, b, hk);
   const __bf16* dob = dout + base_off(a, TDO, b, h);
   const long long qt = a.s[TQ][2], kt = a.s[TK][2], vt = a.s[TV][2], dot = a.s[TDO][2];
   const float* nlb = nl + ((long long)b * a.H + h) * T;
@@ -1243,16 +1273,30 @@ __global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __b
     dvo_q[i] = 2 * (row * (int)qt + ch * 8);
     dvo_o[i] = 2 * (row * (int)dot + ch * 8);
   }
-  auto stage_dma = [&](int tile, int buf) {
+  // g (GRP): the tile's query head within this workgroup's GS heads: Q, dO, nl, nd of head h + g
+  auto stage_dma = [&](int tile, int buf, int g = 0) {
     const int q0 = qstart + tile * BQ;
     char* qi = qtiles + buf * 2 * QT;
     char* oi = qi + QT;
+    const i32x4 dq_d = GRP ? slice_desc(qb + g * a.s[TQ][1], 2LL * T * qt) : dq_desc;
+    const i32x4 ddo_d = GRP ? slice_desc(dob + g * a.s[TDO][1], 2LL * T * dot) : ddo_desc;
+    const i32x4 drow_d = GRP ? slice_desc((wv == 0 ? nlb : ndb) + (long long)g * T, 4LL * T) : drow_desc;
 #pragma unroll
     for (int i = 0; i < NPC; ++i) {
-      dma16(dq_desc, lds_addr(qi + (wv * NPC + i) * 1024), dvo_q[i], 2 * q0 * (int)qt);
-      dma16(ddo_desc, lds_addr(oi + (wv * NPC + i) * 1024), dvo_o[i], 2 * q0 * (int)dot);
+      dma16(dq_d, lds_addr(qi + (wv * NPC + i) * 1024), dvo_q[i], 2 * q0 * (int)qt);
+      dma16(ddo_d, lds_addr(oi + (wv * NPC + i) * 1024), dvo_o[i], 2 * q0 * (int)dot);
     }
-    if (wv < 2) dma4(drow_desc, lds_addr(reinterpret_cast<const char*>(rowc + buf * 2 * BQ + wv * BQ)), 4 * lane, 4 * q0);
+    if (wv < 2) dma4(drow_d, lds_addr(reinterpret_cast<const char*>(rowc + buf * 2 * BQ + wv * BQ)), 4 * lane, 4 * q0);
+  };
+  // GRP: the flat sequence of GS * ntiles tiles; (sg, st) = the head and tile that the next staging loads
+  const int nflat = (GRP ? a.GS : 1) * ntiles;
+  int sg = 0, st = 0;
+  auto stage_next = [&](int buf) {
+    stage_dma(st, buf, sg);
+    if (++st == ntiles) {
+      st = 0;
+      ++sg;
+    }
   };
 
   int koff[KS], voff0[ND], voff1[ND];
@@ -1278,14 +1322,21 @@ __global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __b
     dvacc[n] = (f32x16){};
   }
 
-  if (ntiles > 0) stage_dma(0, 0);
+  if (ntiles > 0) {
+    if constexpr (GRP) stage_next(0);
+    else stage_dma(0, 0);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  auto tile_body = [&](int it, auto BUFC) __attribute__((always_inline)) {
+  // it: the tile's index within its head's sweep; more: another tile follows (GRP: maybe of the next head)
+  auto tile_body = [&](int it, bool more, auto BUFC) __attribute__((always_inline)) {
     constexpr int BUF = decltype(BUFC)::value;
     const int q0 = qstart + it * BQ;
-    if ((KFATT_DKDV_ABL & 1) == 0 && it + 1 < ntiles) stage_dma(it + 1, 1 - BUF);  // ABL 1: no staging
+    if ((KFATT_DKDV_ABL & 1) == 0 && more) {  // ABL 1: no staging
+      if constexpr (GRP) stage_next(1 - BUF);
+      else stage_dma(it + 1, 1 - BUF);
+    }
     const char* qi = qtiles + BUF * 2 * QT + 32 * jh * D * 2;  // this wave's 32 query rows
     const char* oi = qi + QT;
     const float* nl_s = rowc + BUF * 2 * BQ + 32 * jh;
@@ -1396,9 +1447,21 @@ __global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __b
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next tile's pieces (the loop's only VMEM)
     if ((KFATT_DKDV_ABL & 2) == 0) __syncthreads();       // ABL 2: no barrier (timing only)
   };
-  for (int it = 0; it < ntiles; it += 2) {
-    tile_body(it, std::integral_constant<int, 0>{});
-    if (it + 1 < ntiles) tile_body(it + 1, std::integral_constant<int, 1>{});
+  if constexpr (GRP) {
+    int ct = 0;  // the computed tile's index within its head
+    for (int f = 0; f < nflat; f += 2) {
+      tile_body(ct, f + 1 < nflat, std::integral_constant<int, 0>{});
+      if (++ct == ntiles) ct = 0;
+      if (f + 1 < nflat) {
+        tile_body(ct, f + 2 < nflat, std::integral_constant<int, 1>{});
+        if (++ct == ntiles) ct = 0;
+      }
+    }
+  } else {
+    for (int it = 0; it < ntiles; it += 2) {
+      tile_body(it, it + 1 < ntiles, std::integral_constant<int, 0>{});
+      if (it + 1 < ntiles) tile_body(it + 1, it + 2 < ntiles, std::integral_constant<int, 1>{});
+    }
   }
 
   // the two query halves' partial sums: half 1 stages its accumulators (f32, lane-major) in the
@@ -1429,12 +1492,31 @@ __global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __b
   reduce(dkacc);
   reduce(dvacc);
   // lane = key, rows d = 32 n + (e & 3) + 8 (e >> 2) + 4 hh
+  if constexpr (GRP) {
+    if (a.GS != a.G) {  // this part's unscaled fp32 sums, [dk, dv][part][B][Hkv][T][D]: attn_bwd_gqa_reduce finishes
+      if (jh == 0 && key < T) {
+        const long long per = (long long)a.B * a.Hkv * T * D;  // one part of one tensor
+        float* pk = gpart + gp * per + (((long long)b * a.Hkv + hk) * T + key) * D;
+        float* pv = pk + (a.G / a.GS) * per;
+#pragma unroll
+        for (int n = 0; n < ND; ++n) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int d = 32 * n + 8 * g + 4 * hh;
+            *reinterpret_cast<f32x4*>(pk + d) = (f32x4){dkacc[n][4 * g], dkacc[n][4 * g + 1], dkacc[n][4 * g + 2], dkacc[n][4 * g + 3]};
+            *reinterpret_cast<f32x4*>(pv + d) = (f32x4){dvacc[n][4 * g], dvacc[n][4 * g + 1], dvacc[n][4 * g + 2], dvacc[n][4 * g + 3]};
+          }
+        }
+      }
+      return;
+    }
+  }
   if (KFATT_BWD_WIDE && jh == 0) {  // (jh: wave-uniform, so whole waves run the swaps)
-    store_rows16<ND>(dk + base_off(a, TDK, b, h) + key * a.s[TDK][2], dkacc, a.scale, key < T, hh);
-    store_rows16<ND>(dv + base_off(a, TDV, b, h) + key * a.s[TDV][2], dvacc, 1.f, key < T, hh);
+    store_rows16<ND>(dk + base_off(a, TDK, b, hk) + key * a.s[TDK][2], dkacc, a.scale, key < T, hh);
+    store_rows16<ND>(dv + base_off(a, TDV, b, hk) + key * a.s[TDV][2], dvacc, 1.f, key < T, hh);
   } else if (jh == 0 && key < T) {
-    __bf16* dkr = dk + base_off(a, TDK, b, h) + key * a.s[TDK][2];
-    __bf16* dvr = dv + base_off(a, TDV, b, h) + key * a.s[TDV][2];
+    __bf16* dkr = dk + base_off(a, TDK, b, hk) + key * a.s[TDK][2];
+    __bf16* dvr = dv + base_off(a, TDV, b, hk) + key * a.s[TDV][2];
 #pragma unroll
     for (int n = 0; n < ND; ++n) {
 #pragma unroll
@@ -1447,6 +1529,44 @@ __global__ __launch_bounds__(512, D == 64 ? 2 : 1) void attn_bwd_dkdv8(const __b
             (u32x2){pack2(dvacc[n][4 * g], dvacc[n][4 * g + 1]), pack2(dvacc[n][4 * g + 2], dvacc[n][4 * g + 3])};
       }
     }
+  }
+}
+
+// The group-split route's second pass (attn_bwd_dkdv8 GRP with GS < G): dk / dv (bf16, strided, Hkv heads) =
+// the NP = G / GS fp32 parts of a row added in part order (fixed: bit-identical from call to call), dk scaled,
+// each rounded once. One thread per 8 columns of one (b, hkv, t) row, both tensors.
+template <int D>
+__global__ __launch_bounds__(256) void attn_bwd_gqa_reduce(const float* __restrict__ gpart, __bf16* __restrict__ dk,
+                                                           __bf16* __restrict__ dv, AttnShape a) {
+  constexpr int LPR = D / 8;
+  constexpr int RPB = 256 / LPR;
+  const long long nrows = (long long)a.B * a.Hkv * a.T;
+  const long long row = (long long)blockIdx.x * RPB + threadIdx.x / LPR;
+  const int c8 = threadIdx.x % LPR;
+  if (row >= nrows) return;
+  const int t = (int)(row % a.T);
+  const int hk = (int)((row / a.T) % a.Hkv);
+  const int b = (int)(row / ((long long)a.T * a.Hkv));
+  const int np = a.G / a.GS;
+  const long long per = nrows * D;
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    const float* src = gpart + which * np * per + row * D + c8 * 8;
+    f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
+    for (int p = 1; p < np; ++p) {
+      src += per;
+      const f32x4 y0 = *reinterpret_cast<const f32x4*>(src), y1 = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x0[e] += y0[e];
+        x1[e] += y1[e];
+      }
+    }
+    const float s = which == 0 ? a.scale : 1.f;
+    const u32x4 y = {pack2(x0[0] * s, x0[1] * s), pack2(x0[2] * s, x0[3] * s), pack2(x1[0] * s, x1[1] * s),
+                     pack2(x1[2] * s, x1[3] * s)};
+    __bf16* dst = which == 0 ? dk + base_off(a, TDK, b, hk) + t * a.s[TDK][2] : dv + base_off(a, TDV, b, hk) + t * a.s[TDV][2];
+    *reinterpret_cast<u32x4*>(dst + c8 * 8) = y;
   }
 }
 
@@ -1803,6 +1923,8 @@ bool fill_shape(AttnShape& s, int B, int H, int T, int D, float scale, const lon
   s.H = H;
   s.T = T;
   s.scale = scale;
+  s.Hkv = H;
+  s.G = s.GS = 1;
   for (int t = 0; t < 8; ++t)
     for (int j = 0; j < 3; ++j) s.s[t][j] = t < ntensors ? strides[3 * t + j] : 0;
   for (int t = 0; t < ntensors; ++t)
@@ -1829,13 +1951,42 @@ bool slice_ok(int T, long long row_stride, int elem_bytes) {
   return row_stride > 0 && (long long)T * row_stride * elem_bytes < (1ll << 31);
 }
 
-}  // namespace
+// Hkv K / V heads for H query heads: at least one, dividing H
+bool set_kv_heads(AttnShape& s, int Hkv) {
+  if (Hkv < 1 || s.H % Hkv != 0) return false;
+  s.Hkv = Hkv;
+  s.G = s.H / Hkv;
+  s.GS = s.G;
+  return true;
+}
 
-extern "C" int kfamd_attn_fwd_bf16(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int T,
-                                   int D, float scale, int causal, const long long* strides, void* stream) {
+// The dK / dV group split (attn_bwd_dkdv8 GRP): GS query heads of a group per workgroup. Sweeping the whole
+// group (GS = G) shrinks the grid by G (B = 1, Hkv = 2, T = 2048: 32 workgroups on 256 CUs), and a causal grid
+// that only just fills the chip finishes with its heaviest workgroup (key block 0: GS times every query tile).
+// So: the largest divisor GS of G whose grid nk * Hkv * B * (G / GS) has at least 1.5 workgroups per slot
+// (slots = compute units x resident workgroups: 1 at D = 128, 2 at D = 64), else 1 (every query head its own
+// workgroup, as the ungrouped kernel, plus the reduce pass). Measured (profiles/flash_gqa, causal T = 2048,
+// medians of 7 interleaved blocks, us; * = this rule's pick, within the spread of the best everywhere):
+//   4x16 D=128  G=2: GS 2 254* 1 302 | G=4: GS 4 317, 2 268*, 1 300 | G=8: GS 8 503, 4 326, 2 315*, 1 314
+//   16x12 D=64  G=2: GS 2 423* 1 473 | G=4: GS 4 401*, 2 431, 1 465 | G=6: GS 6 449, 3 422*, 2 456, 1 468
+//   1x8 D=128   G=4: GS 4 261, 2 169, 1 125*
+// (the first rule, one workgroup per compute unit, picked GS = 4 at 4x16 G = 4 and 8, and GS = 6 at 16x12 G = 6).
+int gqa_group_split(int B, int H, int Hkv, int T, int D) {
+  const int G = H / Hkv;
+  const long long nkv = (long long)((T + BK - 1) / BK) * Hkv * B;
+  const long long slots = (long long)device_cus() * (D == 64 ? 2 : 1);
+  for (int gs = G; gs > 1; --gs)
+    if (G % gs == 0 && 2 * nkv * (G / gs) >= 3 * slots) return gs;
+  return 1;
+}
+
+long long align16(long long n) { return (n + 15) & ~15ll; }
+
+int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int Hkv, int T,
+                    int D, float scale, int causal, const long long* strides, void* stream) {
   AttnShape s;
   if (!q || !k || !v || !o || !lse) return KFAMD_EINVAL;
-  if (!fill_shape(s, B, H, T, D, scale, strides, 4)) return KFAMD_EINVAL;
+  if (!fill_shape(s, B, H, T, D, scale, strides, 4) || !set_kv_heads(s, Hkv)) return KFAMD_EINVAL;
   if (!al16(q) || !al16(k) || !al16(v) || !al16(o)) return KFAMD_EALIGN;
   const long long nwg = (long long)((T + FQ - 1) / FQ) * H * B;
   if (nwg >= (1ll << 31)) return KFAMD_EINVAL;
@@ -1891,19 +2042,20 @@ extern "C" int kfamd_attn_fwd_bf16(const void* q, const void* k, const void* v, 
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
 
-extern "C" long long kfamd_attn_bwd_workspace(int B, int H, int T, int D) {
-  // nl, nd f32 [B][H][T] (+ dq_acc f32 [B][T][H][D] in front of them when dQ goes through atomics)
-  return (KFATT_DQ_SPLIT ? 0LL : (long long)B * T * H * D * 4) + 2LL * B * H * T * 4;
-}
+// only the default schedule (split dQ kernel with delta, 8-wave dK / dV at both head dims) knows grouped K / V
+constexpr bool kGroupedBwd = KFATT_DQ_SPLIT && KFATT_DQ_DELTA && KFATT_DKDV8 && KFATT_DKDV8_64;
 
-// strides: 8 tensors x (b, h, t): q, k, v, o, do, dq, dk, dv. workspace: kfamd_attn_bwd_workspace bytes
-// (16-B aligned); it is zeroed here on the stream (memset node) before the dQ atomics.
-extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                   const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int T,
-                                   int D, float scale, int causal, const long long* strides, void* stream) {
+// group_split: 0 = gqa_group_split's rule, else the GS to use (a divisor of G). Hkv == H: the ungrouped kernels.
+int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout, const void* lse,
+                    void* dq, void* dk, void* dv, void* workspace, int B, int H, int Hkv, int T, int D, float scale,
+                    int causal, int group_split, const long long* strides, void* stream) {
   AttnShape s;
   if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !workspace) return KFAMD_EINVAL;
-  if (!fill_shape(s, B, H, T, D, scale, strides, 8)) return KFAMD_EINVAL;
+  if (!fill_shape(s, B, H, T, D, scale, strides, 8) || !set_kv_heads(s, Hkv)) return KFAMD_EINVAL;
+  if (group_split < 0 || (group_split > 0 && s.G % group_split != 0)) return KFAMD_EINVAL;
+  const bool grouped = Hkv != H;
+  if (grouped && !kGroupedBwd) return KFAMD_EINVAL;
+  if (grouped) s.GS = group_split > 0 ? group_split : gqa_group_split(B, H, Hkv, T, D);
   if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(dout) || !al16(dq) || !al16(dk) || !al16(dv) ||
       !al16(workspace))
     return KFAMD_EALIGN;
@@ -1938,17 +2090,36 @@ extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, 
     if (KFATT_DQ_DELTA && (D == 128 ? KFATT_DKDV8 : KFATT_DKDV8_64)) {
       // the dQ kernel first, as the prologue too (nl / nd), then the 8-wave dK / dV kernel
       const bool pair = KFATT_DQ_PAIR && causal && ((T + FQ - 1) / FQ) % 2 == 0;
+      // grouped K / V: the dK / dV grid runs over K / V heads and the G / GS parts of each group; the parts'
+      // fp32 sums (GS < G) sit behind nl / nd in the workspace and attn_bwd_gqa_reduce finishes them
+      const long long nkg = grouped ? nk / s.G * (s.G / s.GS) : nk;
+      float* gpart = grouped && s.GS != s.G ? reinterpret_cast<float*>(static_cast<char*>(workspace) + align16(2LL * B * H * T * 4))
+                                            : nullptr;
       auto runq = [&](auto dq_k, auto main_k) {
         hipLaunchKernelGGL(dq_k, dim3((unsigned)(pair ? nq / 2 : nq)), dim3(256), 0, st, static_cast<const __bf16*>(q),
                            static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
                            static_cast<const __bf16*>(dout), static_cast<const float*>(lse),
                            static_cast<const float*>(nullptr), static_cast<__bf16*>(dq), s,
                            static_cast<const __bf16*>(o), nl, nd);
-        hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(512), 0, st, static_cast<const __bf16*>(q),
+        hipLaunchKernelGGL(main_k, dim3((unsigned)nkg), dim3(512), 0, st, static_cast<const __bf16*>(q),
                            static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
                            static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
+                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s, gpart);
+        if (gpart) {
+          const long long krows = (long long)B * Hkv * T;
+          const unsigned kblocks = (unsigned)((krows + 256 / (D / 8) - 1) / (256 / (D / 8)));
+          if (D == 128) hipLaunchKernelGGL(attn_bwd_gqa_reduce<128>, dim3(kblocks), dim3(256), 0, st, gpart,
+                                           static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
+          else hipLaunchKernelGGL(attn_bwd_gqa_reduce<64>, dim3(kblocks), dim3(256), 0, st, gpart,
+                                  static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
+        }
       };
+      if (grouped) {
+        if (D == 128) causal ? runq(attn_bwd_dq_split<128, true, true>, attn_bwd_dkdv8<128, true, true>)
+                             : runq(attn_bwd_dq_split<128, false, true>, attn_bwd_dkdv8<128, false, true>);
+        else causal ? runq(attn_bwd_dq_split<64, true, true>, attn_bwd_dkdv8<64, true, true>)
+                    : runq(attn_bwd_dq_split<64, false, true>, attn_bwd_dkdv8<64, false, true>);
+      } else
       if (pair) D == 128 ? runq(attn_bwd_dq_split<128, true, true, true>, attn_bwd_dkdv8<128, true>)
                          : runq(attn_bwd_dq_split<64, true, true, true>, attn_bwd_dkdv8<64, true>);
       else if (D == 128) causal ? runq(attn_bwd_dq_split<128, true, true>, attn_bwd_dkdv8<128, true>)
@@ -1962,7 +2133,8 @@ extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, 
         hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(512), 0, st, static_cast<const __bf16*>(q),
                            static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
                            static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
+                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s,
+                           static_cast<float*>(nullptr));
         hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
                            static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
                            static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
@@ -1980,7 +2152,8 @@ extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, 
         hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(512), 0, st, static_cast<const __bf16*>(q),
                            static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
                            static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
+                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s,
+                           static_cast<float*>(nullptr));
         hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
                            static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
                            static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
@@ -2012,4 +2185,56 @@ extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, 
               : run(attn_bwd_delta<64>, attn_bwd<64, false>, attn_bwd_dq<64>);
   e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
+}
+
+}  // namespace
+
+extern "C" int kfamd_attn_fwd_bf16(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int T,
+                                   int D, float scale, int causal, const long long* strides, void* stream) {
+  return attn_fwd_launch(q, k, v, o, lse, B, H, H, T, D, scale, causal, strides, stream);
+}
+
+extern "C" long long kfamd_attn_bwd_workspace(int B, int H, int T, int D) {
+  // nl, nd f32 [B][H][T] (+ dq_acc f32 [B][T][H][D] in front of them when dQ goes through atomics)
+  return (KFATT_DQ_SPLIT ? 0LL : (long long)B * T * H * D * 4) + 2LL * B * H * T * 4;
+}
+
+// strides: 8 tensors x (b, h, t): q, k, v, o, do, dq, dk, dv. workspace: kfamd_attn_bwd_workspace bytes
+// (16-B aligned); it is zeroed here on the stream (memset node) before the dQ atomics.
+extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                   const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int T,
+                                   int D, float scale, int causal, const long long* strides, void* stream) {
+  return attn_bwd_launch(q, k, v, o, dout, lse, dq, dk, dv, workspace, B, H, H, T, D, scale, causal, 0, strides, stream);
+}
+
+// ---- grouped K / V heads (kfamd_kernels.h) ----
+extern "C" int kfamd_attn_fwd_gqa_bf16(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H,
+                                       int Hkv, int T, int D, float scale, int causal, const long long* strides,
+                                       void* stream) {
+  return attn_fwd_launch(q, k, v, o, lse, B, H, Hkv, T, D, scale, causal, strides, stream);
+}
+
+extern "C" int kfamd_attn_bwd_gqa_group_split(int B, int H, int Hkv, int T, int D) {
+  if (B <= 0 || H <= 0 || T <= 0 || (D != 64 && D != 128) || Hkv < 1 || H % Hkv != 0) return KFAMD_EINVAL;
+  if (Hkv != H && !kGroupedBwd) return KFAMD_EINVAL;
+  return gqa_group_split(B, H, Hkv, T, D);
+}
+
+extern "C" long long kfamd_attn_bwd_gqa_workspace(int B, int H, int Hkv, int T, int D, int group_split) {
+  const int rule = kfamd_attn_bwd_gqa_group_split(B, H, Hkv, T, D);
+  if (rule < 0) return KFAMD_EINVAL;
+  const int G = H / Hkv;
+  if (group_split < 0 || (group_split > 0 && G % group_split != 0)) return KFAMD_EINVAL;
+  if (Hkv == H) return kfamd_attn_bwd_workspace(B, H, T, D);
+  const int gs = group_split > 0 ? group_split : rule;
+  // nl, nd f32 [B][H][T], then (GS < G) the parts' fp32 sums [dk, dv][G / GS][B][Hkv][T][D]
+  return align16(2LL * B * H * T * 4) + (gs == G ? 0LL : 2LL * (G / gs) * B * Hkv * T * D * 4);
+}
+
+extern "C" int kfamd_attn_bwd_gqa_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                       const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H,
+                                       int Hkv, int T, int D, float scale, int causal, int group_split,
+                                       const long long* strides, void* stream) {
+  return attn_bwd_launch(q, k, v, o, dout, lse, dq, dk, dv, workspace, B, H, Hkv, T, D, scale, causal, group_split,
+                         strides, stream);
 }

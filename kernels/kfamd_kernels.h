@@ -210,6 +210,26 @@ long long kfamd_attn_bwd_workspace(int B, int H, int T, int D);
 int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
                         const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int T,
                         int D, float scale, int causal, const long long* strides, void* stream);
+// Grouped-query attention on the same kernels: k, v (and dk, dv) are [B][Hkv][T][D] views with Hkv dividing H;
+// query head h reads K / V head h / G, G = H / Hkv (the Llama convention of the KV-cache kernels), in place: no
+// expanded copy. q, o, do, dq and lse keep H heads; the grids of the forward and of dQ stay in query heads, so a
+// query head does the arithmetic it does on K / V expanded to H heads, bit for bit. dK / dV: one workgroup sweeps
+// the query tiles of GS query heads of a group (GS divides G) and sums them in fp32 registers. GS = G stores
+// bf16 directly; GS < G writes fp32 parts to the workspace and a reduce kernel adds them in a fixed order (no
+// atomics: both routes are deterministic). group_split: the GS to use, 0 = the launcher's rule, which
+// kfamd_attn_bwd_gqa_group_split returns (the largest divisor of G whose grid ceil(T / 128) * Hkv * B * (G / GS)
+// has 1.5 workgroups per slot, slots = compute units x (D == 64 ? 2 : 1), else 1). kfamd_attn_bwd_gqa_workspace: bytes for that group_split.
+// Hkv == H is kfamd_attn_fwd_bf16 / kfamd_attn_bwd_bf16: the same kernels, grids and bits.
+// KFAMD_EINVAL (group_split / workspace: a negative value): Hkv < 1, H % Hkv != 0, a group_split that does not
+// divide G, and Hkv != H in a build whose backward is not the default schedule (the A/B macros of the .hip).
+int kfamd_attn_fwd_gqa_bf16(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int Hkv,
+                            int T, int D, float scale, int causal, const long long* strides, void* stream);
+int kfamd_attn_bwd_gqa_group_split(int B, int H, int Hkv, int T, int D);
+long long kfamd_attn_bwd_gqa_workspace(int B, int H, int Hkv, int T, int D, int group_split);
+int kfamd_attn_bwd_gqa_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                            const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int Hkv,
+                            int T, int D, float scale, int causal, int group_split, const long long* strides,
+                            void* stream);
 
 // ---- decode (KV-cache generation) ------------------------------------------------------------
 // Everything from here to the FP8 entry points is attn_kv.hip.

@@ -25,9 +25,11 @@ Grouped-query attention: ``GPTConfig(n_kv_heads=Hkv)`` with ``Hkv`` dividing ``n
 ``G = n_heads // Hkv`` query heads one K / V head (query head h reads K / V head ``h // G``); the fused QKV
 projection then has ``(n_heads + 2 * Hkv) * head_dim`` features, ``q | k | v``. The KV cache holds the ``Hkv``
 heads (1 / G of the bytes) and the decode / extend / chunk kernels stream K / V once per group. Training and
-``prefill`` run the flash kernel on K / V expanded to ``n_heads`` heads (a materialised copy; autograd sums dK / dV
-over the group); a GQA-native flash forward / backward, tensor-parallel K / V head sharding and group sizes outside
-{1, 2, 4, 8, 16} on a GPU are not built.
+``prefill`` run the flash kernels on the ``Hkv`` K / V heads in place (``ops.attn_block(kv_heads=...)`` on the fused
+single-rank path, ``ops.attention_qkv(kv_heads=...)`` on the others and in ``prefill``): no expanded copy, dq / dk /
+dv written straight into the ``(n_heads + 2 * Hkv) * head_dim`` QKV gradient, dK / dV summed over a group in fp32
+inside the kernel, for any ``G`` dividing ``n_heads``. Tensor-parallel K / V head sharding and, on the KV-cache
+kernels, group sizes outside {1, 2, 4, 8, 16} are not built.
 
 Rotary position embeddings: ``GPTConfig(pos="rope", rope_theta=...)`` drops the learned position table (no ``pos``
 parameter, nothing of it in ``state_dict()``) and rotates q and k instead (rotate-half over the whole head dim; the
@@ -238,41 +240,44 @@ class Block(torch.nn.Module):
         self.fc2 = tpl.RowParallelLinear(cfg.d_ff, cfg.d_model, group=tp_group, dtype=cfg.dtype, device=device, seed=seed + 4)
 
     def _attention_gqa(self, x, residual, rope=None):
-        """Grouped-query attention of the training forward. The fused ``ops.attn_block`` node (and
-        ``ops.attention_qkv``) assume a ``[3 h hd]`` activation and are bypassed: q and the K / V heads, each
-        repeated over its group (a materialised copy), go through ``ops.flash_attention`` on the native flash
-        kernel, and autograd's backward of the expansion sums dK / dV over the group."""
+        """Grouped-query attention of the training forward off the fused ``ops.attn_block`` path (CPU, other head
+        dims, forced-distributed runs). On the GPU the flash kernels read the ``[B, T, (h + 2 hkv) hd]`` activation
+        in place (``ops.attention_qkv(kv_heads=...)``: every K / V head serves its group, dk / dv summed over the
+        group in the kernel); elsewhere SDPA runs on K / V repeated over the group."""
         B, T, _ = x.shape
         h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
         G = h // hkv
         qkv = self.qkv(x)
         if rope is not None:
             qkv = ops.rope_qkv(qkv, rope, h, hkv)
+        if ops.native_enabled() and ops.attention_supported(qkv, hd):
+            y = ops.attention_qkv(qkv.contiguous(), h, hd, causal=True, kv_heads=hkv)  # [B, T, h * hd]
+            return self.proj(y, residual=residual)
         q = qkv[..., :h * hd].view(B, T, h, hd)
         k, v = qkv[..., h * hd:].view(B, T, 2, hkv, hd).unbind(2)
         k = k.unsqueeze(3).expand(B, T, hkv, G, hd).reshape(B, T, h, hd)
         v = v.unsqueeze(3).expand(B, T, hkv, G, hd).reshape(B, T, h, hd)
         q, k, v = (t.transpose(1, 2) for t in (q, k, v))  # [B, h, T, hd] views
-        if ops.native_enabled() and ops.attention_supported(qkv, hd):
-            y = ops.flash_attention(q, k, v, causal=True)
-        else:
-            y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
 
     def attention(self, x, residual=None, rope=None):
         """``rope``: the model's rotary table (``GPTConfig(pos="rope")``): q and k are rotated right after the QKV
         projection, inside ``ops.attn_block`` on the fused path, by ``ops.rope_qkv`` on the others."""
         B, T, _ = x.shape
-        h, hd = self.local_heads, self.cfg.head_dim
-        if self.local_kv_heads != h:
-            return self._attention_gqa(x, residual, rope)
+        h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
         # the fused single-rank path whenever the TP layers would issue no collective; a forced-distributed
         # run at world size 1 (KFAMD_FORCE_DIST) takes the TP layers and their RCCL all-reduces (ADVICE r5)
         if x.is_cuda and ops.native_enabled() and ops.attention_supported(x, hd) and not tpl._collective(self.tp_group):
             # one autograd node on the HIP path (ops.attn_block): its backward runs the QKV and
             # output-projection weight gradients as one GEMM launch
+            if hkv != h:  # grouped-query attention: the same node on the (h + 2 hkv) hd activation
+                return ops.attn_block(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, h, hd,
+                                      residual=residual, rope=rope, kv_heads=hkv)
             return ops.attn_block(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, h, hd,
                                   residual=residual, rope=rope)
+        if hkv != h:
+            return self._attention_gqa(x, residual, rope)
         qkv = self.qkv(x)  # [B, T, 3 * h * hd] — the column shard is [q_h | k_h | v_h] per rank
         if rope is not None:  # per head: a tensor-parallel shard rotates its own heads
             qkv = ops.rope_qkv(qkv, rope, h, h)
@@ -480,9 +485,8 @@ class GPT(torch.nn.Module):
                 ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
                 if hkv == h:
                     a = ops.attention_qkv(qkv, h, hd, causal=True).view(B * T, h * hd)
-                else:  # the flash kernel on K / V expanded to h heads (a copy)
-                    q, k, v = self._split_gqa(qkv, h, hkv, hd)
-                    a = ops.flash_attention(q, k, v, causal=True).transpose(1, 2).reshape(B * T, h * hd)
+                else:  # grouped K / V heads, read in place by the flash kernel
+                    a = ops.attention_qkv(qkv, h, hd, causal=True, kv_heads=hkv).view(B * T, h * hd)
                 x2 = ops.gemm_nt(a, blk.proj.weight, bias=blk.proj.bias, residual=x2)
                 y = self._fc1(self._auto, blk.ln2.fwd(x2), blk.fc1.weight, blk)  # "auto" like its other linears
                 x = ops.gemm_nt(y, blk.fc2.weight, bias=blk.fc2.bias, residual=x2).view(B, T, c.d_model)

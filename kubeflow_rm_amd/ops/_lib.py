@@ -87,6 +87,12 @@ _SIGNATURES = {
     "kfamd_attn_bwd_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
     "kfamd_attn_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                     c_int, c_float, c_int, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_fwd_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                        ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_bwd_gqa_group_split": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_bwd_gqa_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_bwd_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                        c_int, c_int, c_float, c_int, c_int, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_attn_decode_split_keys": (c_int, []),
     "kfamd_attn_decode_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
     "kfamd_attn_decode_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float,
