@@ -3,6 +3,7 @@
 //   forward:  lse[r] = log sum_j exp(x[r][j]);  loss[r] = lse[r] - x[r][t[r]]  (0 where t = ignore)
 //   backward: dx[r][j] = (exp(x[r][j] - lse[r]) - [j == t[r]]) * scale,  scale = *g / *count read on
 //             the device (no host sync for the upstream gradient or the number of counted rows)
+// -inf logits (masked vocabulary entries) count as exp() = 0 in both; +inf / NaN logits are out of contract.
 // One 256-thread block per row; 16-B loads (8 bf16 per lane per step), the row max / sum meet
 // through wave shuffles and LDS. The forward reads the logits once, the backward reads them once
 // and writes the gradient once: ~1.5x the logits' bytes in total, against widen + softmax forward +
@@ -34,13 +35,16 @@ __device__ __forceinline__ void row_stats(const __bf16* __restrict__ x, int V, b
 #pragma unroll
     for (int k = 1; k < 8; ++k) vm = fmaxf(vm, (float)v[k]);
     if (vm > m) { s *= __expf(m - vm); m = vm; }
+    // masked (-inf) logits: while m is still -inf every value seen is -inf and adds exp(-inf - 0) = 0,
+    // not exp(-inf - -inf) = NaN, which the first finite value's rescale (NaN * 0) would keep
+    const float mf = m == -INFINITY ? 0.f : m;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) s += __expf((float)v[k] - m);
+    for (int k = 0; k < 8; ++k) s += __expf((float)v[k] - mf);
   }
   for (int j = nv * 8 + t; j < V; j += kThreads) {
     const float v = (float)x[j];
     if (v > m) { s *= __expf(m - v); m = v; }
-    s += __expf(v - m);
+    s += __expf(v - (m == -INFINITY ? 0.f : m));
   }
   // combine (m, s) pairs: wave, then across the block's waves
   float wm = wave_max(m);
@@ -85,7 +89,9 @@ __global__ __launch_bounds__(kThreads) void xent_bwd(const __bf16* __restrict__ 
   const long long tg = target[r];
   const bool skip = tg == ignore || tg < 0 || tg >= V;
   const float c = *count;
-  const float scale = (skip || c <= 0.f) ? 0.f : *g / c;
+  const bool dead = skip || c <= 0.f;  // a row that is not counted: +0 everywhere, the ignored index too
+  const float scale = dead ? 0.f : *g / c;
+  const long long hot = dead ? -1 : tg;
   const float l = lse[r];
   const int nv = vec ? V / 8 : 0;
   for (int i = threadIdx.x; i < nv; i += kThreads) {
@@ -94,12 +100,12 @@ __global__ __launch_bounds__(kThreads) void xent_bwd(const __bf16* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int j = i * 8 + k;
-      o[k] = (__bf16)((__expf((float)v[k] - l) - (j == tg ? 1.f : 0.f)) * scale);
+      o[k] = (__bf16)((__expf((float)v[k] - l) - (j == hot ? 1.f : 0.f)) * scale);
     }
     reinterpret_cast<bf16x8*>(d)[i] = o;
   }
   for (int j = nv * 8 + threadIdx.x; j < V; j += kThreads)
-    d[j] = (__bf16)((__expf((float)x[j] - l) - (j == tg ? 1.f : 0.f)) * scale);
+    d[j] = (__bf16)((__expf((float)x[j] - l) - (j == hot ? 1.f : 0.f)) * scale);
 }
 
 }  // namespace

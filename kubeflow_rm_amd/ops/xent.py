@@ -3,7 +3,12 @@
 The forward stores one fp32 log-sum-exp per row; the backward re-reads the logits once and writes
 ``(softmax - onehot) * g / count`` with the upstream gradient and the counted-row total read on the
 device (no host sync). Matches ``F.cross_entropy(logits.float(), target, ignore_index=...)`` with
-the mean reduction.
+the mean reduction. A row whose target is ``ignore_index``, negative or ``>= V`` is not counted: its
+loss is 0 and its gradient row is +0.
+
+``-inf`` logits (masked vocabulary entries) are supported: they add 0 to the row's sum and get a zero
+gradient; a row whose target is itself ``-inf`` has loss ``+inf`` and a finite gradient, as in torch.
+``+inf`` and NaN logits, and a row that is ``-inf`` everywhere, are out of contract, as in torch.
 """
 from __future__ import annotations
 

@@ -78,6 +78,8 @@ class AdamW(torch.optim.Optimizer):
             st = self.state[p]
             ptrs.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                          p.numel()))
+        if not any(n for *_, n in ptrs):  # only empty tensors: no chunk, nothing to launch
+            return
         key = tuple(ptrs)
         cached = self._tables.get((dev, gi))
         if cached is None or cached[0] != key:
