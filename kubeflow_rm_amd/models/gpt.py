@@ -431,6 +431,8 @@ class GPT(torch.nn.Module):
     # ops.attention_decode); CPU tensors and ops.torch_reference() run the same methods on torch ops.
     # Nothing in decode_step depends on a host-side position (the position embedding is gathered by
     # the device-side cache.lens), so it can be captured once into a hipGraph and replayed.
+    # prefill(), decode_step() and extend()'s _extend_chunk() keep the embedding, the positions and cache.advance;
+    # the layer itself is _cache_layer() and the LM head _lm_head(), each written once per path.
 
     def new_cache(self, B: int, capacity: int, device=None, kv_dtype: torch.dtype | None = None) -> "ops.KVCache":
         """A cache for B sequences of up to ``capacity`` tokens. ``kv_dtype``: what the cache stores;
@@ -460,6 +462,33 @@ class GPT(torch.nn.Module):
         if cache._bound + T > cache.capacity:
             raise ValueError(f"cache capacity {cache.capacity} exceeded")
 
+    def _cache_layer(self, blk, li: int, x, cache, *, native: bool, lin, w, attend):
+        """One layer against ``cache``, the body ``prefill``, ``decode_step`` and ``_extend_chunk`` share. They vary
+        ``lin`` (``self._skinny`` or ``self._auto``), ``w(li, name)`` (the weight of "qkv" / "proj" / "fc1" / "fc2":
+        ``_weight_selector``) and ``attend(li, qkv, native)``, the attention over the QKV linear's output as the linear
+        returned it. ``native``: the HIP kernels on ``x [rows, d_model]``, ``attend`` returning ``[rows, h * hd]``; else
+        torch ops (CPU tensors / ops.torch_reference()) on ``x [B, ..., d_model]``, ``attend`` returning that shape.
+        The append also rotates a rotary layer's q and k in place, at positions read from the device-side lens."""
+        h, rope = blk.local_heads, self.rope_table
+        if native:
+            qkv = lin(blk.ln1.fwd(x), w(li, "qkv"), blk.qkv.bias)  # [rows, (h + 2 * hkv) * hd]
+            ops.kv_append(qkv.view(cache.B, -1, qkv.shape[-1]), cache, li, q_heads=h, rope=rope)
+            x = lin(attend(li, qkv, True), w(li, "proj"), blk.proj.bias, residual=x)
+            y = self._fc1(lin, blk.ln2.fwd(x), w(li, "fc1"), blk)
+            return lin(y, w(li, "fc2"), blk.fc2.bias, residual=x)
+        qkv = _flinear(blk.ln1(x), w(li, "qkv"), blk.qkv.bias)
+        ops.kv_append(qkv.view(cache.B, -1, qkv.shape[-1]), cache, li, q_heads=h, rope=rope)
+        x = x + _flinear(attend(li, qkv, False), w(li, "proj"), blk.proj.bias)
+        y = self._fc1_torch(blk.ln2(x), w(li, "fc1"), blk)
+        return x + _flinear(y, w(li, "fc2"), blk.fc2.bias)
+
+    def _lm_head(self, x, w, lin, native: bool):
+        """``ln_f`` -> the tied LM head on the weight ``w`` (``_head_weight``): ``lin`` (``_skinny`` / ``_auto``) over
+        ``x [rows, d_model]`` on the HIP kernels, else torch ops over ``x [..., d_model]``."""
+        if native:
+            return lin(self.ln_f.fwd(x), w)
+        return _flinear(self.ln_f(x), w)
+
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
         """Run the prompt ``idx [B, T0]`` into an empty ``cache``; logits ``[B, vocab]`` of the last position.
@@ -472,38 +501,26 @@ class GPT(torch.nn.Module):
             raise ValueError("prefill expects an empty cache (continuing a cache takes decode_step)")
         native = self._native_decode(self.tok)
         c = self.cfg
+        h, hkv, hd = self.blocks[0].local_heads, self.blocks[0].local_kv_heads, c.head_dim
+        kv = {} if hkv == h else {"kv_heads": hkv}  # grouped K / V heads, read in place by the flash kernel
+
+        def attend(li, qkv, native):  # over the QKV activation itself, which kv_append has rotated (rotary)
+            if native:
+                return ops.attention_qkv(qkv.view(B, T, -1), h, hd, causal=True, **kv).view(B * T, h * hd)
+            q, k, v = self._split_gqa(qkv, h, hkv, hd)
+            return F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
         x = F.embedding(idx, self.tok)
         if self.pos is not None:
             x = x + self.pos[:T]
-        rope = self.rope_table  # rotary: kv_append rotates q and k of qkv in place, the attention below reads them
-        for li, blk in enumerate(self.blocks):
-            h, hkv, hd = blk.local_heads, blk.local_kv_heads, c.head_dim
-            if native:
-                x2 = x.reshape(B * T, c.d_model)
-                y = blk.ln1.fwd(x2)
-                qkv = ops.gemm_nt(y, blk.qkv.weight, bias=blk.qkv.bias).view(B, T, (h + 2 * hkv) * hd)
-                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
-                if hkv == h:
-                    a = ops.attention_qkv(qkv, h, hd, causal=True).view(B * T, h * hd)
-                else:  # grouped K / V heads, read in place by the flash kernel
-                    a = ops.attention_qkv(qkv, h, hd, causal=True, kv_heads=hkv).view(B * T, h * hd)
-                x2 = ops.gemm_nt(a, blk.proj.weight, bias=blk.proj.bias, residual=x2)
-                y = self._fc1(self._auto, blk.ln2.fwd(x2), blk.fc1.weight, blk)  # "auto" like its other linears
-                x = ops.gemm_nt(y, blk.fc2.weight, bias=blk.fc2.bias, residual=x2).view(B, T, c.d_model)
-            else:
-                qkv = F.linear(blk.ln1(x), blk.qkv.weight, blk.qkv.bias)
-                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
-                q, k, v = self._split_gqa(qkv, h, hkv, hd)
-                a = F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
-                x = x + F.linear(a, blk.proj.weight, blk.proj.bias)
-                y = self._fc1_torch(blk.ln2(x), blk.fc1.weight, blk)
-                x = x + F.linear(y, blk.fc2.weight, blk.fc2.bias)
-        cache.advance(T)
-        last = x[:, -1]  # the LM head of the last position only
         if native:
-            last = self.ln_f.fwd(last.contiguous())
-            return ops.gemm_nt(last, self.tok)  # M = B rows: auto routes it as the parent commit did
-        return F.linear(self.ln_f(last), self.tok)
+            x = x.reshape(B * T, c.d_model)
+        w = self._weight_selector(None, B * T)  # the model's own weights, on the "auto" route, whatever B * T is
+        for li, blk in enumerate(self.blocks):
+            x = self._cache_layer(blk, li, x, cache, native=native, lin=self._auto, w=w, attend=attend)
+        cache.advance(T)
+        last = x.view(B, T, c.d_model)[:, -1]  # the LM head of the last position only
+        # M = B rows: auto routes it as the parent commit did
+        return self._lm_head(last.contiguous() if native else last, self.tok, self._auto, native)
 
     @staticmethod
     def _split_gqa(qkv, h: int, hkv: int, hd: int):
@@ -605,37 +622,26 @@ class GPT(torch.nn.Module):
         B = tok.shape[0]
         self._check_cache(cache, B, 1)
         native = self._native_decode(self.tok)
-        c = self.cfg
+        h, hd = self.blocks[0].local_heads, self.cfg.head_dim
         wsel = self._weight_selector(weights, B)
         head_w = self._head_weight(weights, B)
         x = F.embedding(tok, self.tok)  # [B, d_model]
         if self.pos is not None:
             x = x + F.embedding(cache.lens, self.pos)
-        rope = self.rope_table  # rotary: the append rotates q and k in place at position cache.lens, on the device
         # the step's attention sees the row it appends: lens + 1, computed on the device
         att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1)}
+
+        def attend(li, qkv, native):
+            q = qkv[:, :h * hd].view(B, h, hd)
+            if not native:
+                return ops.attention_decode(q, cache, li, **att).reshape(B, h * hd)
+            a = torch.empty(B, h * hd, device=qkv.device, dtype=qkv.dtype)
+            ops.attention_decode(q, cache, li, out=a.view(B, h, hd), **att)
+            return a
         for li, blk in enumerate(self.blocks):
-            h, hd = blk.local_heads, c.head_dim
-            if native:
-                y = blk.ln1.fwd(x)
-                qkv = self._skinny(y, wsel(li, "qkv"), blk.qkv.bias)  # [B, (h + 2 * hkv) * hd]
-                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h, rope=rope)
-                a = torch.empty(B, h * hd, device=x.device, dtype=x.dtype)
-                ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, out=a.view(B, h, hd), **att)
-                x = self._skinny(a, wsel(li, "proj"), blk.proj.bias, residual=x)
-                y = self._fc1(self._skinny, blk.ln2.fwd(x), wsel(li, "fc1"), blk)
-                x = self._skinny(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
-            else:
-                qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
-                ops.kv_append(qkv.view(B, 1, -1), cache, li, q_heads=h, rope=rope)  # torch ops: CPU / torch_reference()
-                a = ops.attention_decode(qkv[:, :h * hd].view(B, h, hd), cache, li, **att).reshape(B, h * hd)
-                x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
-                y = self._fc1_torch(blk.ln2(x), wsel(li, "fc1"), blk)
-                x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
+            x = self._cache_layer(blk, li, x, cache, native=native, lin=self._skinny, w=wsel, attend=attend)
         cache.advance(1)
-        if native:
-            return self._skinny(self.ln_f.fwd(x), head_w)
-        return _flinear(self.ln_f(x), head_w)
+        return self._lm_head(x, head_w, self._skinny, native)
 
     @torch.no_grad()
     def extend(self, idx: torch.Tensor, cache, last_only: bool = False,
@@ -691,50 +697,41 @@ class GPT(torch.nn.Module):
         """One extend step of T tokens per row (T <= 16 on ``ops.attention_extend``; any T with ``mfma``, on
         ``ops.attention_chunk``); ``head``: LM head on "all" rows, the "last", or "none"."""
         B, T = idx.shape
-        attend = ops.attention_chunk if mfma else ops.attention_extend
+        attention = ops.attention_chunk if mfma else ops.attention_extend
         c = self.cfg
+        h, hd = self.blocks[0].local_heads, c.head_dim
         x = F.embedding(idx, self.tok)  # [B, T, d_model]
         if self.pos is not None:
             pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
             x = x + F.embedding(pos, self.pos)
-        rope = self.rope_table
         # the step's attention sees the rows it appends: lens + T, computed on the device
         att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T)}
         lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
         wsel = self._weight_selector(weights, B * T)
+
+        def attend(li, qkv, native):
+            q = qkv[..., :h * hd].view(B, T, h, hd)
+            if not native:
+                return attention(q, cache, li, **att).reshape(B, T, h * hd)
+            a = torch.empty(B, T, h * hd, device=qkv.device, dtype=qkv.dtype)
+            attention(q, cache, li, out=a.view(B, T, h, hd), **att)
+            return a.view(B * T, h * hd)
         if native:
             x = x.reshape(B * T, c.d_model)
         for li, blk in enumerate(self.blocks):
-            h, hd = blk.local_heads, c.head_dim
-            if native:
-                y = blk.ln1.fwd(x)
-                qkv = lin(y, wsel(li, "qkv"), blk.qkv.bias).view(B, T, -1)
-                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)
-                a = torch.empty(B, T, h * hd, device=x.device, dtype=x.dtype)
-                attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, out=a.view(B, T, h, hd), **att)
-                x = lin(a.view(B * T, h * hd), wsel(li, "proj"), blk.proj.bias, residual=x)
-                y = self._fc1(lin, blk.ln2.fwd(x), wsel(li, "fc1"), blk)
-                x = lin(y, wsel(li, "fc2"), blk.fc2.bias, residual=x)
-            else:
-                qkv = _flinear(blk.ln1(x), wsel(li, "qkv"), blk.qkv.bias)
-                ops.kv_append(qkv, cache, li, q_heads=h, rope=rope)  # torch ops: CPU tensors / torch_reference()
-                a = attend(qkv[..., :h * hd].view(B, T, h, hd), cache, li, **att).reshape(B, T, h * hd)
-                x = x + _flinear(a, wsel(li, "proj"), blk.proj.bias)
-                y = self._fc1_torch(blk.ln2(x), wsel(li, "fc1"), blk)
-                x = x + _flinear(y, wsel(li, "fc2"), blk.fc2.bias)
+            x = self._cache_layer(blk, li, x, cache, native=native, lin=lin, w=wsel, attend=attend)
         cache.advance(T)
         if head == "none":
             return None
         x = x.view(B, T, c.d_model)
         if head == "last":
             x = x[:, -1].contiguous()  # [B, d_model]
-        head_w = self._head_weight(weights, x.numel() // c.d_model)
+        rows = x.numel() // c.d_model  # the head's own row count picks its weight and its route
+        head_w = self._head_weight(weights, rows)
+        head_lin = self._skinny if rows <= ops.gemm.SKINNY_MAX_M else self._auto
         if not native:
-            return _flinear(self.ln_f(x), head_w)
-        rows = x.reshape(-1, c.d_model)
-        head_lin = self._skinny if rows.shape[0] <= ops.gemm.SKINNY_MAX_M else self._auto
-        logits = head_lin(self.ln_f.fwd(rows), head_w)
-        return logits.view(*x.shape[:-1], c.vocab_size)
+            return self._lm_head(x, head_w, head_lin, False)
+        return self._lm_head(x.reshape(rows, c.d_model), head_w, head_lin, True).view(*x.shape[:-1], c.vocab_size)
 
     def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int, kv_dtype=None, tw=None,
                         dw=None):

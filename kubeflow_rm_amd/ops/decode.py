@@ -277,37 +277,50 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None
     (``kfamd_kv_append_rope_*``); on the torch path rotate, then the append below. ``rope=None``: no rotation."""
     B, H, D = cache.B, cache.H, cache.D
     Hq = H if q_heads is None else int(q_heads)
-    G = _group("kv_append", Hq, cache, _native(qkv))
+    native = _native(qkv)
+    G = _group("kv_append", Hq, cache, native)
     if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != (Hq + 2 * H) * D:
         raise ValueError(f"kv_append: qkv [B={B}, T, {(Hq + 2 * H) * D}] expected, got {tuple(qkv.shape)}")
-    T = qkv.shape[1]
-    k, v = cache.k[layer], cache.v[layer]
     if rope is not None:
         if rope.dim() != 2 or rope.shape[1] != D or rope.shape[0] < cache.capacity or rope.dtype != torch.float32:
             raise ValueError(f"kv_append: rope must be an fp32 [max_pos >= {cache.capacity}, {D}] table, got "
                              f"{tuple(rope.shape)} {rope.dtype}")
-        if _native(qkv):
+        if native:
             _kv_append_rope_native(qkv, cache, layer, Hq, rope)
             return
         from .rope import rotate_torch  # rows at or beyond the capacity have no table row here: left as they are
         qkv.copy_(rotate_torch(qkv, rope[:cache.capacity], Hq, H, positions=cache.lens))
-    if not _native(qkv):  # [B, T, 3, H, D]: slot 0 the last H query heads (unused), slots 1 and 2 k and v
-        x = qkv[:, :, (Hq - H) * D:].reshape(B, T, 3, H, D)
-    if cache.fp8 and not _native(qkv):
+    if native:
+        _kv_append_native(qkv, cache, layer, Hq, G)
+    else:
+        _kv_append_torch(qkv, cache, layer, Hq)
+
+
+def _kv_append_torch(qkv, cache: KVCache, layer: int, Hq: int) -> None:
+    """The append on torch ops (CPU tensors / ops.torch_reference()); a rotary layer's qkv is already rotated."""
+    B, H, D, T = cache.B, cache.H, cache.D, qkv.shape[1]
+    k, v = cache.k[layer], cache.v[layer]
+    # [B, T, 3, H, D]: slot 0 the last H query heads (unused), slots 1 and 2 k and v
+    x = qkv[:, :, (Hq - H) * D:].reshape(B, T, 3, H, D)
+    if cache.fp8:
         _kv_append_fp8_torch(x, cache, layer)
         return
-    if not _native(qkv):
-        rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=qkv.device).unsqueeze(0)  # [B, T]
-        if cache._bound + T <= cache.capacity:  # no row can fall off the end: one index_put per tensor
-            bidx = torch.arange(B, device=qkv.device).unsqueeze(1).expand(B, T)
-            k[bidx, :, rows] = x[:, :, 1].to(k.dtype)
-            v[bidx, :, rows] = x[:, :, 2].to(v.dtype)
-            return
-        for b in range(B):
-            keep = rows[b] < cache.capacity
-            k[b].index_copy_(1, rows[b][keep], x[b, keep, 1].transpose(0, 1).to(k.dtype))
-            v[b].index_copy_(1, rows[b][keep], x[b, keep, 2].transpose(0, 1).to(v.dtype))
+    rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=qkv.device).unsqueeze(0)  # [B, T]
+    if cache._bound + T <= cache.capacity:  # no row can fall off the end: one index_put per tensor
+        bidx = torch.arange(B, device=qkv.device).unsqueeze(1).expand(B, T)
+        k[bidx, :, rows] = x[:, :, 1].to(k.dtype)
+        v[bidx, :, rows] = x[:, :, 2].to(v.dtype)
         return
+    for b in range(B):
+        keep = rows[b] < cache.capacity
+        k[b].index_copy_(1, rows[b][keep], x[b, keep, 1].transpose(0, 1).to(k.dtype))
+        v[b].index_copy_(1, rows[b][keep], x[b, keep, 2].transpose(0, 1).to(v.dtype))
+
+
+def _kv_append_native(qkv, cache: KVCache, layer: int, Hq: int, G: int) -> None:
+    """The append launch without rotation (``kernels/attn_kv.hip``)."""
+    B, H, D, T = cache.B, cache.H, cache.D, qkv.shape[1]
+    k, v = cache.k[layer], cache.v[layer]
     if qkv.dtype != torch.bfloat16 or qkv.stride(2) != 1:
         raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
     if cache.fp8 and D not in HEAD_DIMS:
@@ -371,74 +384,6 @@ def _attention_decode_torch(q, k, v, lens, scale):
     return F.scaled_dot_product_attention(q.unsqueeze(2), k, v, attn_mask=mask, scale=scale).squeeze(2)
 
 
-def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
-                     out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
-                     t_bound: int | None = None, return_lse: bool = False):
-    """softmax(scale * q k^T) v for one query row per head: q ``[B, H, D]`` (any b / h strides, e.g. a
-    view of the fused QKV output), keys ``0 .. lens[b]-1`` of ``cache`` layer ``layer``. ``out``:
-    optional ``[B, H, D]`` view to write (e.g. of a ``[B, 1, H*D]`` buffer). ``lens`` / ``t_bound``
-    default to the cache's. Grouped-query attention: ``H = G * cache.H`` query heads, head h on K / V head
-    ``h // G``; on a GPU G > 1 runs the group's G rows as ``attention_extend`` does at T = 1: the extend kernel's
-    row slots for G < ``GQA_MFMA_MIN_ROWS``, the MFMA kernel for G = 8 and 16 (K / V streamed once per group; the
-    extend / chunk workspace, allocated on first use and never inside a capture)."""
-    B, D = cache.B, cache.D
-    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != D:
-        raise ValueError(f"attention_decode: q [{B}, G * {cache.H}, {D}] expected, got {tuple(q.shape)}")
-    H = q.shape[1]
-    G = _group("attention_decode", H, cache, _native(q))
-    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-    lens = cache.lens if lens is None else lens
-    t_bound = cache.t_bound if t_bound is None else int(t_bound)
-    k, v = cache.k[layer], cache.v[layer]
-    if not _native(q):
-        if cache.fp8:  # the visible rows, dequantised; then the reference code as it is
-            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1),
-                                       q.dtype if q.is_cuda else torch.float32)
-        k, v = _expand_kv(k, v, G)
-        o = _attention_decode_torch(q, k, v, lens, scale).to(q.dtype)
-        if out is not None:
-            out.copy_(o)
-            o = out
-        if return_lse:
-            s = (q.float().unsqueeze(2) @ k.float().transpose(-1, -2)).squeeze(2) * scale
-            dead = torch.arange(k.shape[2], device=q.device).view(1, 1, -1) >= lens.view(-1, 1, 1)
-            return o, torch.logsumexp(s.masked_fill(dead, float("-inf")), -1)
-        return o
-    if D not in HEAD_DIMS:
-        raise ValueError(f"attention_decode: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
-    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
-        raise ValueError("attention_decode: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
-    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
-        raise ValueError("attention_decode: lens must be a device int32 [B] tensor")
-    if not 1 <= t_bound <= cache.capacity:
-        raise ValueError(f"attention_decode: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
-    if out is None:
-        out = torch.empty(B, H, D, device=q.device, dtype=q.dtype)
-    elif tuple(out.shape) != (B, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
-        raise ValueError(f"attention_decode: out must be a bf16 GPU [{B}, {H}, {D}] view with a contiguous head dim")
-    if _gqa_mfma(1, G):  # the group's G rows on an MFMA tile
-        res = attention_chunk(q.unsqueeze(1), cache, layer, scale=scale, out=out.unsqueeze(1), lens=lens,
-                              t_bound=t_bound, return_lse=return_lse)
-        return (out, res[1].squeeze(1)) if return_lse else out
-    lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
-    if G > 1:  # the group's G rows on the extend kernel's row slots: T = 1, no t stride
-        fn, scales, tag = _entry("kfamd_attn_extend_gqa", cache, layer)
-        rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(),
-                out.data_ptr(), lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B, cache.H,
-                G, D, 1, t_bound, scale,
-                _ll(q.stride(0), 0, q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), 0, out.stride(1),
-                    *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
-        _lib.check(rc, f"attention_decode[{tag}B={B} H={H} G={G} D={D} t_bound={t_bound}]")
-        return (out, lse) if return_lse else out
-    fn, scales, tag = _entry("kfamd_attn_decode", cache, layer)
-    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
-            _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
-                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
-    _lib.check(rc, f"attention_decode[{tag}B={B} H={H} D={D} t_bound={t_bound}]")
-    return (out, lse) if return_lse else out
-
-
 def _attention_extend_torch(q, k, v, lens, scale):
     """Masked fp32 SDPA of T query rows per head, row i over keys 0 .. lens[b]-T+i. A row with no key
     gives zeros and lse = -inf. Returns (o [B, T, H, D] fp32, lse [B, T, H])."""
@@ -454,6 +399,120 @@ def _attention_extend_torch(q, k, v, lens, scale):
     return o.transpose(1, 2), lse.transpose(1, 2)
 
 
+# ---- the front end the three attention ops share ----------------------------------------------------------------
+# Each op is: _attend_args -> (torch path: _attend_torch) -> its own row limit -> _attend_contract -> its launch.
+# The front end comes in two halves because the row limits fire between them. ``what`` names the public function in
+# every message; ``q`` is ``[B, T, H, D]``, or attention_decode's ``[B, H, D]`` (T = 1), and ``out`` has q's shape.
+
+def _attend_args(what: str, q, cache: KVCache, scale, lens, t_bound, rank: int = 4):
+    """The checks of every device and the defaults -> ``(T, G, scale, lens, t_bound)``."""
+    B, D = cache.B, cache.D
+    if q.dim() != rank or q.shape[0] != B or q.shape[-1] != D:
+        raise ValueError(f"{what}: q [{B}, {'T, ' if rank == 4 else ''}G * {cache.H}, {D}] expected, got "
+                         f"{tuple(q.shape)}")
+    T = q.shape[1] if rank == 4 else 1
+    G = _group(what, q.shape[-2], cache, _native(q))
+    if T < 1:
+        raise ValueError(f"{what}: at least one query row expected")
+    return (T, G, float(scale) if scale is not None else 1.0 / math.sqrt(D), cache.lens if lens is None else lens,
+            cache.t_bound if t_bound is None else int(t_bound))
+
+
+def _attend_torch(reference, q, cache: KVCache, layer: int, G: int, scale, out, lens, t_bound, return_lse, dtype):
+    """The torch path (CPU tensors / ops.torch_reference()): ``reference(q, k, v, lens, scale) -> (o, lse)`` over the
+    cache's K / V expanded to q's heads, an FP8 cache's as its visible rows dequantised to ``dtype``."""
+    k, v = cache.k[layer], cache.v[layer]
+    if cache.fp8:
+        k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), dtype)
+    o, lse = reference(q, *_expand_kv(k, v, G), lens, scale)
+    o = o.to(q.dtype)
+    if out is not None:
+        out.copy_(o)
+        o = out
+    return (o, lse) if return_lse else o
+
+
+def _attend_contract(what: str, q, cache: KVCache, layer: int, lens, t_bound, out):
+    """The kernels' contract on a GPU; returns ``out``, allocated when not given."""
+    B, D = cache.B, cache.D
+    if D not in HEAD_DIMS:
+        raise ValueError(f"{what}: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
+    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or cache.k[layer].dtype not in CACHE_DTYPES:
+        raise ValueError(f"{what}: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
+    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
+        raise ValueError(f"{what}: lens must be a device int32 [B] tensor")
+    if not 1 <= t_bound <= cache.capacity:
+        raise ValueError(f"{what}: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
+    if out is None:
+        return torch.empty(q.shape, device=q.device, dtype=q.dtype)
+    if out.shape != q.shape or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
+        raise ValueError(f"{what}: out must be a bf16 GPU {list(q.shape)} view with a contiguous head dim")
+    return out
+
+
+def _attend_launch(what: str, name: str, q, cache: KVCache, layer: int, out, lens, ws, G: int, t_bound: int,
+                   scale: float, return_lse: bool):
+    """``name[_gqa]_{bf16,fp8}(q, k, v, *scales, lens, out, lse, ws, B, (H | Hkv, G), D, T, t_bound, scale, strides,
+    stream)``: the extend and chunk entry points. A rank-3 ``q`` / ``out`` (attention_decode's G rows of a group) is
+    T = 1 with a zero t stride."""
+    B, D, k, v = cache.B, cache.D, cache.k[layer], cache.v[layer]
+    if q.dim() == 4:
+        T, qs, os, dims = q.shape[1], q.stride()[:3], out.stride()[:3], f"T={q.shape[1]} H={q.shape[2]}"
+    else:
+        T, qs, os, dims = 1, (q.stride(0), 0, q.stride(1)), (out.stride(0), 0, out.stride(1)), f"H={q.shape[1]} G={G}"
+    lse = torch.empty(q.shape[:-1], device=q.device, dtype=torch.float32) if return_lse else None
+    fn, scales, tag = _entry(name if G == 1 else name + "_gqa", cache, layer)
+    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
+            lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, *((cache.H,) if G == 1 else (cache.H, G)),
+            D, T, t_bound, scale,
+            _ll(*qs, *k.stride()[:3], *v.stride()[:3], *os, *(n for s in scales for n in s.stride()[:2])),
+            _stream_ptr(q))
+    _lib.check(rc, f"{what}[{tag}B={B} {dims} D={D} t_bound={t_bound}]")
+    return (out, lse) if return_lse else out
+
+
+def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
+                     out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
+                     t_bound: int | None = None, return_lse: bool = False):
+    """softmax(scale * q k^T) v for one query row per head: q ``[B, H, D]`` (any b / h strides, e.g. a
+    view of the fused QKV output), keys ``0 .. lens[b]-1`` of ``cache`` layer ``layer``. ``out``:
+    optional ``[B, H, D]`` view to write (e.g. of a ``[B, 1, H*D]`` buffer). ``lens`` / ``t_bound``
+    default to the cache's. Grouped-query attention: ``H = G * cache.H`` query heads, head h on K / V head
+    ``h // G``; on a GPU G > 1 runs the group's G rows as ``attention_extend`` does at T = 1: the extend kernel's
+    row slots for G < ``GQA_MFMA_MIN_ROWS``, the MFMA kernel for G = 8 and 16 (K / V streamed once per group; the
+    extend / chunk workspace, allocated on first use and never inside a capture)."""
+    what = "attention_decode"
+    _, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound, rank=3)
+    if not _native(q):
+        def reference(q, k, v, lens, scale):  # its own SDPA, not attention_extend's at T = 1; lse only on request
+            o = _attention_decode_torch(q, k, v, lens, scale)
+            if not return_lse:
+                return o, None
+            s = (q.float().unsqueeze(2) @ k.float().transpose(-1, -2)).squeeze(2) * scale
+            dead = torch.arange(k.shape[2], device=q.device).view(1, 1, -1) >= lens.view(-1, 1, 1)
+            return o, torch.logsumexp(s.masked_fill(dead, float("-inf")), -1)
+        return _attend_torch(reference, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
+                             q.dtype if q.is_cuda else torch.float32)
+    out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
+    if _gqa_mfma(1, G):  # the group's G rows on an MFMA tile
+        res = attention_chunk(q.unsqueeze(1), cache, layer, scale=scale, out=out.unsqueeze(1), lens=lens,
+                              t_bound=t_bound, return_lse=return_lse)
+        return (out, res[1].squeeze(1)) if return_lse else out
+    if G > 1:  # the group's G rows on the extend kernel's row slots: T = 1, no t stride
+        return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(), G, t_bound,
+                              scale, return_lse)
+    B, H, D = q.shape
+    k, v = cache.k[layer], cache.v[layer]
+    lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
+    fn, scales, tag = _entry("kfamd_attn_decode", cache, layer)
+    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
+            lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
+            _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
+                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
+    _lib.check(rc, f"attention_decode[{tag}B={B} H={H} D={D} t_bound={t_bound}]")
+    return (out, lse) if return_lse else out
+
+
 def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
                      out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
                      t_bound: int | None = None, return_lse: bool = False):
@@ -465,54 +524,20 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     per 8 query rows (``kernels/attn_kv.hip``). Grouped-query attention: ``H = G * cache.H`` query heads; the
     rows of a K / V head are then the ``T * G`` (token, head-in-group) pairs, and the GPU limit is
     ``T * G <= MAX_EXTEND_ROWS``; with G > 1, ``GQA_MFMA_MIN_ROWS`` rows or more run ``attention_chunk``'s kernel."""
-    B, D = cache.B, cache.D
-    if q.dim() != 4 or q.shape[0] != B or q.shape[3] != D:
-        raise ValueError(f"attention_extend: q [{B}, T, G * {cache.H}, {D}] expected, got {tuple(q.shape)}")
-    T, H = q.shape[1], q.shape[2]
-    G = _group("attention_extend", H, cache, _native(q))
-    if T < 1:
-        raise ValueError("attention_extend: at least one query row expected")
-    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-    lens = cache.lens if lens is None else lens
-    t_bound = cache.t_bound if t_bound is None else int(t_bound)
-    k, v = cache.k[layer], cache.v[layer]
+    what = "attention_extend"
+    T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
     if not _native(q):
-        if cache.fp8:
-            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), torch.float32)
-        o, lse = _attention_extend_torch(q, *_expand_kv(k, v, G), lens, scale)
-        o = o.to(q.dtype)
-        if out is not None:
-            out.copy_(o)
-            o = out
-        return (o, lse) if return_lse else o
+        return _attend_torch(_attention_extend_torch, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
+                             torch.float32)
     if T * G > MAX_EXTEND_ROWS:
         raise ValueError(f"attention_extend: 1 <= T * G <= {MAX_EXTEND_ROWS} query rows per K / V head expected on a "
                          f"GPU, got T = {T}, G = {G}")
-    if D not in HEAD_DIMS:
-        raise ValueError(f"attention_extend: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
-    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
-        raise ValueError("attention_extend: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
-    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
-        raise ValueError("attention_extend: lens must be a device int32 [B] tensor")
-    if not 1 <= t_bound <= cache.capacity:
-        raise ValueError(f"attention_extend: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
-    if out is None:
-        out = torch.empty(B, T, H, D, device=q.device, dtype=q.dtype)
-    elif tuple(out.shape) != (B, T, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
-        raise ValueError(f"attention_extend: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
-                         "head dim")
+    out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if _gqa_mfma(T, G):
         return attention_chunk(q, cache, layer, scale=scale, out=out, lens=lens, t_bound=t_bound,
                                return_lse=return_lse)
-    lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry("kfamd_attn_extend" if G == 1 else "kfamd_attn_extend_gqa", cache, layer)
-    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache._extend_ws().data_ptr(), B,
-            *((H,) if G == 1 else (cache.H, G)), D, T, t_bound, scale,
-            _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
-                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
-    _lib.check(rc, f"attention_extend[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")
-    return (out, lse) if return_lse else out
+    return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(), G, t_bound, scale,
+                          return_lse)
 
 
 def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
@@ -528,50 +553,16 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     tensors and under ``ops.torch_reference()`` it is the same torch code as ``attention_extend``. Grouped-query
     attention: ``H = G * cache.H`` query heads; the kernel tiles the ``T * G`` rows of a K / V head
     (``T * G <= 65535``)."""
-    B, D = cache.B, cache.D
-    if q.dim() != 4 or q.shape[0] != B or q.shape[3] != D:
-        raise ValueError(f"attention_chunk: q [{B}, T, G * {cache.H}, {D}] expected, got {tuple(q.shape)}")
-    T, H = q.shape[1], q.shape[2]
-    G = _group("attention_chunk", H, cache, _native(q))
-    if T < 1:
-        raise ValueError("attention_chunk: at least one query row expected")
-    scale = float(scale) if scale is not None else 1.0 / math.sqrt(D)
-    lens = cache.lens if lens is None else lens
-    t_bound = cache.t_bound if t_bound is None else int(t_bound)
-    k, v = cache.k[layer], cache.v[layer]
+    what = "attention_chunk"
+    T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
     if not _native(q):
-        if cache.fp8:
-            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), torch.float32)
-        o, lse = _attention_extend_torch(q, *_expand_kv(k, v, G), lens, scale)
-        o = o.to(q.dtype)
-        if out is not None:
-            out.copy_(o)
-            o = out
-        return (o, lse) if return_lse else o
+        return _attend_torch(_attention_extend_torch, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
+                             torch.float32)
     if T > cache.capacity:
         raise ValueError(f"attention_chunk: 1 <= T <= capacity ({cache.capacity}) query rows expected on a GPU, "
                          f"got {T}")
-    if D not in HEAD_DIMS:
-        raise ValueError(f"attention_chunk: head dim in {HEAD_DIMS} expected on a GPU, got {D}")
-    if q.dtype != torch.bfloat16 or q.stride(-1) != 1 or k.dtype not in CACHE_DTYPES:
-        raise ValueError("attention_chunk: bf16 q (contiguous head dim) and a bf16 or float8_e4m3fn cache expected")
-    if lens.dtype != torch.int32 or not lens.is_cuda or lens.numel() != B or not lens.is_contiguous():
-        raise ValueError("attention_chunk: lens must be a device int32 [B] tensor")
-    if not 1 <= t_bound <= cache.capacity:
-        raise ValueError(f"attention_chunk: 1 <= t_bound <= capacity ({cache.capacity}) expected, got {t_bound}")
-    if out is None:
-        out = torch.empty(B, T, H, D, device=q.device, dtype=q.dtype)
-    elif tuple(out.shape) != (B, T, H, D) or out.dtype != torch.bfloat16 or out.stride(-1) != 1 or not out.is_cuda:
-        raise ValueError(f"attention_chunk: out must be a bf16 GPU [{B}, {T}, {H}, {D}] view with a contiguous "
-                         "head dim")
-    lse = torch.empty(B, T, H, device=q.device, dtype=torch.float32) if return_lse else None
+    out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if G > 1 and T * G > 65535:
         raise ValueError(f"attention_chunk: T * G <= 65535 query rows per K / V head expected, got T = {T}, G = {G}")
-    fn, scales, tag = _entry("kfamd_attn_chunk" if G == 1 else "kfamd_attn_chunk_gqa", cache, layer)
-    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache._chunk_ws(T, G).data_ptr(), B,
-            *((H,) if G == 1 else (cache.H, G)), D, T, t_bound, scale,
-            _ll(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *out.stride()[:3],
-                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
-    _lib.check(rc, f"attention_chunk[{tag}B={B} T={T} H={H} D={D} t_bound={t_bound}]")
-    return (out, lse) if return_lse else out
+    return _attend_launch(what, "kfamd_attn_chunk", q, cache, layer, out, lens, cache._chunk_ws(T, G), G, t_bound,
+                          scale, return_lse)
