@@ -149,6 +149,18 @@ int kfamd_layernorm_fwd_bf16(const void* x, const void* gamma, const void* beta,
 int kfamd_rmsnorm_fwd_bf16(const void* x, const void* gamma, void* y, float* rstd,
                            int rows, int hidden, float eps, void* stream);
 
+// The two forwards with the launch path forced (tests / bench); rms != 0: RMSNorm (beta and mean are ignored).
+//   path 0: the launcher's rule   1: one-shot wave per row (hidden 512 * {1,2,3,4,5,6,8,10,12,16} on 16-B pointers,
+//   256 * {1,3,5} on 8-B pointers)   2: streaming (hidden 512 * {1,2,3,4,5,6,8} double-buffered, 8192 rolling reload;
+//   16-B pointers)   3: one workgroup per row (any hidden, any alignment)
+//   blocks: the streaming kernel's grid in workgroups of 4 waves, 0 = the launcher's.
+// A path the shape or the alignment cannot take, a path outside 0 .. 3 or blocks < 0: KFAMD_EINVAL, nothing launched.
+int kfamd_norm_fwd_bf16_path(int rms, int path, int blocks, const void* x, const void* gamma, const void* beta, void* y,
+                             float* mean, float* rstd, int rows, int hidden, float eps, void* stream);
+// the path (1 .. 3) that path 0 takes for this shape on 16-B aligned pointers on the current device; KFAMD_EINVAL
+// for rows or hidden < 1
+int kfamd_norm_fwd_path_for(int rms, int rows, int hidden);
+
 // LayerNorm backward. dx: [rows][hidden] bf16. dgamma/dbeta: fp32 [hidden] (fully written).
 // workspace: fp32 scratch of kfamd_layernorm_bwd_workspace(rows, hidden) bytes.
 long long kfamd_layernorm_bwd_workspace(int rows, int hidden);
@@ -444,6 +456,15 @@ int kfamd_swiglu_bwd_bf16(const void* dh, const void* z, void* dz, long long row
 // kfamd_layernorm_bwd_workspace bytes (required with dgamma).
 int kfamd_rmsnorm_bwd_bf16(const void* dy, const void* dres, const void* x, const void* gamma, const float* rstd,
                            void* dx, void* dgamma, int dgb_bf16, float* workspace, int rows, int hidden, void* stream);
+// kfamd_layernorm_bwd_bf16_v3 / kfamd_rmsnorm_bwd_bf16 (rms != 0: mean and dbeta are ignored) with the launch path
+// forced (tests / bench), whatever KFAMD_LN_BWD_SPLIT says:
+//   path 0: the launcher's rule   1: fused dx + column partials in one pass (dgamma or dbeta given; hidden 512 *
+//   {1,2,3,4} on 16-B pointers, 256 * {1,3,5} on 8-B pointers)   2: dx wave per row (the forward's widths and
+//   alignment), then the column partials   3: dx one workgroup per row (any hidden, any alignment), then the partials
+// A path the shape or the alignment cannot take, or outside 0 .. 3: KFAMD_EINVAL, nothing launched.
+int kfamd_norm_bwd_bf16_path(int rms, int path, const void* dy, const void* dres, const void* x, const void* gamma,
+                             const float* mean, const float* rstd, void* dx, void* dgamma, void* dbeta, int dgb_bf16,
+                             float* workspace, int rows, int hidden, void* stream);
 
 // Token sampling (sample_bf16.hip): one token per row of bf16 logits [B][V] (row stride ld elements, the
 // vocabulary contiguous, 2-byte alignment only; 1 <= V <= 2^20; -inf allowed, NaN / an all -inf row out of

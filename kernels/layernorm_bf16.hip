@@ -584,49 +584,73 @@ long long resident_rows() {
 // one-shot kernel stays. Hidden 8192 streams with the rolling reload up to two generations
 // (4096 x 8192 26.6 -> 24.7 us, 8192 x 8192 48.3-49.3 -> 47.7 us) and is 2.5-6 % slower beyond, where
 // the one-shot kernel with gamma / beta prefetched runs (32768 x 8192: 178.8 us, 6.0 TB/s).
+// path: 0 = the rule above, 1 = one-shot wave-per-row, 2 = streaming, 3 = block kernel; a path the width or the
+// alignment cannot take is KFAMD_EINVAL (nothing launched). blocks: the streaming grid, 0 = the launcher's.
+// picked: a dry run; nothing is launched (pointers count as aligned) and the path chosen is stored there.
+enum { kPathAuto = 0, kPathWave = 1, kPathStream = 2, kPathBlock = 3 };
+
 template <bool RMS>
-int norm_fwd(const void* x, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
-             int rows, int hidden, float eps, void* stream) {
-  if (!x || !gamma || !y || rows <= 0 || hidden <= 0) return KFAMD_EINVAL;
+int norm_fwd(int path, int blocks, const void* x, const void* gamma, const void* beta, void* y, float* mean,
+             float* rstd, int rows, int hidden, float eps, void* stream, int* picked = nullptr) {
+  const bool dry = picked != nullptr;
+  if ((!dry && (!x || !gamma || !y)) || rows <= 0 || hidden <= 0) return KFAMD_EINVAL;
+  if (path < kPathAuto || path > kPathBlock || blocks < 0) return KFAMD_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const __bf16* xp = static_cast<const __bf16*>(x);
   const __bf16* gp = static_cast<const __bf16*>(gamma);
   const __bf16* bp = static_cast<const __bf16*>(beta);
   __bf16* yp = static_cast<__bf16*>(y);
   const int vpl = vpl_for(hidden);
-  const bool vec = vpl && a16(x) && a16(gamma) && a16(y) && (!beta || a16(beta));
+  const bool vec = path != kPathBlock && vpl && (dry || (a16(x) && a16(gamma) && a16(y) && (!beta || a16(beta))));
+  const int v4 = path != kPathBlock && !vec ? vpl4_for(hidden) : 0;
+  const bool vec4 = v4 && (dry || (a8(x) && a8(gamma) && a8(y) && (!beta || a8(beta))));
+  int took = kPathBlock;
   if (vec) {
     dim3 grid((rows + 3) / 4), block(256);
     switch (vpl) {
 #define KFAMD_NORM_FWD_CASE(V)                                                                                   \
-  case V:                                                                                                      \
-    if (V == 16 && rows <= 2 * resident_rows<norm_fwd_wave<V, RMS>>()) {                        \
-      const long long waves = resident_rows<norm_fwd_stream<16, RMS, true>>();                                  \
-      const long long rpw = (rows + waves - 1) / waves;                                                        \
-      hipLaunchKernelGGL((norm_fwd_stream<16, RMS, true>), dim3((int)((rows + 4 * rpw - 1) / (4 * rpw))),     \
-                         block, 0, s, xp, gp, bp, yp, mean, rstd, rows, eps);                                  \
-    } else if (V <= 8 && rows > resident_rows<norm_fwd_wave<V, RMS>>() &&                       \
-        rows <= 2 * resident_rows<norm_fwd_wave<V, RMS>>()) {                                       \
-      const long long waves = resident_rows<norm_fwd_stream<V <= 8 ? V : 8, RMS>>();                             \
+  case V: {                                                                                                    \
+    constexpr bool kRoll = V == 16, kCanStream = V <= 8 || V == 16;                                            \
+    constexpr int SV = kRoll ? 16 : (V <= 8 ? V : 8); /* V 10 / 12 never stream: no instantiation of their own */ \
+    took = path;                                                                                               \
+    if (path == kPathAuto) {                                                                                   \
+      took = kPathWave;                                                                                        \
+      if (kCanStream) {                                                                                        \
+        const long long res = resident_rows<norm_fwd_wave<V, RMS>>();                                          \
+        if (rows <= 2 * res && (kRoll || rows > res)) took = kPathStream;                                      \
+      }                                                                                                        \
+    }                                                                                                          \
+    if (took == kPathStream && !kCanStream) return KFAMD_EINVAL;                                               \
+    if (dry) break;                                                                                            \
+    if (took == kPathStream) {                                                                                 \
+      const long long waves = resident_rows<norm_fwd_stream<SV, RMS, kRoll>>();                                \
       const long long rpw = (rows + waves - 1) / waves; /* rows per wave, the same for every wave */          \
-      hipLaunchKernelGGL((norm_fwd_stream<V <= 8 ? V : 8, RMS>), dim3((int)((rows + 4 * rpw - 1) / (4 * rpw))), \
-                         block, 0, s, xp, gp, bp, yp, mean, rstd, rows, eps);                                  \
+      const int nblk = blocks ? blocks : (int)((rows + 4 * rpw - 1) / (4 * rpw));                              \
+      hipLaunchKernelGGL((norm_fwd_stream<SV, RMS, kRoll>), dim3(nblk), block, 0, s, xp, gp, bp, yp, mean, rstd, \
+                         rows, eps);                                                                           \
     } else {                                                                                                   \
       hipLaunchKernelGGL((norm_fwd_wave<V, RMS, 8, V == 16>), grid, block, 0, s, xp, gp, bp, yp, mean, rstd, rows, eps); \
     }                                                                                                          \
-    break;
+  } break;
       KFAMD_FOR_EACH_VPL(KFAMD_NORM_FWD_CASE)
 #undef KFAMD_NORM_FWD_CASE
     }
-  } else if (const int v4 = vpl4_for(hidden); v4 && a8(x) && a8(gamma) && a8(y) && (!beta || a8(beta))) {
+  } else if (vec4) {
+    if (path == kPathStream) return KFAMD_EINVAL;
+    took = kPathWave;
     dim3 grid((rows + 3) / 4), block(256);
-    switch (v4) {
+    if (!dry) switch (v4) {
       case 1: hipLaunchKernelGGL((norm_fwd_wave<1, RMS, 4>), grid, block, 0, s, xp, gp, bp, yp, mean, rstd, rows, eps); break;
       case 3: hipLaunchKernelGGL((norm_fwd_wave<3, RMS, 4>), grid, block, 0, s, xp, gp, bp, yp, mean, rstd, rows, eps); break;
       case 5: hipLaunchKernelGGL((norm_fwd_wave<5, RMS, 4>), grid, block, 0, s, xp, gp, bp, yp, mean, rstd, rows, eps); break;
     }
   } else {
-    hipLaunchKernelGGL((norm_fwd_block<RMS>), dim3(rows), dim3(256), 0, s, xp, gp, bp, yp, mean, rstd, hidden, eps);
+    if (path == kPathWave || path == kPathStream) return KFAMD_EINVAL;
+    if (!dry) hipLaunchKernelGGL((norm_fwd_block<RMS>), dim3(rows), dim3(256), 0, s, xp, gp, bp, yp, mean, rstd, hidden, eps);
+  }
+  if (dry) {
+    *picked = took;
+    return KFAMD_OK;
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
@@ -637,12 +661,26 @@ int norm_fwd(const void* x, const void* gamma, const void* beta, void* y, float*
 extern "C" int kfamd_layernorm_fwd_bf16(const void* x, const void* gamma, const void* beta, void* y,
                                         float* mean, float* rstd, int rows, int hidden, float eps,
                                         void* stream) {
-  return norm_fwd<false>(x, gamma, beta, y, mean, rstd, rows, hidden, eps, stream);
+  return norm_fwd<false>(kPathAuto, 0, x, gamma, beta, y, mean, rstd, rows, hidden, eps, stream);
 }
 
 extern "C" int kfamd_rmsnorm_fwd_bf16(const void* x, const void* gamma, void* y, float* rstd,
                                       int rows, int hidden, float eps, void* stream) {
-  return norm_fwd<true>(x, gamma, nullptr, y, nullptr, rstd, rows, hidden, eps, stream);
+  return norm_fwd<true>(kPathAuto, 0, x, gamma, nullptr, y, nullptr, rstd, rows, hidden, eps, stream);
+}
+
+extern "C" int kfamd_norm_fwd_bf16_path(int rms, int path, int blocks, const void* x, const void* gamma,
+                                        const void* beta, void* y, float* mean, float* rstd, int rows, int hidden,
+                                        float eps, void* stream) {
+  return rms ? norm_fwd<true>(path, blocks, x, gamma, nullptr, y, nullptr, rstd, rows, hidden, eps, stream)
+             : norm_fwd<false>(path, blocks, x, gamma, beta, y, mean, rstd, rows, hidden, eps, stream);
+}
+
+extern "C" int kfamd_norm_fwd_path_for(int rms, int rows, int hidden) {
+  int picked = 0;
+  const int rc = rms ? norm_fwd<true>(kPathAuto, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rows, hidden, 0.f, nullptr, &picked)
+                     : norm_fwd<false>(kPathAuto, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rows, hidden, 0.f, nullptr, &picked);
+  return rc == KFAMD_OK ? picked : rc;
 }
 
 extern "C" long long kfamd_layernorm_bwd_workspace(int rows, int hidden) {
@@ -653,13 +691,20 @@ extern "C" long long kfamd_layernorm_bwd_workspace(int rows, int hidden) {
 // dgamma / dbeta: fp32, or bf16 (the parameter dtype) when dgb_bf16; sums accumulate in fp32 either way.
 // dres (optional, same layout as dx): dx = dres + the LayerNorm input gradient — the pre-norm
 // residual stream's two gradient contributions summed in the dx store.
+// path: 0 = the rule below, 1 = fused (ln_bwd_fused, needs dgamma or dbeta), 2 = the dx wave kernel + column partials,
+// 3 = the dx block kernel + column partials; a path the width or the alignment cannot take is KFAMD_EINVAL (nothing
+// launched). A forced path does not read KFAMD_LN_BWD_SPLIT.
 namespace {
+enum { kBwdAuto = 0, kBwdFused = 1, kBwdWave = 2, kBwdBlock = 3 };
+
 template <bool RMS>
-int norm_bwd(const void* dy, const void* dres, const void* x, const void* gamma, const float* mean, const float* rstd,
-             void* dx, void* dgamma, void* dbeta, int dgb_bf16, float* workspace, int rows, int hidden, void* stream) {
+int norm_bwd(int path, const void* dy, const void* dres, const void* x, const void* gamma, const float* mean,
+             const float* rstd, void* dx, void* dgamma, void* dbeta, int dgb_bf16, float* workspace, int rows,
+             int hidden, void* stream) {
   if (!dy || !x || !gamma || (!RMS && !mean) || !rstd || !dx || rows <= 0 || hidden <= 0) return KFAMD_EINVAL;
   if (dres == dx) return KFAMD_EINVAL;
   if ((dgamma || dbeta) && !workspace) return KFAMD_EINVAL;
+  if (path < kBwdAuto || path > kBwdBlock) return KFAMD_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const __bf16* dyp = static_cast<const __bf16*>(dy);
   const __bf16* xp = static_cast<const __bf16*>(x);
@@ -667,13 +712,15 @@ int norm_bwd(const void* dy, const void* dres, const void* x, const void* gamma,
   __bf16* dxp = static_cast<__bf16*>(dx);
   const __bf16* rp = static_cast<const __bf16*>(dres);
   const int vpl = vpl_for(hidden);
-  const bool vec = vpl && a16(dy) && a16(x) && a16(gamma) && a16(dx) && (!dres || a16(dres));
-  const int v4 = vec ? 0 : vpl4_for(hidden);
+  const bool vec = path != kBwdBlock && vpl && a16(dy) && a16(x) && a16(gamma) && a16(dx) && (!dres || a16(dres));
+  const int v4 = vec || path == kBwdBlock ? 0 : vpl4_for(hidden);
   const bool vec4 = v4 && a8(dy) && a8(x) && a8(gamma) && a8(dx) && (!dres || a8(dres));
   // dx + dgamma / dbeta in one pass (ln_bwd_fused) where the sums fit beside the row: hidden <= 2048
   // (W = 8) or 256 x {1, 3, 5} (W = 4); KFAMD_LN_BWD_SPLIT=1 forces the split path (A/B runs)
   static const bool force_split = [] { const char* e = getenv("KFAMD_LN_BWD_SPLIT"); return e && *e == '1'; }();
-  const bool fused = (dgamma || dbeta) && !force_split && ((vec && vpl <= 4) || vec4);
+  const bool can_fuse = (dgamma || dbeta) && ((vec && vpl <= 4) || vec4);
+  if ((path == kBwdFused && !can_fuse) || (path == kBwdWave && !vec && !vec4)) return KFAMD_EINVAL;
+  const bool fused = path == kBwdAuto ? can_fuse && !force_split : path == kBwdFused;
   if (fused) {
     int nblk = (rows + kFusedWaves - 1) / kFusedWaves;
     if (nblk > kFusedBlocks) nblk = kFusedBlocks;
@@ -728,7 +775,17 @@ int norm_bwd(const void* dy, const void* dres, const void* x, const void* gamma,
 extern "C" int kfamd_layernorm_bwd_bf16_v3(const void* dy, const void* dres, const void* x, const void* gamma,
                                            const float* mean, const float* rstd, void* dx, void* dgamma, void* dbeta,
                                            int dgb_bf16, float* workspace, int rows, int hidden, void* stream) {
-  return norm_bwd<false>(dy, dres, x, gamma, mean, rstd, dx, dgamma, dbeta, dgb_bf16, workspace, rows, hidden, stream);
+  return norm_bwd<false>(kBwdAuto, dy, dres, x, gamma, mean, rstd, dx, dgamma, dbeta, dgb_bf16, workspace, rows, hidden,
+                         stream);
+}
+
+extern "C" int kfamd_norm_bwd_bf16_path(int rms, int path, const void* dy, const void* dres, const void* x,
+                                        const void* gamma, const float* mean, const float* rstd, void* dx, void* dgamma,
+                                        void* dbeta, int dgb_bf16, float* workspace, int rows, int hidden, void* stream) {
+  return rms ? norm_bwd<true>(path, dy, dres, x, gamma, nullptr, rstd, dx, dgamma, nullptr, dgb_bf16, workspace, rows,
+                              hidden, stream)
+             : norm_bwd<false>(path, dy, dres, x, gamma, mean, rstd, dx, dgamma, dbeta, dgb_bf16, workspace, rows,
+                               hidden, stream);
 }
 
 // RMSNorm backward from the forward's saved rstd: dx = rstd * (gamma dy - xhat * mean(gamma dy xhat)) (+ dres),
@@ -738,8 +795,8 @@ extern "C" int kfamd_layernorm_bwd_bf16_v3(const void* dy, const void* dres, con
 extern "C" int kfamd_rmsnorm_bwd_bf16(const void* dy, const void* dres, const void* x, const void* gamma,
                                       const float* rstd, void* dx, void* dgamma, int dgb_bf16, float* workspace,
                                       int rows, int hidden, void* stream) {
-  return norm_bwd<true>(dy, dres, x, gamma, nullptr, rstd, dx, dgamma, nullptr, dgb_bf16, workspace, rows, hidden,
-                        stream);
+  return norm_bwd<true>(kBwdAuto, dy, dres, x, gamma, nullptr, rstd, dx, dgamma, nullptr, dgb_bf16, workspace, rows,
+                        hidden, stream);
 }
 
 extern "C" int kfamd_layernorm_bwd_bf16_v2(const void* dy, const void* x, const void* gamma, const float* mean,

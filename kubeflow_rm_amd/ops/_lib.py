@@ -62,6 +62,11 @@ _SIGNATURES = {
                                    c_vp, c_int, c_vp]),
     "kfamd_layernorm_fwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_vp]),
     "kfamd_rmsnorm_fwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_vp]),
+    "kfamd_norm_fwd_bf16_path": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                                         c_float, c_vp]),
+    "kfamd_norm_fwd_path_for": (c_int, [c_int, c_int, c_int]),
+    "kfamd_norm_bwd_bf16_path": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                                         c_vp, c_int, c_int, c_vp]),
     "kfamd_layernorm_bwd_workspace": (c_ll, [c_int, c_int]),
     "kfamd_layernorm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                          c_int, c_int, c_vp]),

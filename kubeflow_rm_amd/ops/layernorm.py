@@ -11,6 +11,8 @@ def layer_norm_fwd(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | N
                    save_stats: bool = False):
     _check_operand(x, "x")
     _check_operand(weight, "weight")
+    if bias is not None:
+        _check_operand(bias, "bias")
     H = x.shape[-1]
     x2 = x.reshape(-1, H).contiguous()
     rows = x2.shape[0]
@@ -30,6 +32,7 @@ def layer_norm_fwd(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | N
 
 def rms_norm_fwd(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6, save_stats: bool = False):
     _check_operand(x, "x")
+    _check_operand(weight, "weight")
     H = x.shape[-1]
     x2 = x.reshape(-1, H).contiguous()
     y = torch.empty_like(x2)
