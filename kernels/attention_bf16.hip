@@ -15,14 +15,15 @@
 //     O^T[d][q]   += V^T . P^T        A = V columns (LDS, ds_read_b64_tr_b16), B = P^T = the S^T
 //                                     accumulator in bf16 (query on the lane: the online-softmax
 //                                     max / sum / rescale of a row stay in its lane pair)
-//   backward, per wave = 32 keys, per 32-query tile (keys on the lane):
+//   backward dK / dV (attn_bwd_dkdv8), per wave = 32 keys, per 32-query tile (keys on the lane):
 //     S[q][key]   = Q . K^T - lse/scale    (the row constant preloaded into the accumulator)
 //     dP[q][key]  = dO . V^T - delta       (delta = rowsum(dO * O), preloaded the same way)
 //     dV^T[d][key] += dO^T . P             A = dO columns (tr reads), B = P accumulator
 //     dK^T[d][key] += Q^T . dS             A = Q columns (tr reads),  B = dS accumulator
-//     dQ[q][d]    += dS . K                dS crosses LDS once as a [key][q] image (tr reads for
-//                                          the A operand), K columns by tr reads; one wave per
-//                                          32-column d slice, f32 atomics into a workspace
+//   backward dQ (attn_bwd_dq_split, runs first), per wave = 32 query rows, per 64-key tile, as the
+//   forward: S^T and dP^T recomputed with the query on the lane, dS^T the B operand of
+//     dQ^T[d][q]  += K^T . dS^T            A = K columns (tr reads); written once as bf16, no atomics.
+//   It also computes delta and writes both row constants for the dK / dV kernel.
 //
 // LDS images: one swizzle per head dim serves both the row reads (ds_read_b128 of a 16-B chunk
 // by 32 different rows) and the transposed reads (ds_read_b64_tr_b16 of 4 consecutive rows by 32
@@ -80,7 +81,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-// Work order (KFATT_LPT). A causal pass's blocks differ in work: query block i of the forward sees
+// Work order (profiles/r5zb_attn_lpt). A causal pass's blocks differ in work: query block i of the forward sees
 // i + 1 key tiles, key block i of the backward sees the queries from i on. The hardware deals
 // workgroups to the 8 XCDs round-robin (bid % 8) and each XCD starts its share in bid order, so a
 // head-major order left the heaviest blocks of an XCD's last heads to start when the rest was done
@@ -88,14 +89,11 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // [x BH/8, (x+1) BH/8) and walks them in groups of G heads, the fewest whose blocks fill its slots:
 // the heaviest rank of every head of the group first (longest-processing-time order), the group's
 // K / V shared in the XCD's L2. rank 0 = the heaviest block. Other head counts: the plain order.
-#ifndef KFATT_LPT
-#define KFATT_LPT 1
-#endif
 struct BlockId {
   int bh, rank;
 };
 __device__ __forceinline__ BlockId block_order(int bid, int nblk, int BH, int slots) {
-  if (KFATT_LPT && (BH & 7) == 0) {
+  if ((BH & 7) == 0) {
     const int hpx = BH >> 3, xcd = bid & 7, i = bid >> 3;
     int G = 1;
     while (G < hpx && (G * nblk < slots || hpx % G != 0)) ++G;
@@ -107,59 +105,14 @@ __device__ __forceinline__ BlockId block_order(int bid, int nblk, int BH, int sl
   return {lid / nblk, lid % nblk};
 }
 
-// KFATT_BUF: row-guarded loads and the dQ atomics as raw buffer operations over one (b, h) slice
-// whose range ends at row T: a row past T reads as zero / is dropped by the address unit, so the
-// inner loops carry no per-row branches (a divergent `if (row < T)` around each load / atomic split
-// the loops into ~30 basic blocks and cost the scheduler and the register allocator). The host
-// requires every slice's extent below 2^31 bytes (32-bit buffer offsets).
-#ifndef KFATT_BUF
-#define KFATT_BUF 1
-#endif
-#ifndef KFATT_ABL
-#define KFATT_ABL 0  // timing ablations (tools/attn_ab.py builds): 1 = dQ atomics dropped
-#endif
-// Backward schedule (profiles/r5q_attn_split, tools/attn_ab.py variants, one box, 2 rounds each):
-//   gpt-1b 4x16x2048x128 bwd: register-staged + dQ atomics 570 us; + LDS-DMA staging 557-568; the
-//   atomics dropped (timing only) 525-545; the atomic-free dQ kernel 482 (-15 %); D = 64
-//   (16x12x2048): 827-832 -> 557-559 (-33 %: at D = 64 the fp32 atomics are a third of the pass);
-//   1x16x4096x128: 489-495 -> 417-419. The forward with LDS-DMA K / V was 2-7 % slower: kept off.
-#ifndef KFATT_DQ_SPLIT
-#define KFATT_DQ_SPLIT 1  // dQ by the atomic-free attn_bwd_dq_split kernel (recomputes S and dP)
-#endif
-#ifndef KFATT_DMA
-#define KFATT_DMA 1  // backward Q / dO tiles by LDS-DMA (attn_bwd stage_dma)
-#endif
-#ifndef KFATT_DKDV8
-#define KFATT_DKDV8 1  // D = 128 dK / dV with 8 waves (two per SIMD), attn_bwd_dkdv8 (profiles/r5w_attn_dkdv8)
-#endif
-#ifndef KFATT_DKDV8_64
-#define KFATT_DKDV8_64 1  // D = 64 with the 8-wave dK / dV kernel too (16x12x2048x64: 516 -> 485 us)
-#endif
-#ifndef KFATT_DQ_DELTA
-#define KFATT_DQ_DELTA 1  // the dQ kernel computes delta (runs first; no separate prologue kernel): gpt-1b bwd -5 %
-#endif
-#ifndef KFATT_FWD_OFFS
-#define KFATT_FWD_OFFS 1  // forward: LDS read offsets precomputed per lane, buffers unrolled
-#endif
-#ifndef KFATT_FWD_PAIR
-#define KFATT_FWD_PAIR 1  // causal forward: heavy + light query block per workgroup (attn_fwd PAIR, profiles/r5zm_fpair)
-#endif
-#ifndef KFATT_FWD_NW
-#define KFATT_FWD_NW 4  // forward workgroup: 4 waves (two workgroups per CU) or 8 (one; A/B runs)
-#endif
-#ifndef KFATT_DKDV_ABL
-#define KFATT_DKDV_ABL 0  // attn_bwd_dkdv8 timing ablations (tools/attn_ab.py builds; wrong results)
-#endif
-#ifndef KFATT_DQ_PAIR
-#define KFATT_DQ_PAIR 0  // the same for the dQ kernel (attn_bwd_dq_split PAIR)
-#endif
-#ifndef KFATT_FWD_WIDE
-#define KFATT_FWD_WIDE 1  // the forwards store O in whole 16-B rows per lane (store_rows16, T21)
-#endif
-#ifndef KFATT_FWD_DMA
-#define KFATT_FWD_DMA 0  // forward K / V tiles by LDS-DMA (attn_fwd stage_dma)
-#endif
-// LDS-DMA as inline asm (KFATT_DMA): the compiler, seeing a buffer_load ... lds builtin, waits
+// Row-guarded loads are raw buffer operations over one (b, h) slice whose range ends at row T
+// (slice_rsrc / bload16, slice_desc / dma16): a row past T reads as zero by the address unit, so the
+// inner loops carry no per-row branches (a divergent `if (row < T)` around each load split
+// the loops into ~30 basic blocks and cost the scheduler and the register allocator;
+// profiles/r5o_attn_buf). The host requires every slice's extent below 2^31 bytes (32-bit buffer
+// offsets): slice_ok.
+//
+// LDS-DMA as inline asm: the compiler, seeing a buffer_load ... lds builtin, waits
 // vmcnt(0) before later LDS reads it cannot prove disjoint (it did, mid-tile, before the dV / dK tr
 // reads: the next tile's DMA latency exposed). The kernel's own waits cover the pieces instead.
 // The descriptor is an SGPR quad (base, base_hi | stride 0, records, gfx9 raw-buffer word 3); M0 holds
@@ -186,21 +139,6 @@ __device__ __forceinline__ void dma4(const i32x4& desc, unsigned lds, int voff, 
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 1\n\tbuffer_load_dword %1, %2, %3 offen lds"
                :: "s"(__builtin_amdgcn_readfirstlane(lds)), "v"(voff), "s"(desc),
                   "s"(__builtin_amdgcn_readfirstlane(soff)) : "memory");
-}
-
-// The A operand of a product whose k index is an accumulator's row (the permuted order of
-// §3): element j of lane half hh is row kbase + 8 * (j >> 2) + 4 * hh + (j & 3) of the operand's
-// k dimension, column `col` (this lane's row of the A operand). Read as two tr reads of 4 rows.
-// Address of lane (group g, index i = 4 qq + p): row kbase + 4 hh + qq (+ 8), columns
-// col0 + 4 p .. +3 with col0 = the 16-column half of the 32-column tile this group covers.
-template <int D>
-__device__ __forceinline__ bf16x8 tr_operand(const char* smem, int kbase, int colbase, int lane) {
-  const int g = lane >> 4, i = lane & 15, qq = i >> 2, p = i & 3, hh = lane >> 5;
-  const int col = colbase + 16 * (g & 1) + 4 * p;
-  const int r0 = kbase + 4 * hh + qq;
-  const int off0 = img_off<D>(r0, col >> 3) + 8 * (p & 1);
-  const int off1 = img_off<D>(r0 + 8, col >> 3) + 8 * (p & 1);
-  return join(tr_read(smem, off0), tr_read(smem, off1));
 }
 
 // Whole 16-B row stores of an accumulator in the O^T layout (cdna_hip_programming.md T21): lane
@@ -235,10 +173,14 @@ __device__ __forceinline__ void store_rows16(__bf16* row, const f32x16 (&acc)[ND
 // ------------------------------------------------------------------------------------------------
 constexpr int FQ = 128, FK = 64;
 
-// PAIR (causal, an even number of query blocks, KFATT_FWD_PAIR): one workgroup runs query blocks
-// nq - 1 - i and i one after the other, nq + 1 key tiles for every workgroup, half the grid
+// PAIR (causal, an even number of query blocks; profiles/r5zm_fpair): one workgroup runs query blocks
+// nq - 1 - i and i one after the other, nq + 1 key tiles for every workgroup, half the grid.
+// Measured and not taken: K / V tiles by LDS-DMA as the backward's (2-7 % slower,
+// profiles/r5q_attn_split); 8 waves x 32 rows per workgroup (lost to attn_fwd_pp: profiles/r5zo_fwd8,
+// profiles/r6d_attn_pp).
+//
 // The forwards' two MFMA phases with every LDS operand read RA MFMAs ahead of its use, the order
-// pinned by sched groups (KFATT_FWD_RA, profiles/r6v_ra): the compiler's own order read each
+// pinned by sched groups (profiles/r6v_ra): the compiler's own order read each
 // fragment one or two MFMAs early and waited on it there, so a wave paid an LDS round trip per
 // k-step. S^T = K Q^T: MFMA i is k-step i / 2, key half t = i & 1.
 template <int D, int RA>
@@ -291,24 +233,23 @@ __device__ __forceinline__ void pv_ra(const char* vimg, const int (&voff0)[D / 3
   }
 }
 
-#ifndef KFATT_FWD4_RA
-#define KFATT_FWD4_RA 2  // attn_fwd (4 waves; D = 64 and small grids): KFATT_FWD_RA's pinned reads
-#endif
+// attn_fwd (D = 64 and small grids): LDS reads pinned this many MFMAs ahead of their use (profiles/r6v_ra)
+constexpr int kFwd4ReadAhead = 2;
 
-template <int D, bool CAUSAL, bool PAIR = false, int NW = 4>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
+template <int D, bool CAUSAL, bool PAIR = false>
+__global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                    const __bf16* __restrict__ v, __bf16* __restrict__ o,
                                                    float* __restrict__ lse, AttnShape a) {
   constexpr int KS = D / 16;           // k-steps of the QK^T product
   constexpr int ND = D / 32;           // 32-wide d tiles of O
   constexpr int CH = D / 8;            // 16-B chunks per row
-  constexpr int NT = 64 * NW, FQW = 32 * NW;  // threads, query rows per workgroup (NW waves x 32)
+  constexpr int NT = 256, FQW = FQ;    // threads, query rows per workgroup (4 waves x 32)
   constexpr int NCH = FK * CH / NT;    // chunks per thread per K (and per V) tile
   constexpr int TILE = FK * D * 2;     // bytes of one K (or V) tile image
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];  // [buf][K, V]
 
   const int nq = (a.T + FQW - 1) / FQW;
-  const BlockId bo = block_order(blockIdx.x, PAIR ? nq / 2 : nq, a.H * a.B, NW == 4 ? 64 : 32);  // workgroups per XCD
+  const BlockId bo = block_order(blockIdx.x, PAIR ? nq / 2 : nq, a.H * a.B, 64);  // workgroups per XCD
   const int bh = bo.bh, h = bh % a.H, b = bh / a.H;
 #pragma unroll 1
   for (int pass = 0; pass < (PAIR ? 2 : 1); ++pass) {
@@ -334,14 +275,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
 
   const int ntiles = CAUSAL ? min((T + FK - 1) / FK, (q0 + FQW) / FK) : (T + FK - 1) / FK;
 
-  constexpr bool kDma = KFATT_FWD_DMA && KFATT_BUF;
-  u32x4 kreg[kDma ? 1 : NCH], vreg[kDma ? 1 : NCH];
+  u32x4 kreg[NCH], vreg[NCH];
   const auto rk = slice_rsrc(kb, 2LL * T * kt), rv = slice_rsrc(vb, 2LL * T * vt);
-  const i32x4 dk_desc = slice_desc(kb, 2LL * T * kt), dv_desc = slice_desc(vb, 2LL * T * vt);
-  // KFATT_DMA: K / V tiles by LDS-DMA (as the backward's stage_dma): no staging registers
-  constexpr int NPC = TILE / 1024 / NW;
-  // LDS-DMA pieces: the wave index as a uniform value, each piece's per-lane source offset computed
-  // once (image chunk sc of row `row` holds source chunk sc ^ swz(row, 0))
+  // The per-lane source offsets of the LDS-DMA staging that was measured and not taken (above). Nothing reads
+  // them, but without them the compiler orders the staging loads of attn_fwd<128, *, false> and their registers
+  // differently, and the kernel is then not the one that was measured: they stay until that is measured again.
+  constexpr int NPC = TILE / 1024 / 4;
   const int wu = __builtin_amdgcn_readfirstlane(w);
   int dvo_k[NPC], dvo_v[NPC];
 #pragma unroll
@@ -351,42 +290,21 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
     dvo_k[i] = 2 * (row * (int)kt + ch * 8);
     dvo_v[i] = 2 * (row * (int)vt + ch * 8);
   }
-  auto stage_dma = [&](int tile, int buf) {
-    const int k0 = tile * FK;
-    char* kimg = smem + buf * 2 * TILE;
-    char* vimg = kimg + TILE;
-#pragma unroll
-    for (int i = 0; i < NPC; ++i) {
-      dma16(dk_desc, lds_addr(kimg + (wu * NPC + i) * 1024), dvo_k[i], 2 * k0 * (int)kt);
-      dma16(dv_desc, lds_addr(vimg + (wu * NPC + i) * 1024), dvo_v[i], 2 * k0 * (int)vt);
-    }
-  };
   auto stage_load = [&](int tile) {
     const int k0 = tile * FK;
 #pragma unroll
-    for (int i = 0; i < (kDma ? 0 : NCH); ++i) {
+    for (int i = 0; i < NCH; ++i) {
       const int c = tid + NT * i, row = c / CH, ch = c % CH;
-      const int key = k0 + row;
-      if constexpr (KFATT_BUF) {
-        // lane part in the voffset, the tile's row offset in the (scalar) soffset: no VALU per load
-        kreg[i] = bload16(rk, 2 * (row * (int)kt + ch * 8), 2 * k0 * (int)kt);
-        vreg[i] = bload16(rv, 2 * (row * (int)vt + ch * 8), 2 * k0 * (int)vt);
-      } else {
-        u32x4 xk = {0u, 0u, 0u, 0u}, xv = {0u, 0u, 0u, 0u};
-        if (key < T) {
-          xk = gload16(kb + key * kt + ch * 8);
-          xv = gload16(vb + key * vt + ch * 8);
-        }
-        kreg[i] = xk;
-        vreg[i] = xv;
-      }
+      // lane part in the voffset, the tile's row offset in the (scalar) soffset: no VALU per load
+      kreg[i] = bload16(rk, 2 * (row * (int)kt + ch * 8), 2 * k0 * (int)kt);
+      vreg[i] = bload16(rv, 2 * (row * (int)vt + ch * 8), 2 * k0 * (int)vt);
     }
   };
   auto stage_write = [&](int buf) {
     char* kimg = smem + buf * 2 * TILE;
     char* vimg = kimg + TILE;
 #pragma unroll
-    for (int i = 0; i < (kDma ? 0 : NCH); ++i) {
+    for (int i = 0; i < NCH; ++i) {
       const int c = tid + NT * i, row = c / CH, ch = c % CH;
       const int off = img_off<D>(row, ch);
       *reinterpret_cast<u32x4*>(kimg + off) = kreg[i];
@@ -400,15 +318,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
 #pragma unroll
   for (int n = 0; n < ND; ++n) oacc[n] = (f32x16){};
 
-  if constexpr (kDma) {
-    stage_dma(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
   stage_load(0);
   stage_write(0);
   __syncthreads();
 
-  // per-lane LDS offsets of every operand read, computed once (KFATT_FWD_OFFS): the row parts that
+  // per-lane LDS offsets of every operand read, computed once: the row parts that
   // vary per read (t, k-step, buffer) are compile-time and ride in the ds_read immediate, so the loop
   // body carries no address arithmetic (it was ~80 VALU per 64-key tile, a third of the VALU stream)
   int koff[KS], voff0[ND], voff1[ND];
@@ -429,26 +343,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
     constexpr int BUF = decltype(BUFC)::value;
     const int k0 = j * FK;
     const bool more = j + 1 < ntiles;
-    if (more) {
-      if constexpr (kDma) stage_dma(j + 1, 1 - BUF);
-      stage_load(j + 1);
-    }
+    if (more) stage_load(j + 1);
     const char* kimg = smem + BUF * 2 * TILE;
     const char* vimg = kimg + TILE;
     // a wave whose 32 rows all precede the tile's first key has nothing to do (causal)
     if (!(CAUSAL && k0 > qw + 31)) {
       f32x16 sacc[2] = {(f32x16){}, (f32x16){}};
-      if constexpr (KFATT_FWD4_RA > 0 && KFATT_FWD_OFFS) qk_ra<D, KFATT_FWD4_RA>(kimg, koff, qf, sacc);
-      else
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const bf16x8 kf = KFATT_FWD_OFFS ? lds_row(kimg + 32 * t * D * 2, koff[kk])
-                                           : lds_row(kimg, img_off<D>(32 * t + r, 2 * kk + hh));
-          sacc[t] = mfma32(kf, qf[kk], sacc[t]);
-        }
-      }
+      qk_ra<D, kFwd4ReadAhead>(kimg, koff, qf, sacc);
       // masks: causal (key > query) on tiles that reach the wave's diagonal, key >= T on the tail
       const bool causal_mask = CAUSAL && k0 + FK - 1 > qw;
       if (causal_mask || k0 + FK > T) {
@@ -493,27 +394,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
       } else {
         l += rs;
       }
-      if constexpr (KFATT_FWD4_RA > 0 && KFATT_FWD_OFFS) pv_ra<D, KFATT_FWD4_RA>(vimg, voff0, voff1, pf, oacc);
-      else
-#pragma unroll
-      for (int n = 0; n < ND; ++n) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const bf16x8 vf = KFATT_FWD_OFFS ? join(tr_read(vimg + (32 * t + 16 * s) * D * 2, voff0[n]),
-                                                    tr_read(vimg + (32 * t + 16 * s) * D * 2, voff1[n]))
-                                               : tr_operand<D>(vimg, 32 * t + 16 * s, 32 * n, lane);
-            const u32x4 pw = {pf[t][s][0], pf[t][s][1], pf[t][s][2], pf[t][s][3]};
-            oacc[n] = mfma32(vf, __builtin_bit_cast(bf16x8, pw), oacc[n]);
-          }
-        }
-      }
+      pv_ra<D, kFwd4ReadAhead>(vimg, voff0, voff1, pf, oacc);
     }
-    if (more) {
-      if constexpr (kDma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next tile's pieces
-      stage_write(1 - BUF);
-    }
+    if (more) stage_write(1 - BUF);
     __syncthreads();
   };
   for (int j = 0; j < ntiles; j += 2) {
@@ -525,78 +408,33 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd(const __bf1
   const float lt = kfw::sum_halves(l);
   const float inv = 1.f / lt;
   __bf16* ob = o + base_off(a, TO, b, h) + qrow * a.s[TO][2];
-  if constexpr (KFATT_FWD_WIDE) {
-    store_rows16<ND>(ob, oacc, inv, qrow < T, hh);
-  } else if (qrow < T) {
-#pragma unroll
-    for (int n = 0; n < ND; ++n) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const u32x2 v2 = {pack2(oacc[n][4 * g] * inv, oacc[n][4 * g + 1] * inv),
-                          pack2(oacc[n][4 * g + 2] * inv, oacc[n][4 * g + 3] * inv)};
-        *reinterpret_cast<u32x2*>(ob + 32 * n + 8 * g + 4 * hh) = v2;
-      }
-    }
-  }
+  store_rows16<ND>(ob, oacc, inv, qrow < T, hh);
   if (qrow < T && hh == 0) lse[((long long)b * a.H + h) * T + qrow] = m * a.scale + logf(lt);
   }  // pass
 }
 
 // ------------------------------------------------------------------------------------------------
-// forward, 8 waves x 32 query rows = 256 rows per workgroup, one workgroup per CU (KFATT_FWD_PP,
-// profiles/r6d_attn_pp): two waves per SIMD share its matrix pipe, one K / V image per CU per tile
+// forward, 8 waves x 32 query rows = 256 rows per workgroup, one workgroup per CU
+// (profiles/r6d_attn_pp): two waves per SIMD share its matrix pipe, one K / V image per CU per tile
 // instead of two (half the LDS stores and global loads of attn_fwd's two 128-row workgroups), and the
 // hardware interleaves one wave's softmax VALU with the other's MFMAs. One barrier per tile.
 // The running max is a reference that moves only when a row's scores pass it by more than
-// KFATT_FWD_THR (log2 units; cdna_hip_programming.md T13): probabilities stay <= 2^THR (exact in the
+// kFwdMaxThreshold (log2 units; cdna_hip_programming.md T13): probabilities stay <= 2^THR (exact in the
 // fp32 l and O, bf16 keeps its relative precision), and the 64-register O rescale runs only on
 // those tiles instead of on nearly every early one (the tests force both branches: rule 26).
-// K / V are loaded two tiles ahead (KFATT_FWD_PF2: a four-slot ring, two staging register sets;
-// without it one tile ahead through a three-slot ring).
+// K / V are loaded two tiles ahead (a four-slot ring, two staging register sets).
 // Measured and not taken (tools/attn_ab.py, profiles/r6d_attn_pp): staggering waves 4-7 half a tile
 // behind waves 0-3 (MI355X_MICROARCH.md "Two waves per SIMD" item 9): +7 % time; the QK^T of tile
-// j + 1 issued beside softmax(j), Q moved to LDS to pay for the second S tile (T15): +6 %.
+// j + 1 issued beside softmax(j), Q moved to LDS to pay for the second S tile (T15): +6 %; static
+// priority 1 for waves 4-7, the second-dispatched half that loses every VALU arbitration to its SIMD
+// partner (MI355X_MICROARCH.md "Two waves per SIMD" item 4); row max and row sum as 4 independent chains.
 // ------------------------------------------------------------------------------------------------
-#ifndef KFATT_FWD_PP
-#define KFATT_FWD_PP 1  // forward by attn_fwd_pp (profiles/r6d_attn_pp)
-#endif
-#ifndef KFATT_FWD_THR
-#define KFATT_FWD_THR 8.0f
-#endif
-#ifndef KFATT_FWD_FENCE
-#define KFATT_FWD_FENCE 1  // scheduling fences between the QK^T / softmax / PV phases of attn_fwd_pp
-#endif
-#define FENCE() \
-  do {                                                   \
-    if (KFATT_FWD_FENCE) __builtin_amdgcn_sched_barrier(0); \
-  } while (0)
-#ifndef KFATT_FWD_PF2
-#define KFATT_FWD_PF2 1  // K / V loads two tiles ahead (four-tile ring)
-#endif
-#ifndef KFATT_BWD_WIDE
-#define KFATT_BWD_WIDE 1  // dQ / dK / dV in whole 16-B rows per lane (store_rows16)
-#endif
-#ifndef KFATT_FWD_PRIO
-#define KFATT_FWD_PRIO 0  // attn_fwd_pp: static priority 1 for waves 4-7 (A/B knob)
-#endif
-#ifndef KFATT_FWD_PXP
-#define KFATT_FWD_PXP 1  // attn_fwd_pp pairs: the light block's prologue loads issued under the heavy block's epilogue
-#endif
-#ifndef KFATT_FWD_ABL
-#define KFATT_FWD_ABL 0  // timing ablations of attn_fwd_pp (tools/attn_ab.py; wrong results)
-#endif
-#ifndef KFATT_FWD_RA
-#define KFATT_FWD_RA 2  // attn_fwd_pp: LDS reads pinned this many MFMAs ahead of their use (0: compiler order)
-#endif
-#ifndef KFATT_DQ_RA
-#define KFATT_DQ_RA 0  // attn_bwd_dq_split (D = 128): LDS reads pinned this many MFMAs ahead (0: compiler order)
-#endif
-#ifndef KFATT_BWD_RA
-#define KFATT_BWD_RA 0  // attn_bwd_dkdv8: LDS reads pinned this many MFMAs ahead (0: compiler order)
-#endif
-#ifndef KFATT_FWD_SPLIT
-#define KFATT_FWD_SPLIT 0  // attn_fwd_pp softmax: row max and row sum as 4 independent chains
-#endif
+// the running max moves only past this margin: probabilities stay <= 2^8, exact in fp32 l and O (profiles/r6d_attn_pp)
+constexpr float kFwdMaxThreshold = 8.0f;
+// attn_fwd_pp: LDS reads pinned this many MFMAs ahead of their use (profiles/r6v_ra)
+constexpr int kFwdReadAhead = 2;
+// scheduling fence between the QK^T / softmax / PV phases of attn_fwd_pp
+#define FENCE() __builtin_amdgcn_sched_barrier(0)
 
 template <int D, bool CAUSAL, bool PAIR>
 __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
@@ -608,7 +446,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
   constexpr int TILE = FK * D * 2;
   // K ring [NS][TILE] then V ring [NS][TILE]; the V ring's base VBASE rides in the V read offsets,
   // so every slot / row offset of a read fits the 16-bit ds_read immediate
-  constexpr int NS = KFATT_FWD_PF2 ? 4 : 3, VBASE = NS * TILE;
+  constexpr int NS = 4, VBASE = NS * TILE;
   __shared__ __attribute__((aligned(16))) char smem[2 * NS * TILE];
 
   const int T = a.T;
@@ -617,9 +455,6 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
   const int bh = bo.bh, h = bh % a.H, b = bh / a.H;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hh = lane >> 5;
   const int wu = __builtin_amdgcn_readfirstlane(w);  // the wave index as a uniform (scalar) value
-  // KFATT_FWD_PRIO: waves 4-7, the second-dispatched half that loses every VALU arbitration to its
-  // SIMD partner, at priority 1 for the whole kernel (MI355X_MICROARCH.md "Two waves per SIMD" item 4)
-  if (KFATT_FWD_PRIO && wu >= 4) __builtin_amdgcn_s_setprio(1);
 
   const __bf16* qb = q + base_off(a, TQ, b, h);
   const __bf16* kb = k + base_off(a, TK, b, h / a.G);  // grouped K / V heads: query head h reads head h / G
@@ -627,9 +462,9 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
   const long long qt = a.s[TQ][2], kt = a.s[TK][2], vt = a.s[TV][2];
   const auto rk = slice_rsrc(kb, 2LL * T * kt), rv = slice_rsrc(vb, 2LL * T * vt);
   const float c = a.scale * kLog2e;
-  constexpr float THR = KFATT_FWD_THR;
+  constexpr float THR = kFwdMaxThreshold;
 
-  // per-lane LDS offsets (as attn_fwd KFATT_FWD_OFFS): tile row parts ride in the ds_read immediates
+  // per-lane LDS offsets (as attn_fwd): tile row parts ride in the ds_read immediates
   int koff[KS], voff0[ND], voff1[ND];
 #pragma unroll
   for (int kk = 0; kk < KS; ++kk) koff[kk] = img_off<D>(r, 2 * kk + hh);
@@ -644,51 +479,13 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     }
   }
   u32x4 kreg[NCH], vreg[NCH];
-  auto stage_load = [&](int tile) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int cc = tid + NT * i, row = cc / CH, ch = cc % CH;
-      kreg[i] = bload16(rk, 2 * (row * (int)kt + ch * 8), 2 * tile * FK * (int)kt);
-      vreg[i] = bload16(rv, 2 * (row * (int)vt + ch * 8), 2 * tile * FK * (int)vt);
-    }
-  };
-  auto stage_write = [&](int slot) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int cc = tid + NT * i;
-      const int off = img_off<D>(cc / CH, cc % CH);
-      *reinterpret_cast<u32x4*>(smem + slot * TILE + off) = kreg[i];
-      *reinterpret_cast<u32x4*>(smem + VBASE + slot * TILE + off) = vreg[i];
-    }
-  };
   auto qk = [&](const char* kimg, const bf16x8 (&qf)[KS], f32x16 (&s)[2]) __attribute__((always_inline)) {
     s[0] = (f32x16){};
     s[1] = (f32x16){};
-    if constexpr (KFATT_FWD_RA > 0) {
-      qk_ra<D, KFATT_FWD_RA>(kimg, koff, qf, s);
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) s[t] = mfma32(lds_row(kimg + 32 * t * D * 2, koff[kk]), qf[kk], s[t]);
-    }
+    qk_ra<D, kFwdReadAhead>(kimg, koff, qf, s);
   };
   auto pv = [&](const char* vimg, const uint32_t (&pf)[2][2][4], f32x16 (&oa)[ND]) __attribute__((always_inline)) {
-    if constexpr (KFATT_FWD_RA > 0) {
-      pv_ra<D, KFATT_FWD_RA>(vimg, voff0, voff1, pf, oa);
-      return;
-    }
-#pragma unroll
-    for (int n = 0; n < ND; ++n)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 vf = join(tr_read(vimg + (32 * t + 16 * s2) * D * 2, voff0[n]),
-                                 tr_read(vimg + (32 * t + 16 * s2) * D * 2, voff1[n]));
-          const u32x4 pw = {pf[t][s2][0], pf[t][s2][1], pf[t][s2][2], pf[t][s2][3]};
-          oa[n] = mfma32(vf, __builtin_bit_cast(bf16x8, pw), oa[n]);
-        }
+    pv_ra<D, kFwdReadAhead>(vimg, voff0, voff1, pf, oa);
   };
   // causal / tail mask of the wave's S^T tile (keys from k0, rows from qw); a uniform branch
   auto mask = [&](f32x16 (&s)[2], int k0, int qw) __attribute__((always_inline)) {
@@ -706,36 +503,26 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
   auto softmax = [&](const f32x16 (&s)[2], float& m, float& l, uint32_t (&pf)[2][2][4], f32x16 (&oa)[ND])
                      __attribute__((always_inline)) {
     float mx = -INFINITY;
-    if constexpr (KFATT_FWD_SPLIT) {
-      float mp[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) mp[e & 3] = fmaxf(mp[e & 3], s[t][e]);
-      mx = fmaxf(fmaxf(mp[0], mp[1]), fmaxf(mp[2], mp[3]));
-    } else {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[t][e]);
-    }
+      for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[t][e]);
     mx = kfw::max_halves(mx);
     const bool move = (mx - m) * c > THR;  // m = -inf on the first tile: moves
     const float mn = move ? mx : m;
     const float alpha = move ? fast_exp2((m - mn) * c) : 1.f;
     m = mn;
     const float mc = mn * c;
-    float rp[4] = {0.f, 0.f, 0.f, 0.f};
+    float rs = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e = 0; e < 16; e += 2) {
         const float p0 = fast_exp2(fmaf(s[t][e], c, -mc));
         const float p1 = fast_exp2(fmaf(s[t][e + 1], c, -mc));
-        rp[KFATT_FWD_SPLIT ? (e >> 1) & 3 : 0] += p0 + p1;
+        rs += p0 + p1;
         pf[t][e >> 3][(e & 7) >> 1] = pack2(p0, p1);
       }
-    const float rs = KFATT_FWD_SPLIT ? (rp[0] + rp[1]) + (rp[2] + rp[3]) : rp[0];
     l = l * alpha + rs;
     if (__builtin_amdgcn_ballot_w64(move) != 0) {
 #pragma unroll
@@ -752,7 +539,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
       qf[kk] = __builtin_bit_cast(bf16x8, x);
     }
   };
-  // KFATT_FWD_PF2 staging: two register sets, tile j + 2 issued at tile j (see the tile loop)
+  // staging: two register sets, tile j + 2 issued at tile j (see the tile loop)
   u32x4 kr2[NCH], vr2[NCH];
   auto ld = [&](int tile, u32x4 (&kr)[NCH], u32x4 (&vr)[NCH]) __attribute__((always_inline)) {
 #pragma unroll
@@ -771,10 +558,10 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
       *reinterpret_cast<u32x4*>(smem + VBASE + slot * TILE + off) = vr[i];
     }
   };
-  // KFATT_FWD_PXP (pairs): the light block's Q and first two K / V tiles are issued when the heavy
+  // pairs: the light block's Q and first two K / V tiles are issued when the heavy
   // block's tile loop ends, so their latency hides under its epilogue instead of stalling a second
   // prologue
-  constexpr bool PXP = KFATT_FWD_PXP && KFATT_FWD_PF2 && PAIR;
+  constexpr bool PXP = PAIR;
 
 #pragma unroll 1
   for (int pass = 0; pass < (PAIR ? 2 : 1); ++pass) {
@@ -791,78 +578,48 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     for (int n = 0; n < ND; ++n) oacc[n] = (f32x16){};
     float m = -INFINITY, l = 0.f;
     uint32_t pf[2][2][4];
-    // tile j sits in ring slot j % 3, compile-time in the unrolled loop (pv reads through
+    // tile j sits in ring slot j % 4, compile-time in the unrolled loop (pv reads through
     // smem + slot * TILE, the V ring base riding in voff)
-    if constexpr (KFATT_FWD_PF2) {
-      // K / V two tiles ahead: tile j + 2's loads are issued at tile j into the register set tile j
-      // used (written at tile j - 1), and tile j + 1's set is written at the end of tile j into the
-      // slot of tile j - 3 (a four-tile ring: slot and set compile-time in the 4x unrolled loop)
-      if (!pre) ld(0, kreg, vreg);
-      st(0, kreg, vreg);
-      if (!pre && 1 < ntiles) ld(1, kr2, vr2);
-      __syncthreads();
-      auto tile = [&](int j, auto SLC) __attribute__((always_inline)) {
-        constexpr int SL = decltype(SLC)::value;  // j % 4; register set j & 1
-        auto& kc = (SL & 1) ? kr2 : kreg;
-        auto& vc = (SL & 1) ? vr2 : vreg;
-        auto& kn = (SL & 1) ? kreg : kr2;
-        auto& vn = (SL & 1) ? vreg : vr2;
-        if ((KFATT_FWD_ABL & 1) == 0 && j + 2 < ntiles) ld(j + 2, kc, vc);
-        if (j <= jl) {
-          qk(smem + SL * TILE, qf, S[0]);
-          mask(S[0], j * FK, qw);
-          FENCE();
-          softmax(S[0], m, l, pf, oacc);
-          FENCE();
-          pv(smem + SL * TILE, pf, oacc);
-        }
-        if ((KFATT_FWD_ABL & 1) == 0 && j + 1 < ntiles) st((SL + 1) % 4, kn, vn);
-        if ((KFATT_FWD_ABL & 2) == 0) __syncthreads();
-      };
-      using I0 = std::integral_constant<int, 0>;
-      using I1 = std::integral_constant<int, 1>;
-      using I2 = std::integral_constant<int, 2>;
-      using I3 = std::integral_constant<int, 3>;
-      int j = 0;
-#pragma unroll 1
-      for (; j + 3 < ntiles; j += 4) {
-        tile(j, I0{});
-        tile(j + 1, I1{});
-        tile(j + 2, I2{});
-        tile(j + 3, I3{});
+    // K / V two tiles ahead: tile j + 2's loads are issued at tile j into the register set tile j
+    // used (written at tile j - 1), and tile j + 1's set is written at the end of tile j into the
+    // slot of tile j - 3 (a four-tile ring: slot and set compile-time in the 4x unrolled loop)
+    if (!pre) ld(0, kreg, vreg);
+    st(0, kreg, vreg);
+    if (!pre && 1 < ntiles) ld(1, kr2, vr2);
+    __syncthreads();
+    auto tile = [&](int j, auto SLC) __attribute__((always_inline)) {
+      constexpr int SL = decltype(SLC)::value;  // j % 4; register set j & 1
+      auto& kc = (SL & 1) ? kr2 : kreg;
+      auto& vc = (SL & 1) ? vr2 : vreg;
+      auto& kn = (SL & 1) ? kreg : kr2;
+      auto& vn = (SL & 1) ? vreg : vr2;
+      if (j + 2 < ntiles) ld(j + 2, kc, vc);
+      if (j <= jl) {
+        qk(smem + SL * TILE, qf, S[0]);
+        mask(S[0], j * FK, qw);
+        FENCE();
+        softmax(S[0], m, l, pf, oacc);
+        FENCE();
+        pv(smem + SL * TILE, pf, oacc);
       }
-      if (j < ntiles) tile(j, I0{});
-      if (j + 1 < ntiles) tile(j + 1, I1{});
-      if (j + 2 < ntiles) tile(j + 2, I2{});
-    } else {
-      stage_load(0);
-      stage_write(0);
+      if (j + 1 < ntiles) st((SL + 1) % 4, kn, vn);
       __syncthreads();
-      auto tile = [&](int j, auto SLC) __attribute__((always_inline)) {
-        constexpr int SL = decltype(SLC)::value;
-        const bool more = (KFATT_FWD_ABL & 1) == 0 && j + 1 < ntiles;  // ABL 1: no staging (timing only)
-        if (more) stage_load(j + 1);
-        if (j <= jl) {
-          qk(smem + SL * TILE, qf, S[0]);
-          mask(S[0], j * FK, qw);
-          FENCE();
-          softmax(S[0], m, l, pf, oacc);
-          FENCE();
-          pv(smem + SL * TILE, pf, oacc);
-        }
-        if (more) stage_write((SL + 1) % 3);
-        if ((KFATT_FWD_ABL & 2) == 0) __syncthreads();  // ABL 2: no barrier (timing only)
-      };
-      int j = 0;
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using I3 = std::integral_constant<int, 3>;
+    int j = 0;
 #pragma unroll 1
-      for (; j + 2 < ntiles; j += 3) {
-        tile(j, std::integral_constant<int, 0>{});
-        tile(j + 1, std::integral_constant<int, 1>{});
-        tile(j + 2, std::integral_constant<int, 2>{});
-      }
-      if (j < ntiles) tile(j, std::integral_constant<int, 0>{});
-      if (j + 1 < ntiles) tile(j + 1, std::integral_constant<int, 1>{});
+    for (; j + 3 < ntiles; j += 4) {
+      tile(j, I0{});
+      tile(j + 1, I1{});
+      tile(j + 2, I2{});
+      tile(j + 3, I3{});
     }
+    if (j < ntiles) tile(j, I0{});
+    if (j + 1 < ntiles) tile(j + 1, I1{});
+    if (j + 2 < ntiles) tile(j + 2, I2{});
 
     if (PXP && pass == 0) {  // the light block's Q and first K / V tiles, under this epilogue
       const int q0n = bo.rank * FQW;
@@ -875,71 +632,36 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     const float lt = kfw::sum_halves(l);
     const float inv = 1.f / lt;
     __bf16* ob = o + base_off(a, TO, b, h) + qrow * a.s[TO][2];
-    if constexpr (KFATT_FWD_WIDE) {
-      store_rows16<ND>(ob, oacc, inv, qrow < T, hh);
-    } else if (qrow < T) {
-#pragma unroll
-      for (int n = 0; n < ND; ++n)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const u32x2 v2 = {pack2(oacc[n][4 * g] * inv, oacc[n][4 * g + 1] * inv),
-                            pack2(oacc[n][4 * g + 2] * inv, oacc[n][4 * g + 3] * inv)};
-          *reinterpret_cast<u32x2*>(ob + 32 * n + 8 * g + 4 * hh) = v2;
-        }
-    }
+    store_rows16<ND>(ob, oacc, inv, qrow < T, hh);
     if (qrow < T && hh == 0) lse[((long long)b * a.H + h) * T + qrow] = m * a.scale + logf(lt);
   }  // pass
 }
 
 // ------------------------------------------------------------------------------------------------
-// backward prologue, per row [b][h][t]: nd = -sum_d dO * O and nl = -lse / scale (fp32), the two
-// row constants of the backward in the form its products start from: S - lse / scale and dP - delta
-// are the MFMA accumulators initialised with nl and nd (no negate / scale per element and tile)
-// ------------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void attn_bwd_delta(const __bf16* __restrict__ o, const __bf16* __restrict__ dout,
-                                                      const float* __restrict__ lse, float* __restrict__ nl,
-                                                      float* __restrict__ nd, AttnShape a) {
-  constexpr int LPR = D / 8;        // lanes per row (16 B each)
-  constexpr int RPB = 256 / LPR;    // rows per block
-  const long long nrows = (long long)a.B * a.H * a.T;
-  const long long row = (long long)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int part = threadIdx.x % LPR;
-  float s = 0.f;
-  if (row < nrows) {
-    const int t = (int)(row % a.T);
-    const int h = (int)((row / a.T) % a.H);
-    const int b = (int)(row / ((long long)a.T * a.H));
-    const u32x4 x = gload16(o + base_off(a, TO, b, h) + t * a.s[TO][2] + part * 8);
-    const u32x4 y = gload16(dout + base_off(a, TDO, b, h) + t * a.s[TDO][2] + part * 8);
-    const bf16x8 xb = __builtin_bit_cast(bf16x8, x), yb = __builtin_bit_cast(bf16x8, y);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s = fmaf((float)xb[e], (float)yb[e], s);
-  }
-  s = kfw::group_sum<LPR>(s);
-  if (row < nrows && part == 0) {
-    nd[row] = -s;
-    nl[row] = -lse[row] / a.scale;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// backward dQ without atomics (KFATT_DQ_SPLIT): the forward's structure with the log-sum-exp known.
+// backward dQ without atomics: the forward's structure with the log-sum-exp known.
 // One workgroup = 4 waves = 128 query rows; 64-key K / V tiles by LDS-DMA into a double-buffered
 // image; per tile S^T = K Q^T and dP^T = V dO^T (keys on registers, the lane's query on the column),
 // P^T = exp(scale S - lse), dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T with dS^T straight from the
 // registers as the B operand (the permuted k order, as P^T feeds PV in the forward). dQ is written
 // once, scaled, in bf16: no fp32 workspace, no atomics, no conversion pass. Costs the S and dP
-// products a second time (the dK / dV kernel computes them too).
+// products a second time (the dK / dV kernel computes them too): against dQ by f32 atomics from the
+// dK / dV kernel, gpt-1b 4x16x2048x128 bwd 570 -> 482 us, 16x12x2048x64 827 -> 557 (at D = 64 the
+// atomics were a third of the pass), 1x16x4096x128 489 -> 417 (profiles/r5q_attn_split).
+// This kernel runs first and is also the backward's prologue: each lane's query row computes
+// delta = sum_d dO * O from the dO fragments it holds anyway plus one pass over O, and writes the two
+// row constants of the dK / dV kernel in the form its products start from: nl = -lse / scale and
+// nd = -delta (fp32 [B][H][T]); S - lse / scale and dP - delta are its MFMA accumulators initialised
+// with nl and nd (no negate / scale per element and tile). Against a separate prologue kernel:
+// gpt-1b bwd -5 %.
+// PAIR: as attn_fwd's (query blocks nq - 1 - i and i in one workgroup). Measured twice and not taken
+// (profiles/r5zm_fpair, profiles/r6v_ra), so only PAIR = false is instantiated; the pass loop stays
+// because the compiler orders the kernel's prologue differently without it.
+// Measured and not taken as well: LDS reads pinned ahead of their MFMAs as qk_ra / pv_ra (profiles/r6v_ra).
 // ------------------------------------------------------------------------------------------------
-// DELTA (KFATT_DQ_DELTA): this kernel runs first and is also the backward's prologue: each lane's
-// query row computes delta = sum_d dO * O from the dO fragments it holds anyway plus one pass over O,
-// and writes nl / nd for the dK / dV kernel (lse, delta arrive raw; the separate prologue is gone)
-// PAIR: as attn_fwd's (query blocks nq - 1 - i and i in one workgroup; KFATT_DQ_PAIR)
-template <int D, bool CAUSAL, bool DELTA = false, bool PAIR = false>
+template <int D, bool CAUSAL, bool PAIR = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                             const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
-                                                            const float* __restrict__ lse, const float* __restrict__ delta,
+                                                            const float* __restrict__ lse, const float* __restrict__ unused_slot,
                                                             __bf16* __restrict__ dq, AttnShape a,
                                                             const __bf16* __restrict__ o, float* __restrict__ nl_out,
                                                             float* __restrict__ nd_out) {
@@ -977,28 +699,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
     dof[kk] = __builtin_bit_cast(bf16x8, bload16(rdo, 2 * (qrow * (int)dot + kk * 16 + 8 * hh)));
   }
   const long long rowbase = ((long long)b * a.H + h) * T;
-  float nlc, nd_q;
-  if constexpr (DELTA) {
-    const auto ro = slice_rsrc(o + base_off(a, TO, b, h), 2LL * T * a.s[TO][2]);
-    float dd = 0.f;
+  const auto ro = slice_rsrc(o + base_off(a, TO, b, h), 2LL * T * a.s[TO][2]);
+  float dd = 0.f;
 #pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-      const bf16x8 of = __builtin_bit_cast(bf16x8, bload16(ro, 2 * (qrow * (int)a.s[TO][2] + kk * 16 + 8 * hh)));
+  for (int kk = 0; kk < KS; ++kk) {
+    const bf16x8 of = __builtin_bit_cast(bf16x8, bload16(ro, 2 * (qrow * (int)a.s[TO][2] + kk * 16 + 8 * hh)));
 #pragma unroll
-      for (int e = 0; e < 8; ++e) dd = fmaf((float)of[e], (float)dof[kk][e], dd);
-    }
-    const float delta_q = kfw::sum_halves(dd);  // the row's other half of d (lane ^ 32)
-    const float lq = qrow < T ? lse[rowbase + qrow] : 0.f;
-    nlc = -lq * kLog2e;
-    nd_q = -delta_q;
-    if (hh == 0 && qrow < T) {
-      nl_out[rowbase + qrow] = -lq / a.scale;
-      nd_out[rowbase + qrow] = nd_q;
-    }
-  } else {
-    // (lse / delta arrive as the prologue's nl = -lse / scale and nd = -delta)
-    nlc = qrow < T ? lse[rowbase + qrow] * (a.scale * kLog2e) : 0.f;
-    nd_q = qrow < T ? delta[rowbase + qrow] : 0.f;
+    for (int e = 0; e < 8; ++e) dd = fmaf((float)of[e], (float)dof[kk][e], dd);
+  }
+  const float delta_q = kfw::sum_halves(dd);  // the row's other half of d (lane ^ 32)
+  const float lq = qrow < T ? lse[rowbase + qrow] : 0.f;
+  const float nlc = -lq * kLog2e, nd_q = -delta_q;
+  if (hh == 0 && qrow < T) {
+    nl_out[rowbase + qrow] = -lq / a.scale;
+    nd_out[rowbase + qrow] = nd_q;
   }
 
   const int ntiles = CAUSAL ? min((T + FK - 1) / FK, (q0 + FQ) / FK) : (T + FK - 1) / FK;
@@ -1055,31 +769,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
     const char* vimg = kimg + TILE;
     if (!(CAUSAL && k0 > qw + 31)) {
       f32x16 sacc[2] = {(f32x16){}, (f32x16){}}, dpacc[2] = {(f32x16){}, (f32x16){}};
-      if constexpr (KFATT_DQ_RA > 0 && D == 128) {
-        // KFATT_DQ_RA: the K / V fragment of MFMA i + RA read before MFMA i issues (as attn_fwd_pp);
-        // MFMA i: k-step i / 4, t = (i / 2) & 1, S for even i, dP for odd
-        constexpr int RA = KFATT_DQ_RA, NM = 4 * KS;
-        bf16x8 fa[NM];
-        auto rd = [&](int i) __attribute__((always_inline)) {
-          fa[i] = lds_row(((i & 1) ? vimg : kimg) + 32 * ((i >> 1) & 1) * D * 2, koff[i >> 2]);
-        };
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i == 0)
-#pragma unroll
-            for (int u = 0; u < RA; ++u) rd(u);
-          if (i + RA < NM) rd(i + RA);
-          const int t = (i >> 1) & 1;
-          if (i & 1) dpacc[t] = mfma32(fa[i], dof[i >> 2], dpacc[t]);
-          else sacc[t] = mfma32(fa[i], qf[i >> 2], sacc[t]);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, RA, 0);
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i + RA < NM) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      } else
 #pragma unroll
       for (int kk = 0; kk < KS; ++kk) {
 #pragma unroll
@@ -1103,30 +792,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
           sf[t][e >> 3][(e & 7) >> 1] = pack2(p0 * (dpacc[t][e] + nd_q), p1 * (dpacc[t][e + 1] + nd_q));
         }
       }
-      if constexpr (KFATT_DQ_RA > 0 && D == 128) {
-        constexpr int RA = KFATT_DQ_RA, NM = 4 * ND;  // MFMA i: n = i / 4, t = (i / 2) & 1, s2 = i & 1
-        bf16x8 fk[NM];
-        auto rd = [&](int i) __attribute__((always_inline)) {
-          const char* base = kimg + (32 * ((i >> 1) & 1) + 16 * (i & 1)) * D * 2;
-          fk[i] = join(tr_read(base, voff0[i >> 2]), tr_read(base, voff1[i >> 2]));
-        };
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i == 0)
-#pragma unroll
-            for (int u = 0; u < RA; ++u) rd(u);
-          if (i + RA < NM) rd(i + RA);
-          const int t = (i >> 1) & 1, s2 = i & 1;
-          const u32x4 sw = {sf[t][s2][0], sf[t][s2][1], sf[t][s2][2], sf[t][s2][3]};
-          dqacc[i >> 2] = mfma32(fk[i], __builtin_bit_cast(bf16x8, sw), dqacc[i >> 2]);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * RA, 0);
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i + RA < NM) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      } else
 #pragma unroll
       for (int n = 0; n < ND; ++n) {
 #pragma unroll
@@ -1152,46 +817,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
 
   // lane (r, hh) holds row qrow, d = 32 n + (e & 3) + 8 (e >> 2) + 4 hh
   __bf16* dqr = dq + base_off(a, TDQ, b, h) + qrow * a.s[TDQ][2];
-  if constexpr (KFATT_BWD_WIDE) {
-    store_rows16<ND>(dqr, dqacc, a.scale, qrow < T, hh);
-  } else if (qrow < T) {
-    const float sc = a.scale;
-#pragma unroll
-    for (int n = 0; n < ND; ++n) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const u32x2 v2 = {pack2(dqacc[n][4 * g] * sc, dqacc[n][4 * g + 1] * sc),
-                          pack2(dqacc[n][4 * g + 2] * sc, dqacc[n][4 * g + 3] * sc)};
-        *reinterpret_cast<u32x2*>(dqr + 32 * n + 8 * g + 4 * hh) = v2;
-      }
-    }
-  }
+  store_rows16<ND>(dqr, dqacc, a.scale, qrow < T, hh);
   }  // pass
 }
 
-// dS^T image [128 keys][64 queries]: 128-B rows of sixteen 8-B slots (4 queries each), slot ^ f(row),
-// f(row) = (row & 15) ^ (((row >> 1) & 1) << 3). The accumulator's stores (16 lanes = 16 consecutive
-// keys, one slot each) cover all 32 write banks (unswizzled: one slot column, 16-way); the dQ
-// product's transposed reads (4 consecutive keys x 32 queries per 32-lane half) put rows r and r+2,
-// which share a 256-B bank window, on opposite 8-slot halves. (The round-5 first cut's 32-query image
-// without a swizzle cost SQ_LDS_BANK_CONFLICT 4.7e7 cycles per 3 gpt-1b backward passes.)
-__device__ __forceinline__ int dst_off(int row, int slot8) {
-  return row * 128 + ((slot8 ^ ((row & 15) ^ (((row >> 1) & 1) << 3))) << 3);
-}
-
 // ------------------------------------------------------------------------------------------------
-// backward: one workgroup = 4 waves = 128 keys of one (b, h); 64-row query tiles (Q, dO, lse,
-// delta) double-buffered through LDS, two 32-row S / dP sub-tiles per wave; dK / dV in registers
-// for the whole sweep
-// ------------------------------------------------------------------------------------------------
-constexpr int BK = 128, BQ = 64, QS = BQ / 32;
-
-// ------------------------------------------------------------------------------------------------
-// dK / dV with two waves per SIMD (KFATT_DKDV8, used with the split dQ kernel): 8 waves = 4 key
+// backward dK / dV: one workgroup = 128 keys of one (b, h); 64-row query tiles (Q, dO, nl, nd, as
+// attn_bwd_dq_split wrote them) double-buffered through LDS by LDS-DMA; dK / dV in registers for the
+// whole sweep. Two waves per SIMD: 8 waves = 4 key
 // groups of 32 keys x 2 query halves. Wave (w, jh) takes rows 32 jh .. 32 jh + 31 of every 64-row
 // query tile for the keys of group w, so the two waves of a SIMD interleave their LDS waits and
-// barriers with each other's MFMAs (the 4-wave kernel runs one wave per SIMD at D = 128 and waits
-// half its cycles). K and V both sit in LDS (V rows are the dP product's B operand) to keep a wave
+// barriers with each other's MFMAs (with 4 waves, one per SIMD at D = 128, a wave waited half its
+// cycles: profiles/r5w_attn_dkdv8; D = 64, 16x12x2048x64: 516 -> 485 us). K and V both sit in LDS
+// (V rows are the dP product's B operand) to keep a wave
 // within 256 registers; the two halves' partial dK^T / dV^T are summed through LDS at the end.
 //
 // GRP (grouped-query attention, Hkv < H): the grid runs over K / V heads, nk * Hkv * B * (G / GS)
@@ -1202,11 +840,13 @@ constexpr int BK = 128, BQ = 64, QS = BQ / 32;
 // in fp32 registers, rounded once and stored as bf16 with Hkv heads. GS < G: the G / GS workgroups
 // ("parts") of a (key block, K / V head) store their unscaled fp32 sums to `gpart`
 // ([dk, dv][part][B][Hkv][T][D]) and attn_bwd_gqa_reduce adds the parts in part order, scales, rounds
-// once and stores: no atomics on either route, both deterministic. GRP = false is the kernel as it was.
+// once and stores: no atomics on either route, both deterministic. GRP = false: one query head per K / V head.
 // Registers (hipcc 7.2 remarks; no scratch anywhere): D = 128 causal / full 226 / 222 VGPRs ungrouped,
 // 227 / 228 GRP; D = 64 126 / 128 ungrouped, 124 / 128 GRP. GRP at D = 64 asks for 4 waves per SIMD
 // in its launch bounds: unforced, the non-causal kernel took 142 VGPRs and lost the second workgroup per CU.
 // ------------------------------------------------------------------------------------------------
+constexpr int BK = 128, BQ = 64;
+
 template <int D, bool CAUSAL, bool GRP = false>
 __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkdv8(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                          const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
@@ -1333,7 +973,7 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
   auto tile_body = [&](int it, bool more, auto BUFC) __attribute__((always_inline)) {
     constexpr int BUF = decltype(BUFC)::value;
     const int q0 = qstart + it * BQ;
-    if ((KFATT_DKDV_ABL & 1) == 0 && more) {  // ABL 1: no staging
+    if (more) {
       if constexpr (GRP) stage_next(1 - BUF);
       else stage_dma(it + 1, 1 - BUF);
     }
@@ -1356,38 +996,11 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
           dpacc[4 * g + e] = d4[e];
         }
       }
-      // S^T-free form as the 4-wave kernel: rows = this wave's queries, column = the lane's key
-      if constexpr (KFATT_BWD_RA > 0 && D == 128) {
-        // KFATT_BWD_RA: both operands of MFMA i + RA read before MFMA i issues, pinned by sched
-        // groups (MFMA i: k-step i / 2, S for even i, dP for odd)
-        constexpr int RA = KFATT_BWD_RA, NM = 2 * KS;
-        bf16x8 fa[NM], fb[NM];
-        auto rd = [&](int i) __attribute__((always_inline)) {
-          fa[i] = lds_row((i & 1) ? oi : qi, koff[i >> 1]);
-          fb[i] = lds_row((i & 1) ? vimg_w : kimg_w, koff[i >> 1]);
-        };
+      // rows = this wave's queries, column = the lane's key
 #pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i == 0)
-#pragma unroll
-            for (int u = 0; u < RA; ++u) rd(u);
-          if (i + RA < NM) rd(i + RA);
-          if (i & 1) dpacc = mfma32(fa[i], fb[i], dpacc);
-          else sacc = mfma32(fa[i], fb[i], sacc);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * RA, 0);
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i + RA < NM) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      } else {
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-          const int kr = (KFATT_DKDV_ABL & 4) ? 0 : kk;  // ABL 4: one K / V fragment read per tile (timing only)
-          sacc = mfma32(lds_row(qi, koff[kk]), lds_row(kimg_w, koff[kr]), sacc);
-          dpacc = mfma32(lds_row(oi, koff[kk]), lds_row(vimg_w, koff[kr]), dpacc);
-        }
+      for (int kk = 0; kk < KS; ++kk) {
+        sacc = mfma32(lds_row(qi, koff[kk]), lds_row(kimg_w, koff[kk]), sacc);
+        dpacc = mfma32(lds_row(oi, koff[kk]), lds_row(vimg_w, koff[kk]), dpacc);
       }
       uint32_t pf[2][4], sf[2][4];
 #pragma unroll
@@ -1402,35 +1015,6 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
         sf[e >> 3][(e & 7) >> 1] = pack2(p0 * dpacc[e], p1 * dpacc[e + 1]);
       }
       // dV^T += dO^T . P and dK^T += Q^T . dS over this half's rows (permuted k order)
-      if constexpr (KFATT_BWD_RA > 0 && D == 128) {
-        constexpr int RA = 2 * KFATT_BWD_RA, NM = 4 * ND;  // MFMA i: n = i / 4, sx = (i / 2) & 1, dV for even i
-        bf16x8 fa[NM];
-        auto rd = [&](int i) __attribute__((always_inline)) {
-          const char* base = ((i & 1) ? qi : oi) + 16 * ((i >> 1) & 1) * D * 2;
-          fa[i] = join(tr_read(base, voff0[i >> 2]), tr_read(base, voff1[i >> 2]));
-        };
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i == 0)
-#pragma unroll
-            for (int u = 0; u < RA; ++u) rd(u);
-          if (i + RA < NM) rd(i + RA);
-          const int sx = (i >> 1) & 1, n = i >> 2;
-          if (i & 1) {
-            const u32x4 sw = {sf[sx][0], sf[sx][1], sf[sx][2], sf[sx][3]};
-            dkacc[n] = mfma32(fa[i], __builtin_bit_cast(bf16x8, sw), dkacc[n]);
-          } else {
-            const u32x4 pw = {pf[sx][0], pf[sx][1], pf[sx][2], pf[sx][3]};
-            dvacc[n] = mfma32(fa[i], __builtin_bit_cast(bf16x8, pw), dvacc[n]);
-          }
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * RA, 0);
-#pragma unroll
-        for (int i = 0; i < NM; ++i) {
-          if (i + RA < NM) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      } else
 #pragma unroll
       for (int n = 0; n < ND; ++n) {
 #pragma unroll
@@ -1445,7 +1029,7 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next tile's pieces (the loop's only VMEM)
-    if ((KFATT_DKDV_ABL & 2) == 0) __syncthreads();       // ABL 2: no barrier (timing only)
+    __syncthreads();
   };
   if constexpr (GRP) {
     int ct = 0;  // the computed tile's index within its head
@@ -1511,24 +1095,9 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
       return;
     }
   }
-  if (KFATT_BWD_WIDE && jh == 0) {  // (jh: wave-uniform, so whole waves run the swaps)
+  if (jh == 0) {  // (jh: wave-uniform, so whole waves run the swaps)
     store_rows16<ND>(dk + base_off(a, TDK, b, hk) + key * a.s[TDK][2], dkacc, a.scale, key < T, hh);
     store_rows16<ND>(dv + base_off(a, TDV, b, hk) + key * a.s[TDV][2], dvacc, 1.f, key < T, hh);
-  } else if (jh == 0 && key < T) {
-    __bf16* dkr = dk + base_off(a, TDK, b, hk) + key * a.s[TDK][2];
-    __bf16* dvr = dv + base_off(a, TDV, b, hk) + key * a.s[TDV][2];
-#pragma unroll
-    for (int n = 0; n < ND; ++n) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * n + 8 * g + 4 * hh;
-        const float sc = a.scale;
-        *reinterpret_cast<u32x2*>(dkr + d) =
-            (u32x2){pack2(dkacc[n][4 * g] * sc, dkacc[n][4 * g + 1] * sc), pack2(dkacc[n][4 * g + 2] * sc, dkacc[n][4 * g + 3] * sc)};
-        *reinterpret_cast<u32x2*>(dvr + d) =
-            (u32x2){pack2(dvacc[n][4 * g], dvacc[n][4 * g + 1]), pack2(dvacc[n][4 * g + 2], dvacc[n][4 * g + 3])};
-      }
-    }
   }
 }
 
@@ -1570,353 +1139,6 @@ __global__ __launch_bounds__(256) void attn_bwd_gqa_reduce(const float* __restri
   }
 }
 
-// D = 128 holds dK^T, dV^T (128 registers) and V (32) for the whole sweep: one wave per SIMD
-// (512-register budget, no spills); D = 64 fits two
-template <int D, bool CAUSAL, bool DQS = false>
-__global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
-                                                   const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
-                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                   float* __restrict__ dq_acc, __bf16* __restrict__ dk,
-                                                   __bf16* __restrict__ dv, AttnShape a, long long dq_st,
-                                                   long long dq_sh, long long dq_sb) {
-  constexpr int KS = D / 16;
-  constexpr int ND = D / 32;
-  constexpr int CH = D / 8;
-  constexpr int KIMG = BK * D * 2;          // K image: [128 keys][D]
-  constexpr int QT = BQ * D * 2;            // one Q (or dO) tile image: [64][D]
-  constexpr int DST = BK * BQ * 2;          // dS^T image: [128 keys][64 q]
-  constexpr int NQC = BQ * CH / 256;        // chunks per thread per Q (and per dO) tile
-  constexpr int DQT = QS * ND / 4;          // 32x32 dQ tiles per wave per query tile
-  static_assert(NQC >= 1 && DQT >= 1, "head dim");
-  __shared__ __attribute__((aligned(16))) char smem[KIMG + 4 * QT + DST + 4 * BQ * 4];
-  char* const kimg = smem;
-  char* const qtiles = smem + KIMG;         // [buf][Q, dO]
-  char* const dst = qtiles + 4 * QT;
-  float* const rowc = reinterpret_cast<float*>(dst + DST);  // [buf][lse(64), delta(64)]
-
-  const int T = a.T;
-  const int nk = (T + BK - 1) / BK;
-  const BlockId bo = block_order(blockIdx.x, nk, a.H * a.B, D == 128 ? 32 : 64);
-  const int kblk = bo.rank;  // block 0 (all queries) first
-  const int bh = bo.bh, h = bh % a.H, b = bh / a.H;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hh = lane >> 5;
-  const int k0 = kblk * BK, kw = k0 + 32 * w, key = kw + r;
-
-  const __bf16* qb = q + base_off(a, TQ, b, h);
-  const __bf16* kb = k + base_off(a, TK, b, h);
-  const __bf16* vb = v + base_off(a, TV, b, h);
-  const __bf16* dob = dout + base_off(a, TDO, b, h);
-  const long long qt = a.s[TQ][2], kt = a.s[TK][2], vt = a.s[TV][2], dot = a.s[TDO][2];
-  const float* lseb = lse + ((long long)b * a.H + h) * T;
-  const float* deltab = delta + ((long long)b * a.H + h) * T;
-  const auto rdq = slice_rsrc(dq_acc + b * dq_sb + h * dq_sh, 4LL * T * dq_st);
-
-  // K image for the dQ product (tr reads) and the S product (row reads); V rows in registers
-#pragma unroll
-  for (int i = 0; i < BK * CH / 256; ++i) {
-    const int c = tid + 256 * i, row = c / CH, ch = c % CH;
-    u32x4 x = {0u, 0u, 0u, 0u};
-    if (k0 + row < T) x = gload16(kb + (k0 + row) * kt + ch * 8);
-    *reinterpret_cast<u32x4*>(kimg + img_off<D>(row, ch)) = x;
-  }
-  bf16x8 vf[KS];
-#pragma unroll
-  for (int kk = 0; kk < KS; ++kk) {
-    u32x4 x = {0u, 0u, 0u, 0u};
-    if (key < T) x = gload16(vb + key * vt + kk * 16 + 8 * hh);
-    vf[kk] = __builtin_bit_cast(bf16x8, x);
-  }
-
-  const int qstart = CAUSAL ? k0 : 0;
-  const int ntiles = (T - qstart + BQ - 1) / BQ;
-
-  constexpr bool kDma = KFATT_DMA && KFATT_BUF;
-  u32x4 qreg[kDma ? 1 : NQC], oreg[kDma ? 1 : NQC];
-  float rreg = 0.f;
-  const auto rq = slice_rsrc(qb, 2LL * T * qt), rdo = slice_rsrc(dob, 2LL * T * dot);
-  // (the selector through readfirstlane: a per-lane select of the base would make the compiler wrap
-  // the load in a waterfall loop over descriptor values)
-  const auto rrow = slice_rsrc(__builtin_amdgcn_readfirstlane(w) == 0 ? lseb : deltab, 4LL * T);
-  const i32x4 dq_desc = slice_desc(qb, 2LL * T * qt), ddo_desc = slice_desc(dob, 2LL * T * dot);
-  const i32x4 drow_desc = slice_desc(__builtin_amdgcn_readfirstlane(w) == 0 ? lseb : deltab, 4LL * T);
-  auto stage_load = [&](int tile) {
-    const int q0 = qstart + tile * BQ;
-#pragma unroll
-    for (int i = 0; i < (kDma ? 0 : NQC); ++i) {
-      const int c = tid + 256 * i, row = c / CH, ch = c % CH;
-      if constexpr (KFATT_BUF) {
-        qreg[i] = bload16(rq, 2 * ((q0 + row) * (int)qt + ch * 8));
-        oreg[i] = bload16(rdo, 2 * ((q0 + row) * (int)dot + ch * 8));
-      } else {
-        u32x4 xq = {0u, 0u, 0u, 0u}, xo = {0u, 0u, 0u, 0u};
-        if (q0 + row < T) {
-          xq = gload16(qb + (q0 + row) * qt + ch * 8);
-          xo = gload16(dob + (q0 + row) * dot + ch * 8);
-        }
-        qreg[i] = xq;
-        oreg[i] = xo;
-      }
-    }
-    if (!kDma && tid < 2 * BQ) {  // waves 0 / 1: the tile's lse / delta (rows past T read 0)
-      const int row = tid & (BQ - 1);
-      if constexpr (KFATT_BUF) {
-        rreg = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrow, 4 * (q0 + row), 0, 0));
-      } else {
-        rreg = 0.f;
-        if (q0 + row < T) rreg = tid < BQ ? lseb[q0 + row] : deltab[q0 + row];
-      }
-    }
-  };
-  auto stage_write = [&](int buf) {
-    char* qi = qtiles + buf * 2 * QT;
-    char* oi = qi + QT;
-    if constexpr (!kDma) {
-#pragma unroll
-      for (int i = 0; i < NQC; ++i) {
-        const int c = tid + 256 * i, row = c / CH, ch = c % CH;
-        const int off = img_off<D>(row, ch);
-        *reinterpret_cast<u32x4*>(qi + off) = qreg[i];
-        *reinterpret_cast<u32x4*>(oi + off) = oreg[i];
-      }
-    }
-    if (!kDma && tid < 2 * BQ) rowc[buf * 2 * BQ + tid] = rreg;
-  };
-  // KFATT_DMA: the Q / dO tiles go global -> LDS by LDS-DMA (buffer_load ... lds), no staging
-  // registers. A wave instruction fills 1 KiB of the image linearly (lane L at +16 L), so each lane
-  // fetches the chunk that the swizzle puts there: image chunk sc of row `row` holds source chunk
-  // sc ^ swz(row, 0) (the swizzle is an XOR per row). Rows past T land as zeros (buffer range).
-  // LDS-DMA pieces: uniform wave index, per-lane source offsets computed once (as the forward's)
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  int dvo_q[kDma ? NQC : 1], dvo_o[kDma ? NQC : 1];
-#pragma unroll
-  for (int i = 0; i < (kDma ? NQC : 0); ++i) {
-    const int byte = (wu * NQC + i) * 1024 + lane * 16;
-    const int row = byte / (D * 2), ch = ((byte % (D * 2)) >> 4) ^ swz<D>(row, 0);
-    dvo_q[i] = 2 * (row * (int)qt + ch * 8);
-    dvo_o[i] = 2 * (row * (int)dot + ch * 8);
-  }
-  auto stage_dma = [&](int tile, int buf) {
-    const int q0 = qstart + tile * BQ;
-    char* qi = qtiles + buf * 2 * QT;
-    char* oi = qi + QT;
-#pragma unroll
-    for (int i = 0; i < NQC; ++i) {
-      dma16(dq_desc, lds_addr(qi + (wu * NQC + i) * 1024), dvo_q[i], 2 * q0 * (int)qt);
-      dma16(ddo_desc, lds_addr(oi + (wu * NQC + i) * 1024), dvo_o[i], 2 * q0 * (int)dot);
-    }
-    // waves 0 / 1: the tile's 64 lse / delta values (no register staging: a pending load into a
-    // register made the compiler wait vmcnt(0) before the tile's first MFMA)
-    if (wu < 2) dma4(drow_desc, lds_addr(reinterpret_cast<const char*>(rowc + buf * 2 * BQ + wu * BQ)), 4 * lane, 4 * q0);
-  };
-
-  const float c = a.scale * kLog2e;
-  f32x16 dkacc[ND], dvacc[ND];
-#pragma unroll
-  for (int n = 0; n < ND; ++n) {
-    dkacc[n] = (f32x16){};
-    dvacc[n] = (f32x16){};
-  }
-
-  if (ntiles > 0) {
-    if constexpr (kDma) stage_dma(0, 0);
-    stage_load(0);
-    if constexpr (kDma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stage_write(0);
-  }
-  __syncthreads();
-
-  // per-lane LDS read offsets computed once; the q-tile loop unrolled over the two buffers so the
-  // buffer / sub-tile / k-step parts of every read ride in the ds_read immediate (as the forward)
-  int koff[KS], voff0[ND], voff1[ND];
-#pragma unroll
-  for (int kk = 0; kk < KS; ++kk) koff[kk] = img_off<D>(r, 2 * kk + hh);  // + 32 j / 32 w rows
-  {
-    const int g = lane >> 4, i = lane & 15, qq = i >> 2, pp = i & 3;
-#pragma unroll
-    for (int n = 0; n < ND; ++n) {
-      const int col = 32 * n + 16 * (g & 1) + 4 * pp;
-      voff0[n] = img_off<D>(4 * hh + qq, col >> 3) + 8 * (pp & 1);
-      voff1[n] = img_off<D>(4 * hh + qq + 8, col >> 3) + 8 * (pp & 1);
-    }
-  }
-  const char* const kimg_w = kimg + 32 * w * D * 2;  // this wave's 32 key rows
-  auto tile_body = [&](int it, auto BUFC) __attribute__((always_inline)) {
-    constexpr int BUF = decltype(BUFC)::value;
-    const int q0 = qstart + it * BQ;
-    const bool more = it + 1 < ntiles;
-    if (more) {
-      if constexpr (kDma) stage_dma(it + 1, 1 - BUF);
-      stage_load(it + 1);
-    }
-    const char* qi = qtiles + BUF * 2 * QT;
-    const char* oi = qi + QT;
-    const float* lse_s = rowc + BUF * 2 * BQ;
-    const float* del_s = lse_s + BQ;
-
-    // causal: every query of the tile precedes every key of the wave -> P = dS = 0
-    const bool idle = CAUSAL && q0 + BQ - 1 < kw;
-    if (!idle) {
-      const bool need_mask = (CAUSAL && q0 < kw + 31) || q0 + BQ > T || key >= T;
-#pragma unroll
-      for (int j = 0; j < QS; ++j) {
-        // one 32-row sub-tile at a time: its P / dS fragments are consumed before the next one's exist
-        uint32_t pf[2][4], sf[2][4];
-        f32x16 sacc, dpacc;
-        // row constants nl = -lse / scale and nd = -delta (the prologue's) for this lane's query rows
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + 32 * j + 8 * g + 4 * hh);
-          const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_s + 32 * j + 8 * g + 4 * hh);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            sacc[4 * g + e] = l4[e];   // nl = -lse / scale
-            dpacc[4 * g + e] = d4[e];  // nd = -delta
-          }
-        }
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-          const bf16x8 qa = lds_row(qi + 32 * j * D * 2, koff[kk]);
-          const bf16x8 kbf = lds_row(kimg_w, koff[kk]);
-          sacc = mfma32(qa, kbf, sacc);
-          const bf16x8 oa = lds_row(oi + 32 * j * D * 2, koff[kk]);
-          dpacc = mfma32(oa, vf[kk], dpacc);
-        }
-        // P and dS; rows q = q0 + 32 j + (e & 3) + 8 (e >> 2) + 4 hh, column = this lane's key
-#pragma unroll
-        for (int e = 0; e < 16; e += 2) {
-          float p0 = fast_exp2(sacc[e] * c), p1 = fast_exp2(sacc[e + 1] * c);
-          if (need_mask) {
-            const int qa0 = q0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            if ((CAUSAL && qa0 < key) || qa0 >= T || key >= T) p0 = 0.f;
-            if ((CAUSAL && qa0 + 1 < key) || qa0 + 1 >= T || key >= T) p1 = 0.f;
-          }
-          pf[e >> 3][(e & 7) >> 1] = pack2(p0, p1);
-          sf[e >> 3][(e & 7) >> 1] = pack2(p0 * dpacc[e], p1 * dpacc[e + 1]);
-        }
-        // dS^T image [key][q]: registers 4g..4g+3 are queries 32 j + 8 g + 4 hh .. +3 of this lane's key
-        if constexpr (!DQS) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const u32x2 v2 = {sf[g >> 1][2 * (g & 1)], sf[g >> 1][2 * (g & 1) + 1]};
-            *reinterpret_cast<u32x2*>(dst + dst_off(32 * w + r, 8 * j + 2 * g + hh)) = v2;
-          }
-        }
-        // dV^T += dO^T . P and dK^T += Q^T . dS over this sub-tile's rows (permuted k order)
-#pragma unroll
-        for (int n = 0; n < ND; ++n) {
-#pragma unroll
-          for (int sx = 0; sx < 2; ++sx) {
-            const u32x4 pw = {pf[sx][0], pf[sx][1], pf[sx][2], pf[sx][3]};
-            const u32x4 sw = {sf[sx][0], sf[sx][1], sf[sx][2], sf[sx][3]};
-            const bf16x8 doa = join(tr_read(oi + (32 * j + 16 * sx) * D * 2, voff0[n]),
-                                    tr_read(oi + (32 * j + 16 * sx) * D * 2, voff1[n]));
-            dvacc[n] = mfma32(doa, __builtin_bit_cast(bf16x8, pw), dvacc[n]);
-            const bf16x8 qa = join(tr_read(qi + (32 * j + 16 * sx) * D * 2, voff0[n]),
-                                   tr_read(qi + (32 * j + 16 * sx) * D * 2, voff1[n]));
-            dkacc[n] = mfma32(qa, __builtin_bit_cast(bf16x8, sw), dkacc[n]);
-          }
-        }
-      }
-    } else if constexpr (!DQS) {
-      // this wave's 32 rows of the dS^T image are zero (lane half hh clears slots 8 hh .. 8 hh + 7)
-#pragma unroll
-      for (int sl = 0; sl < 8; ++sl)
-        *reinterpret_cast<u32x2*>(dst + dst_off(32 * w + r, 8 * hh + sl)) = (u32x2){0u, 0u};
-    }
-    if constexpr (!DQS) __syncthreads();
-
-    // dQ[q][d]: this wave's 32x32 output tiles (query sub-tile j, d tile n), all 128 keys: A = dS rows
-    // from the [key][q] image by tr reads, B = K columns from the K image by tr reads
-    // (DQS: dQ is the atomic-free attn_bwd_dq_split kernel's)
-    if constexpr (!DQS) {
-      const int g = lane >> 4, i = lane & 15, qq = i >> 2, p = i & 3;
-#pragma unroll
-      for (int tt = 0; tt < DQT; ++tt) {
-        const int t = w + 4 * tt, j = t / ND, dqn = t % ND;
-        f32x16 dqacc = (f32x16){};
-#pragma unroll
-        for (int kk = 0; kk < BK / 16; ++kk) {
-          const int kr = 16 * kk + 8 * hh + qq;          // key row of this lane's tr-read address
-          const int qs = 8 * j + 4 * (g & 1) + p;        // 8-B slot of queries 32 j + 16 (g & 1) + 4 p .. +3
-          const bf16x8 da = join(tr_read(dst, dst_off(kr, qs)), tr_read(dst, dst_off(kr + 4, qs)));
-          const int dc = 32 * dqn + 16 * (g & 1) + 4 * p;
-          const bf16x8 kbf = join(tr_read(kimg, img_off<D>(kr, dc >> 3) + 8 * (p & 1)),
-                                  tr_read(kimg, img_off<D>(kr + 4, dc >> 3) + 8 * (p & 1)));
-          dqacc = mfma32(da, kbf, dqacc);
-        }
-        // rows q0 + 32 j + (e & 3) + 8 (e >> 2) + 4 hh, column d = 32 dqn + r: f32 atomics, each wave
-        // instruction two 128-B row segments
-        if constexpr (KFATT_BUF) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int qr = q0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            // (KFATT_ABL == 1, timing ablation only: every atomic out of range, dropped by the address unit)
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dqacc[e], rdq,
-                                                            4 * (qr * (int)dq_st + 32 * dqn + r) | (KFATT_ABL == 1 ? 0x70000000 : 0), 0, 0);
-          }
-        } else {
-          float* dqb = dq_acc + b * dq_sb + h * dq_sh + 32 * dqn + r;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int qr = q0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            if (qr < T) __hip_atomic_fetch_add(dqb + qr * dq_st, dqacc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-    }
-    if (more) {
-      // the next tile's LDS-DMA pieces (and the lse / delta load) were issued before this tile's
-      // DQT x 16 dQ atomics: waiting down to that many outstanding lands exactly them
-      if constexpr (kDma) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DQS ? 0 : DQT * 16) : "memory");
-      stage_write(1 - BUF);
-    }
-    __syncthreads();
-  };
-  for (int it = 0; it < ntiles; it += 2) {
-    tile_body(it, std::integral_constant<int, 0>{});
-    if (it + 1 < ntiles) tile_body(it + 1, std::integral_constant<int, 1>{});
-  }
-
-  // epilogue: dK = scale * (dK^T)^T, dV; lane = key, rows d = 32 n + (e & 3) + 8 (e >> 2) + 4 hh
-  if (key < T) {
-    __bf16* dkr = dk + base_off(a, TDK, b, h) + key * a.s[TDK][2];
-    __bf16* dvr = dv + base_off(a, TDV, b, h) + key * a.s[TDV][2];
-#pragma unroll
-    for (int n = 0; n < ND; ++n) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = 32 * n + 8 * g + 4 * hh;
-        const float s = a.scale;
-        *reinterpret_cast<u32x2*>(dkr + d) =
-            (u32x2){pack2(dkacc[n][4 * g] * s, dkacc[n][4 * g + 1] * s), pack2(dkacc[n][4 * g + 2] * s, dkacc[n][4 * g + 3] * s)};
-        *reinterpret_cast<u32x2*>(dvr + d) =
-            (u32x2){pack2(dvacc[n][4 * g], dvacc[n][4 * g + 1]), pack2(dvacc[n][4 * g + 2], dvacc[n][4 * g + 3])};
-      }
-    }
-  }
-}
-
-// dq (bf16, strided) = scale * dq_acc (f32 [B][T][H][D] with strides st / sh / sb)
-template <int D>
-__global__ __launch_bounds__(256) void attn_bwd_dq(const float* __restrict__ dq_acc, __bf16* __restrict__ dq,
-                                                   AttnShape a, long long st, long long sh, long long sb) {
-  constexpr int LPR = D / 8;
-  constexpr int RPB = 256 / LPR;
-  const long long nrows = (long long)a.B * a.H * a.T;
-  const long long row = (long long)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int part = threadIdx.x % LPR;
-  if (row >= nrows) return;
-  const int t = (int)(row % a.T);
-  const int h = (int)((row / a.T) % a.H);
-  const int b = (int)(row / ((long long)a.T * a.H));
-  const float* src = dq_acc + b * sb + h * sh + t * st + part * 8;
-  const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
-  const float s = a.scale;
-  const u32x4 y = {pack2(x0[0] * s, x0[1] * s), pack2(x0[2] * s, x0[3] * s), pack2(x1[0] * s, x1[1] * s),
-                   pack2(x1[2] * s, x1[3] * s)};
-  *reinterpret_cast<u32x4*>(dq + base_off(a, TDQ, b, h) + t * a.s[TDQ][2] + part * 8) = y;
-}
-
 bool fill_shape(AttnShape& s, int B, int H, int T, int D, float scale, const long long* strides, int ntensors) {
   if (B <= 0 || H <= 0 || T <= 0 || (D != 64 && D != 128) || !strides) return false;
   s.B = B;
@@ -1946,7 +1168,7 @@ int device_cus() {
   return n;
 }
 
-// a (b, h) slice of T rows read through a buffer descriptor (KFATT_BUF): 32-bit byte offsets
+// a (b, h) slice of T rows read through a buffer descriptor: 32-bit byte offsets
 bool slice_ok(int T, long long row_stride, int elem_bytes) {
   return row_stride > 0 && (long long)T * row_stride * elem_bytes < (1ll << 31);
 }
@@ -2003,7 +1225,7 @@ int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* 
   const long long g4 = (long long)(pair4 ? nq4 / 2 : nq4) * H * B;
   // attn_fwd_pp where its grid fills the chip (one workgroup per CU); attn_fwd otherwise and at
   // D = 64, where the two-workgroups-per-CU kernel measured faster (profiles/r6d_attn_pp)
-  if (KFATT_FWD_PP && D == 128 && g4 >= device_cus()) {
+  if (D == 128 && g4 >= device_cus()) {
     const bool pair = pair4;
     auto go4 = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3((unsigned)g4), dim3(512), 0, st, static_cast<const __bf16*>(q),
@@ -2012,20 +1234,7 @@ int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* 
     };
     pair ? go4(attn_fwd_pp<128, true, true>) : causal ? go4(attn_fwd_pp<128, true, false>)
                                                    : go4(attn_fwd_pp<128, false, false>);
-  } else if constexpr (KFATT_FWD_NW == 8) {  // 8 waves x 32 rows per workgroup (A/B knob)
-    const int nq8 = (T + 255) / 256;
-    const bool pair = KFATT_FWD_PAIR && causal && nq8 % 2 == 0;
-    const long long g8 = (long long)(pair ? nq8 / 2 : nq8) * H * B;
-    auto go8 = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((unsigned)g8), dim3(512), 0, st, static_cast<const __bf16*>(q),
-                         static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<__bf16*>(o),
-                         static_cast<float*>(lse), s);
-    };
-    if (D == 128) pair ? go8(attn_fwd<128, true, true, 8>) : causal ? go8(attn_fwd<128, true, false, 8>)
-                                                                    : go8(attn_fwd<128, false, false, 8>);
-    else pair ? go8(attn_fwd<64, true, true, 8>) : causal ? go8(attn_fwd<64, true, false, 8>)
-                                                          : go8(attn_fwd<64, false, false, 8>);
-  } else if (KFATT_FWD_PAIR && causal && nq % 2 == 0) {
+  } else if (causal && nq % 2 == 0) {
     auto go2 = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3((unsigned)(nwg / 2)), dim3(256), 0, st, static_cast<const __bf16*>(q),
                          static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<__bf16*>(o),
@@ -2042,9 +1251,8 @@ int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* 
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
 
-// only the default schedule (split dQ kernel with delta, 8-wave dK / dV at both head dims) knows grouped K / V
-constexpr bool kGroupedBwd = KFATT_DQ_SPLIT && KFATT_DQ_DELTA && KFATT_DKDV8 && KFATT_DKDV8_64;
-
+// One schedule: attn_bwd_dq_split (dQ, and the row constants nl / nd into the workspace), then attn_bwd_dkdv8,
+// then (grouped K / V with GS < G) attn_bwd_gqa_reduce over the parts' fp32 sums behind nl / nd in the workspace.
 // group_split: 0 = gqa_group_split's rule, else the GS to use (a divisor of G). Hkv == H: the ungrouped kernels.
 int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout, const void* lse,
                     void* dq, void* dk, void* dv, void* workspace, int B, int H, int Hkv, int T, int D, float scale,
@@ -2054,136 +1262,50 @@ int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, 
   if (!fill_shape(s, B, H, T, D, scale, strides, 8) || !set_kv_heads(s, Hkv)) return KFAMD_EINVAL;
   if (group_split < 0 || (group_split > 0 && s.G % group_split != 0)) return KFAMD_EINVAL;
   const bool grouped = Hkv != H;
-  if (grouped && !kGroupedBwd) return KFAMD_EINVAL;
   if (grouped) s.GS = group_split > 0 ? group_split : gqa_group_split(B, H, Hkv, T, D);
   if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(dout) || !al16(dq) || !al16(dk) || !al16(dv) ||
       !al16(workspace))
     return KFAMD_EALIGN;
   const long long nk = (long long)((T + BK - 1) / BK) * H * B;
   if (nk >= (1ll << 31)) return KFAMD_EINVAL;
+  if (!slice_ok(T, s.s[TQ][2], 2) || !slice_ok(T, s.s[TDO][2], 2)) return KFAMD_EINVAL;
+  if (!slice_ok(T, s.s[TK][2], 2) || !slice_ok(T, s.s[TV][2], 2)) return KFAMD_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* dq_acc = static_cast<float*>(workspace);  // (unused with KFATT_DQ_SPLIT)
-  // the prologue's row constants: nl = -lse / scale and nd = -delta, [B][H][T] each
-  float* nl = dq_acc + (KFATT_DQ_SPLIT ? 0LL : (long long)B * T * H * D);
+  float* nl = static_cast<float*>(workspace);  // -lse / scale and -delta, [B][H][T] each
   float* nd = nl + (long long)B * H * T;
-  const long long dq_st = (long long)H * D, dq_sh = D, dq_sb = (long long)T * H * D;
-  if (!slice_ok(T, s.s[TQ][2], 2) || !slice_ok(T, s.s[TDO][2], 2) || !slice_ok(T, dq_st, 4)) return KFAMD_EINVAL;
-  const long long rows = (long long)B * H * T;
-  const unsigned rblocks = (unsigned)((rows + 256 / (D / 8) - 1) / (256 / (D / 8)));
-  hipError_t e = hipSuccess;
-  if constexpr (KFATT_DQ_SPLIT) {
-    // dK / dV kernel without the dQ phase, then the atomic-free dQ kernel (no fp32 workspace)
-    const long long nq = (long long)((T + FQ - 1) / FQ) * H * B;
-    if (!slice_ok(T, s.s[TK][2], 2) || !slice_ok(T, s.s[TV][2], 2)) return KFAMD_EINVAL;
-    auto run = [&](auto delta_k, auto main_k, auto dq_k) {
-      hipLaunchKernelGGL(delta_k, dim3(rblocks), dim3(256), 0, st, static_cast<const __bf16*>(o),
-                         static_cast<const __bf16*>(dout), static_cast<const float*>(lse), nl, nd, s);
-      hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(256), 0, st, static_cast<const __bf16*>(q),
-                         static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<const __bf16*>(dout),
-                         static_cast<const float*>(nl), static_cast<const float*>(nd), dq_acc,
-                         static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s, dq_st, dq_sh, dq_sb);
-      hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
-                         static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<const __bf16*>(dout),
-                         static_cast<const float*>(nl), static_cast<const float*>(nd), static_cast<__bf16*>(dq), s,
-                         static_cast<const __bf16*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr));
-    };
-    if (KFATT_DQ_DELTA && (D == 128 ? KFATT_DKDV8 : KFATT_DKDV8_64)) {
-      // the dQ kernel first, as the prologue too (nl / nd), then the 8-wave dK / dV kernel
-      const bool pair = KFATT_DQ_PAIR && causal && ((T + FQ - 1) / FQ) % 2 == 0;
-      // grouped K / V: the dK / dV grid runs over K / V heads and the G / GS parts of each group; the parts'
-      // fp32 sums (GS < G) sit behind nl / nd in the workspace and attn_bwd_gqa_reduce finishes them
-      const long long nkg = grouped ? nk / s.G * (s.G / s.GS) : nk;
-      float* gpart = grouped && s.GS != s.G ? reinterpret_cast<float*>(static_cast<char*>(workspace) + align16(2LL * B * H * T * 4))
-                                            : nullptr;
-      auto runq = [&](auto dq_k, auto main_k) {
-        hipLaunchKernelGGL(dq_k, dim3((unsigned)(pair ? nq / 2 : nq)), dim3(256), 0, st, static_cast<const __bf16*>(q),
-                           static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(lse),
-                           static_cast<const float*>(nullptr), static_cast<__bf16*>(dq), s,
-                           static_cast<const __bf16*>(o), nl, nd);
-        hipLaunchKernelGGL(main_k, dim3((unsigned)nkg), dim3(512), 0, st, static_cast<const __bf16*>(q),
-                           static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s, gpart);
-        if (gpart) {
-          const long long krows = (long long)B * Hkv * T;
-          const unsigned kblocks = (unsigned)((krows + 256 / (D / 8) - 1) / (256 / (D / 8)));
-          if (D == 128) hipLaunchKernelGGL(attn_bwd_gqa_reduce<128>, dim3(kblocks), dim3(256), 0, st, gpart,
-                                           static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
-          else hipLaunchKernelGGL(attn_bwd_gqa_reduce<64>, dim3(kblocks), dim3(256), 0, st, gpart,
-                                  static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s);
-        }
-      };
-      if (grouped) {
-        if (D == 128) causal ? runq(attn_bwd_dq_split<128, true, true>, attn_bwd_dkdv8<128, true, true>)
-                             : runq(attn_bwd_dq_split<128, false, true>, attn_bwd_dkdv8<128, false, true>);
-        else causal ? runq(attn_bwd_dq_split<64, true, true>, attn_bwd_dkdv8<64, true, true>)
-                    : runq(attn_bwd_dq_split<64, false, true>, attn_bwd_dkdv8<64, false, true>);
-      } else
-      if (pair) D == 128 ? runq(attn_bwd_dq_split<128, true, true, true>, attn_bwd_dkdv8<128, true>)
-                         : runq(attn_bwd_dq_split<64, true, true, true>, attn_bwd_dkdv8<64, true>);
-      else if (D == 128) causal ? runq(attn_bwd_dq_split<128, true, true>, attn_bwd_dkdv8<128, true>)
-                                : runq(attn_bwd_dq_split<128, false, true>, attn_bwd_dkdv8<128, false>);
-      else causal ? runq(attn_bwd_dq_split<64, true, true>, attn_bwd_dkdv8<64, true>)
-                  : runq(attn_bwd_dq_split<64, false, true>, attn_bwd_dkdv8<64, false>);
-    } else if (KFATT_DKDV8 && D == 128) {
-      auto run8 = [&](auto delta_k, auto main_k, auto dq_k) {
-        hipLaunchKernelGGL(delta_k, dim3(rblocks), dim3(256), 0, st, static_cast<const __bf16*>(o),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(lse), nl, nd, s);
-        hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(512), 0, st, static_cast<const __bf16*>(q),
-                           static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s,
-                           static_cast<float*>(nullptr));
-        hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
-                           static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dq), s,
-                           static_cast<const __bf16*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr));
-      };
-      causal ? run8(attn_bwd_delta<128>, attn_bwd_dkdv8<128, true>, attn_bwd_dq_split<128, true>)
-             : run8(attn_bwd_delta<128>, attn_bwd_dkdv8<128, false>, attn_bwd_dq_split<128, false>);
-    } else if (D == 128) causal ? run(attn_bwd_delta<128>, attn_bwd<128, true, true>, attn_bwd_dq_split<128, true>)
-                         : run(attn_bwd_delta<128>, attn_bwd<128, false, true>, attn_bwd_dq_split<128, false>);
-    else if (KFATT_DKDV8_64) {
-      auto run8 = [&](auto delta_k, auto main_k, auto dq_k) {
-        hipLaunchKernelGGL(delta_k, dim3(rblocks), dim3(256), 0, st, static_cast<const __bf16*>(o),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(lse), nl, nd, s);
-        hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(512), 0, st, static_cast<const __bf16*>(q),
-                           static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s,
-                           static_cast<float*>(nullptr));
-        hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
-                           static_cast<const __bf16*>(k), static_cast<const __bf16*>(v),
-                           static_cast<const __bf16*>(dout), static_cast<const float*>(nl),
-                           static_cast<const float*>(nd), static_cast<__bf16*>(dq), s,
-                           static_cast<const __bf16*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr));
-      };
-      causal ? run8(attn_bwd_delta<64>, attn_bwd_dkdv8<64, true>, attn_bwd_dq_split<64, true>)
-             : run8(attn_bwd_delta<64>, attn_bwd_dkdv8<64, false>, attn_bwd_dq_split<64, false>);
-    } else causal ? run(attn_bwd_delta<64>, attn_bwd<64, true, true>, attn_bwd_dq_split<64, true>)
-                : run(attn_bwd_delta<64>, attn_bwd<64, false, true>, attn_bwd_dq_split<64, false>);
-    e = hipGetLastError();
-    return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
-  }
-  e = hipMemsetAsync(dq_acc, 0, (size_t)B * T * H * D * 4, st);
-  if (e != hipSuccess) return static_cast<int>(e);
-  auto run = [&](auto delta_k, auto main_k, auto dq_k) {
-    hipLaunchKernelGGL(delta_k, dim3(rblocks), dim3(256), 0, st, static_cast<const __bf16*>(o),
-                       static_cast<const __bf16*>(dout), static_cast<const float*>(lse), nl, nd, s);
-    hipLaunchKernelGGL(main_k, dim3((unsigned)nk), dim3(256), 0, st, static_cast<const __bf16*>(q),
+  const long long nq = (long long)((T + FQ - 1) / FQ) * H * B;
+  // grouped K / V: the dK / dV grid runs over K / V heads and the G / GS parts of each group
+  const long long nkg = grouped ? nk / s.G * (s.G / s.GS) : nk;
+  float* gpart = grouped && s.GS != s.G ? reinterpret_cast<float*>(static_cast<char*>(workspace) + align16(2LL * B * H * T * 4))
+                                        : nullptr;
+  auto run = [&](auto dq_k, auto dkdv_k, auto reduce_k) {
+    hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
                        static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<const __bf16*>(dout),
-                       static_cast<const float*>(nl), static_cast<const float*>(nd), dq_acc,
-                       static_cast<__bf16*>(dk), static_cast<__bf16*>(dv), s, dq_st, dq_sh, dq_sb);
-    hipLaunchKernelGGL(dq_k, dim3(rblocks), dim3(256), 0, st, static_cast<const float*>(dq_acc),
-                       static_cast<__bf16*>(dq), s, dq_st, dq_sh, dq_sb);
+                       static_cast<const float*>(lse), static_cast<const float*>(nullptr), static_cast<__bf16*>(dq), s,
+                       static_cast<const __bf16*>(o), nl, nd);
+    hipLaunchKernelGGL(dkdv_k, dim3((unsigned)nkg), dim3(512), 0, st, static_cast<const __bf16*>(q),
+                       static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<const __bf16*>(dout),
+                       static_cast<const float*>(nl), static_cast<const float*>(nd), static_cast<__bf16*>(dk),
+                       static_cast<__bf16*>(dv), s, gpart);
+    if (gpart) {
+      const long long krows = (long long)B * Hkv * T;
+      const unsigned kblocks = (unsigned)((krows + 256 / (D / 8) - 1) / (256 / (D / 8)));
+      hipLaunchKernelGGL(reduce_k, dim3(kblocks), dim3(256), 0, st, gpart, static_cast<__bf16*>(dk),
+                         static_cast<__bf16*>(dv), s);
+    }
   };
-  if (D == 128) causal ? run(attn_bwd_delta<128>, attn_bwd<128, true>, attn_bwd_dq<128>)
-                       : run(attn_bwd_delta<128>, attn_bwd<128, false>, attn_bwd_dq<128>);
-  else causal ? run(attn_bwd_delta<64>, attn_bwd<64, true>, attn_bwd_dq<64>)
-              : run(attn_bwd_delta<64>, attn_bwd<64, false>, attn_bwd_dq<64>);
-  e = hipGetLastError();
+  if (D == 128) {
+    if (grouped) causal ? run(attn_bwd_dq_split<128, true>, attn_bwd_dkdv8<128, true, true>, attn_bwd_gqa_reduce<128>)
+                        : run(attn_bwd_dq_split<128, false>, attn_bwd_dkdv8<128, false, true>, attn_bwd_gqa_reduce<128>);
+    else causal ? run(attn_bwd_dq_split<128, true>, attn_bwd_dkdv8<128, true>, attn_bwd_gqa_reduce<128>)
+                : run(attn_bwd_dq_split<128, false>, attn_bwd_dkdv8<128, false>, attn_bwd_gqa_reduce<128>);
+  } else {
+    if (grouped) causal ? run(attn_bwd_dq_split<64, true>, attn_bwd_dkdv8<64, true, true>, attn_bwd_gqa_reduce<64>)
+                        : run(attn_bwd_dq_split<64, false>, attn_bwd_dkdv8<64, false, true>, attn_bwd_gqa_reduce<64>);
+    else causal ? run(attn_bwd_dq_split<64, true>, attn_bwd_dkdv8<64, true>, attn_bwd_gqa_reduce<64>)
+                : run(attn_bwd_dq_split<64, false>, attn_bwd_dkdv8<64, false>, attn_bwd_gqa_reduce<64>);
+  }
+  const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
 
@@ -2195,12 +1317,12 @@ extern "C" int kfamd_attn_fwd_bf16(const void* q, const void* k, const void* v, 
 }
 
 extern "C" long long kfamd_attn_bwd_workspace(int B, int H, int T, int D) {
-  // nl, nd f32 [B][H][T] (+ dq_acc f32 [B][T][H][D] in front of them when dQ goes through atomics)
-  return (KFATT_DQ_SPLIT ? 0LL : (long long)B * T * H * D * 4) + 2LL * B * H * T * 4;
+  return 2LL * B * H * T * 4;  // nl, nd f32 [B][H][T]
 }
 
 // strides: 8 tensors x (b, h, t): q, k, v, o, do, dq, dk, dv. workspace: kfamd_attn_bwd_workspace bytes
-// (16-B aligned); it is zeroed here on the stream (memset node) before the dQ atomics.
+// (16-B aligned): the row constants nl / nd that the dQ kernel writes for the dK / dV kernel. Written before
+// it is read; its contents on entry do not matter.
 extern "C" int kfamd_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
                                    const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int T,
                                    int D, float scale, int causal, const long long* strides, void* stream) {
@@ -2216,7 +1338,6 @@ extern "C" int kfamd_attn_fwd_gqa_bf16(const void* q, const void* k, const void*
 
 extern "C" int kfamd_attn_bwd_gqa_group_split(int B, int H, int Hkv, int T, int D) {
   if (B <= 0 || H <= 0 || T <= 0 || (D != 64 && D != 128) || Hkv < 1 || H % Hkv != 0) return KFAMD_EINVAL;
-  if (Hkv != H && !kGroupedBwd) return KFAMD_EINVAL;
   return gqa_group_split(B, H, Hkv, T, D);
 }
 

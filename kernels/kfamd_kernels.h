@@ -215,7 +215,9 @@ const char* kfamd_build_info(void);
 // Tensors are [B][H][T][D] views with element strides (b, h, t) (multiples of 8) and D contiguous;
 // strides[3 * i + {0, 1, 2}] for tensor i in the order q, k, v, o (forward) or q, k, v, o, do, dq,
 // dk, dv (backward). lse: f32 [B][H][T] (written by the forward, read by the backward).
-// causal: key <= query. The backward zeroes and uses `workspace` (kfamd_attn_bwd_workspace bytes).
+// causal: key <= query. The backward's `workspace` (kfamd_attn_bwd_workspace bytes) holds
+// the row constants -lse / scale and -delta, f32 [B][H][T] each, that its dQ kernel writes for its dK / dV kernel; it
+// need not be zeroed.
 int kfamd_attn_fwd_bf16(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int T,
                         int D, float scale, int causal, const long long* strides, void* stream);
 long long kfamd_attn_bwd_workspace(int B, int H, int T, int D);

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
-"""Flash-attention build A/B: the kernel library re-linked with kernels/attention_bf16.hip compiled
-under other flags / -D knobs, one library per variant (kubeflow_rm_amd/lib/attnab/).
+"""Flash-attention build A/B: the kernel library re-linked with another build of kernels/attention_bf16.hip,
+one library per variant (kubeflow_rm_amd/lib/attnab/): `prod` is the working tree under the production
+flags, `head` the committed source (git HEAD) under the same flags, which is how an experiment on the
+kernel file is measured against what is committed, and `agprform` the working tree without the MFMA
+VGPR-form flag.
 
   python tools/attn_ab.py --build [--variants a,b]   # host: compile + link every variant
   KFAMD_KERNEL_LIB=kubeflow_rm_amd/lib/attnab/libkfamd_kernels_<v>.so python tools/attn_bench.py ...
@@ -25,48 +28,10 @@ def _variants():
     from kubeflow_rm_amd import _build as B
     prod = B.TU_FLAGS.get("attention_bf16.hip", [])
     return {
-        "prod": prod,  # the production flags and knob defaults
+        "prod": prod,  # the working tree with the production flags
         "head": prod,  # git HEAD's attention source with the production flags
-        "sepdelta": [*prod, "-DKFATT_DQ_DELTA=0"],  # the separate delta prologue kernel
-        "dkdv4_64": [*prod, "-DKFATT_DKDV8_64=0"],  # D = 64 with the 4-wave dK / dV kernel
-        "dkdv4": [*prod, "-DKFATT_DKDV8=0"],  # D = 128 dK / dV with the 4-wave kernel (one wave per SIMD)
         # the compiler's default AGPR form: S / dP shuttled through v_accvgpr moves
         "agprform": [],
-        "guarded": [*prod, "-DKFATT_BUF=0", "-DKFATT_DMA=0", "-DKFATT_DQ_SPLIT=0"],  # per-row guards, atomics
-        "atomics": [*prod, "-DKFATT_DQ_SPLIT=0"],  # dQ by fp32 atomics inside the dK / dV kernel
-        "atomics_regstage": [*prod, "-DKFATT_DQ_SPLIT=0", "-DKFATT_DMA=0"],  # ... Q / dO register-staged
-        "atomics_dropped": [*prod, "-DKFATT_DQ_SPLIT=0", "-DKFATT_ABL=1"],  # timing only: atomics dropped
-        "fwd_dma": [*prod, "-DKFATT_FWD_DMA=1"],  # forward K / V by LDS-DMA
-        "nolpt": [*prod, "-DKFATT_LPT=0"],  # head-major block order (no longest-first across heads)
-        "nofpair": [*prod, "-DKFATT_FWD_PAIR=0"],  # causal forward: one query block per workgroup
-        "dqpair": [*prod, "-DKFATT_DQ_PAIR=1"],  # dQ kernel: heavy + light query block per workgroup
-        "fwd8": [*prod, "-DKFATT_FWD_PP=0", "-DKFATT_FWD_NW=8"],  # forward: the unstaggered 8-wave attn_fwd
-        "fwdold": [*prod, "-DKFATT_FWD_PP=0"],  # forward: attn_fwd (4 waves, two workgroups per CU)
-        "fabl1": [*prod, "-DKFATT_FWD_ABL=1"],  # timing only: attn_fwd_pp without K / V staging
-        "fabl2": [*prod, "-DKFATT_FWD_ABL=2"],  # timing only: attn_fwd_pp without the per-tile barrier
-        "fabl3": [*prod, "-DKFATT_FWD_ABL=3"],  # timing only: neither
-        "pf1": [*prod, "-DKFATT_FWD_PF2=0"],  # attn_fwd_pp with K / V loads one tile ahead
-        "nofence": [*prod, "-DKFATT_FWD_FENCE=0"],  # attn_fwd_pp without the phase fences
-        "nowide": [*prod, "-DKFATT_FWD_WIDE=0"],  # attn_fwd_pp with 8-B O stores
-        "bnowide": [*prod, "-DKFATT_BWD_WIDE=0"],  # dQ / dK / dV with 8-B stores
-        "nopxp": [*prod, "-DKFATT_FWD_PXP=0"],  # attn_fwd_pp pairs without the cross-pass prefetch
-        "prio": [*prod, "-DKFATT_FWD_PRIO=1"],  # attn_fwd_pp with waves 4-7 at priority 1
-        "babl1": [*prod, "-DKFATT_DKDV_ABL=1"],  # timing only: dK / dV kernel without Q / dO staging
-        "babl2": [*prod, "-DKFATT_DKDV_ABL=2"],  # timing only: ... without the per-tile barrier
-        "babl4": [*prod, "-DKFATT_DKDV_ABL=4"],  # timing only: ... one K / V fragment read per tile
-        "babl7": [*prod, "-DKFATT_DKDV_ABL=7"],  # timing only: all three
-        "nopp": [*prod, "-DKFATT_FWD_PP=0"],  # forward by attn_fwd everywhere
-        "ra4": [*prod, "-DKFATT_FWD_RA=4"],  # attn_fwd_pp: LDS reads pinned 4 MFMAs ahead (r6v_ra)
-        "split": [*prod, "-DKFATT_FWD_SPLIT=1"],  # attn_fwd_pp softmax max / sum as 4 chains
-        "fra0": [*prod, "-DKFATT_FWD_RA=0"],  # attn_fwd_pp reads in the compiler's order
-        "fra1": [*prod, "-DKFATT_FWD_RA=1"],
-        "fra3": [*prod, "-DKFATT_FWD_RA=3"],
-        "f4ra1": [*prod, "-DKFATT_FWD4_RA=1"],  # attn_fwd (4 waves: D = 64, small grids) with pinned reads
-        "f4ra2": [*prod, "-DKFATT_FWD4_RA=2"],
-        "dra1": [*prod, "-DKFATT_DQ_RA=1"],  # attn_bwd_dq_split (D = 128): reads pinned 1 MFMA ahead
-        "dra2": [*prod, "-DKFATT_DQ_RA=2"],
-        "bra1": [*prod, "-DKFATT_BWD_RA=1"],  # attn_bwd_dkdv8 (D = 128): reads pinned 1 MFMA ahead
-        "bra2": [*prod, "-DKFATT_BWD_RA=2"],  # ... 2 MFMAs ahead
     }
 
 
