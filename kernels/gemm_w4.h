@@ -32,9 +32,17 @@
 //     so the LDS-DMA writes zeros (raw-buffer range check; valid pieces keep voffset + soffset inside
 //     the record, so this holds whether or not the check includes soffset). The K loop itself carries
 //     no edge code.
-// Pipeline (unchanged from r2): two LDS tiles live + one free slot, DMA of tile kt+2 spread over
-// the K-tile (1 per 8 MFMAs), fragments of the next k-substep read under the current substep's
-// MFMAs (two register sets), interleave pinned with sched_barrier.
+// Pipeline: a ring of five operand-tile slots (A or B each): K tile kt being read, tile kt+1 landing,
+// one slot free. Each K tile is two k32 substeps of MF MFMAs; the fragments of the next substep are
+// read under the current substep's MFMAs (two register sets, one read per RG MFMAs), and tile kt+2
+// streams in meanwhile, A during substep 0 and B during substep 1 (one 1-KiB piece per DMA_EVERY
+// MFMAs, the first at MFMA DMA_PHASE). Between the substeps one counted wait and one barrier, with
+// the first PB MFMAs of substep 1 issued ahead of the barrier. The interleave is pinned with a
+// sched_barrier around every MFMA and the waves run the loop at raised priority. In steady state
+// the loop is unrolled over the ring's period of five tiles (every slot index a constant) and the
+// DMA pieces are inline asm with a voffset register per piece, M0 written one MFMA ahead; stream-K
+// alone keeps the rotating loop on the builtin DMA (see kAsmDma). Interior tiles leave through LDS as
+// whole 128-B lines, with non-temporal C stores where no residual is read (see the epilogue).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -101,11 +109,8 @@ __device__ __forceinline__ kf32x2 dact2(kf32x2 z) {
   }
 }
 
-// act(z) on a pair (the forward epilogue, KFW4_ACT_PK): gelu_tanh / silu as z * sigmoid(.), the
-// polynomial parts packed as in dact2
-#ifndef KFW4_ACT_PK
-#define KFW4_ACT_PK 1
-#endif
+// act(z) on a pair (the forward epilogue's gelu_tanh / silu): z * sigmoid(.), the polynomial parts
+// packed as in dact2
 template <int ACT>
 __device__ __forceinline__ kf32x2 act2(kf32x2 z) {
   constexpr float L2E = 1.4426950408889634f;
@@ -126,13 +131,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-#ifndef KFW4_GROUP_M
-#define KFW4_GROUP_M 4  // tile-row group of the grouped raster (A/B runs build other values)
-#endif
-#ifndef KFW4_SUPER
-#define KFW4_SUPER 1  // 16 x 16-tile superblocks across the 8 XCDs for operands past the MALL (tile_of_block)
-#endif
-constexpr int kGroupM = KFW4_GROUP_M;
+constexpr int kGroupM = 4;  // tile rows per group of the grouped raster
 
 // grouped raster: work item wg of a tiles_m x tiles_n problem -> (tm, tn), groups of kGroupM tile rows
 __device__ __forceinline__ void raster_tile(int wg, int tiles_m, int tiles_n, int& tm, int& tn) {
@@ -143,9 +142,8 @@ __device__ __forceinline__ void raster_tile(int wg, int tiles_m, int tiles_n, in
   tn = (wg % per_group) / gm;
 }
 
-// Block -> output tile: the one mapping both a block's own tile and its successor's (block id + 256,
-// the successor prefetch) come from. prob = 0, 1 (GRP: the launch's second problem, M2 x N2) or -1:
-// no tile for this block id; wg = the tile's index in its problem's XCD-remapped order.
+// Block -> output tile. prob = 0, 1 (GRP: the launch's second problem, M2 x N2) or -1: no tile for
+// this block id; wg = the tile's index in its problem's XCD-remapped order.
 struct TileId {
   int prob, wg, tm, tn;
 };
@@ -168,14 +166,14 @@ __device__ __forceinline__ TileId tile_of_block(int bid, int grid, int M, int N,
     t.prob = bid >= nwg ? -1 : 0;
   }
   raster_tile(t.wg, tiles_m, tiles_n, t.tm, t.tn);
-  if constexpr (KFW4_SUPER && !GRP && BM == 256) {
+  if constexpr (!GRP && BM == 256) {
     // the chip's 256 resident tiles (one per CU) as ONE 16 x 16 block of the output: XCD x (block b
     // runs on XCD b % 8) takes its 4 x 8 sub-block, rows 4 (x & 3), columns 8 (x >> 2); the waves walk
     // the superblocks column-major. 16 A + 16 B panels are live at once instead of 32 A + 8 B with the
     // per-XCD row groups (at 16384^3 a panel is 8 MiB: 256 vs 320 MiB against the 256 MiB MALL):
     // 16384^3 0.987 -> 1.012 of hipBLASLt, 4096^3 / 8192^3 level (profiles/r6zm_super). Only where A
     // and B together exceed the MALL; smaller problems keep the row groups.
-    if ((tiles_m & 15) == 0 && (tiles_n & 15) == 0 && grid == nwg &&  // (not the persistent grid)
+    if ((tiles_m & 15) == 0 && (tiles_n & 15) == 0 && grid == nwg &&  // (not stream-K's persistent grid)
         (long long)(M + N) * K * 2 > (256LL << 20)) {
       const int b = bid, x = b & 7, i = b >> 3, wave = i >> 5, j = i & 31;
       const int sbm = tiles_m >> 4, sr = wave % sbm, sc = wave / sbm;
@@ -348,7 +346,7 @@ struct W4Grp {
 // reads R where that pass read both dY and R and wrote G. Whole interior tiles only (the host
 // requires M and N multiples of 256 and 16-B rows), on the full-line residual epilogue.
 template <int ACT, bool HAS_BIAS, bool HAS_RES, bool HAS_AUX, int LA, int LB, int BM, int SPLIT = 0,
-          bool DIAG = false, int ABL = 0, bool SK = false, bool PO = false, bool DACT = false, bool GRP = false>
+          bool DIAG = false, int ABL = 0, bool SK = false, bool DACT = false, bool GRP = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(kThreads, kThreads),
                           amdgpu_waves_per_eu(BM == 256 ? 1 : 2, BM == 256 ? 1 : 2)))
 void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16* __restrict__ C,
@@ -361,42 +359,24 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   constexpr int TILE = BM * kBK * 2;                   // bytes per operand tile
   constexpr int PIECES = BM / 32;                      // 1 KiB DMA pieces per wave per operand tile
   constexpr int MF = NR * NR;                          // MFMAs per wave per k32 substep
-  // Schedule knobs (tools/w4_ab.py A/B builds; the defaults are the production schedule):
-  //   KFW4_RG: one fragment read per RG MFMAs; KFW4_DMA_EVERY / KFW4_DMA_PHASE: DMA piece j at
-  //   MFMA j * DMA_EVERY + DMA_PHASE of its substep; KFW4_PIN_MFMA: sched_barrier around every MFMA.
-#ifndef KFW4_DMA_EVERY
-#define KFW4_DMA_EVERY 0
-#endif
-#ifndef KFW4_DMA_PHASE
-#define KFW4_DMA_PHASE 2
-#endif
-#ifndef KFW4_RG
-#define KFW4_RG 2
-#endif
-#ifndef KFW4_PIN_MFMA
-#define KFW4_PIN_MFMA 1
-#endif
-#ifndef KFW4_PRIO
-#define KFW4_PRIO 1
-#endif
-  constexpr int DMA_EVERY = KFW4_DMA_EVERY > 0 ? KFW4_DMA_EVERY : MF / PIECES;  // one DMA per DMA_EVERY MFMAs
-  constexpr int DMA_PHASE = KFW4_DMA_PHASE;
+  // The schedule of a substep: DMA piece j at MFMA j * DMA_EVERY + DMA_PHASE, one fragment read per
+  // RG MFMAs, the first PB MFMAs of substep 1 ahead of the mid barrier
+  constexpr int DMA_EVERY = MF / PIECES;  // the pieces spread evenly over the substep
+  constexpr int DMA_PHASE = 2;            // >= 1: the asm DMA's M0 is written one MFMA ahead
   static_assert(DMA_EVERY * (PIECES - 1) + DMA_PHASE < MF, "every DMA piece inside its substep");
-  constexpr int RG = KFW4_RG < MF / (2 * NR) ? KFW4_RG : MF / (2 * NR);  // 128 tile: at most 2
+  constexpr int RG = 2;
   static_assert(RG * (2 * NR - 1) < MF, "every fragment read inside its substep");
+  constexpr int PB = 1;
+  static_assert(PB + RG * (2 * NR - 1) < MF && PB <= DMA_PHASE, "pre-barrier MFMAs");
   static_assert(BM == 256 || BM == 128, "tile");
   static_assert(!HAS_AUX || ACT != KFAMD_ACT_NONE, "aux = pre-activation");
   static_assert(SPLIT != 1 || (ACT == KFAMD_ACT_NONE && !HAS_BIAS && !HAS_RES && !HAS_AUX), "split-K: epilogue in the reduce");
   static_assert(SPLIT != 2 || BM == 256, "split-K fixup: 256 tile");
   static_assert(!SK || (!HAS_AUX && BM == 256 && !SPLIT), "stream-K: 256 tile, no pre-activation output");
-  static_assert(!PO || (BM == 256 && !SPLIT && !SK && !DIAG), "persistent overlapped: 256 tile, whole K");
-  static_assert(!GRP || (SPLIT != 1 && !SK && !PO && !DACT && !HAS_BIAS && !HAS_RES && !HAS_AUX && !DIAG),
+  static_assert(!GRP || (SPLIT != 1 && !SK && !DACT && !HAS_BIAS && !HAS_RES && !HAS_AUX && !DIAG),
                 "grouped pair: plain epilogue, whole K or the in-kernel split-K fixup");
-  static_assert(!DACT || (HAS_RES && !HAS_BIAS && !HAS_AUX && ACT != KFAMD_ACT_NONE && !SPLIT && !SK && !PO),
+  static_assert(!DACT || (HAS_RES && !HAS_BIAS && !HAS_AUX && ACT != KFAMD_ACT_NONE && !SPLIT && !SK),
                 "act-grad epilogue: the pre-activation as R, 256 tile, whole K");
-  // PO: the epilogue's LDS staging lives in the ring's fifth slot, which the next tile's prologue
-  // (tiles 0 and 1 into slots 0-3) leaves alone, so that prologue can be issued before the epilogue
-  constexpr int kEpiBase = PO ? (kSlots - 1) * TILE : 0;
   __shared__ __attribute__((aligned(16))) char smem[kSlots * TILE];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -431,9 +411,6 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       nwg = t2;
     }
   }
-#ifndef KFW4_SK_AB
-#define KFW4_SK_AB 0  // stream-K timing ablations (tools/sk_ab.py builds): 1 no partial traffic, 2 no owner wait
-#endif
   const int tm = own.tm, tn = own.tn;
   int m_lo = tm * BM, n_lo = tn * BN;                  // first output row / column this block stores
   int m0 = min(m_lo, M - BM), n0 = min(n_lo, N - BN);  // edge tiles shifted inside
@@ -484,21 +461,13 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
                                              v, j * rs_b + kt * kts_b, 0, 0);
   };
 
-#ifndef KFW4_FASTK
-#define KFW4_FASTK 2  // 2: steady-state DMAs with a voffset register per piece and one soffset per K-tile
-#endif
-  // (a per-K-tile descriptor rebuild, tried as mode 1, made hipcc 7.2's host pass drop the launch stubs)
-#ifndef KFW4_UNROLL5
-#define KFW4_UNROLL5 1  // K loop unrolled over the 5-slot ring's period: every slot index a constant
-#endif
-#ifndef KFW4_ASM_DMA
-#define KFW4_ASM_DMA 1
-#endif
-  static_assert(!KFW4_ASM_DMA || (KFW4_FASTK == 2 && KFW4_DMA_PHASE >= 1), "asm DMA: voffset regs, M0 set one MFMA ahead");
-  // stream-K keeps the round-3 steady state: its persistent schedule's live state plus these
-  // registers (voffsets, descriptors, the unrolled loop's constants) spill
-  constexpr int kFastK = SK ? 0 : KFW4_FASTK;
-  constexpr bool kAsmDma = !SK && KFW4_ASM_DMA;
+  // Steady state: the DMA pieces as inline asm with a voffset register per piece and one soffset per
+  // K tile, in a K loop unrolled over the ring's period (every slot index a constant). Stream-K keeps
+  // the round-3 steady state (dma_a / dma_b, the rotating loop): its persistent schedule's live state
+  // plus these registers (voffsets, descriptors, the unrolled loop's constants) spill.
+  // (a per-K-tile descriptor rebuild made hipcc 7.2's host pass drop the launch stubs)
+  constexpr bool kAsmDma = !SK;
+  static_assert(DMA_PHASE >= 1, "asm DMA: M0 set one MFMA ahead");
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   // raw buffer descriptors as SGPR quads for the asm pieces (gfx9: base, base_hi | stride 0, records, word 3)
   auto make_desc = [&](const void* p) __attribute__((always_inline)) -> i32x4 {
@@ -508,9 +477,9 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   };
   i32x4 dra = make_desc(A), drb = make_desc(B);
   const unsigned lds_w = (unsigned)(uintptr_t)KFW4_LDS_PTR(smem) + (unsigned)(wid * PIECES * 1024);  // wave's pieces
-  // KFW4_FASTK == 2: piece j's full voffset (chunk swizzle + j rows) in a register of its own
+  // piece j's full voffset (chunk swizzle + j rows) in a register of its own
   unsigned vpa[PIECES], vpb[PIECES];
-  if (kFastK == 2) {
+  if (kAsmDma) {
 #pragma unroll
     for (int j = 0; j < PIECES; ++j) {
       vpa[j] = sta.voff[Stage<LA, BM>::variant_of_piece(j)] + (unsigned)(j * rs_a);
@@ -574,7 +543,8 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   unsigned long long sk_mask = 0;  // stream-K owner: which producer splits' partials the epilogue adds
   int sk_base = 0, sk_stride = 0;  // ... split j's partial is slot sk_base + j * sk_stride
   // prologue + K loop over the current (ra, rb, nk, koff): adds into acc
-  // the first two K tiles into slots 0-3 (PO issues them for the next tile before this one's epilogue)
+  // the first two K tiles into slots 0-3 (a lambda of its own: folded into run_k, the stream-K
+  // kernels' assembly listings change, though only in the order of register annotations)
   auto issue_prologue = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < PIECES; ++j) {
@@ -589,13 +559,11 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       }
     }
   };
-  auto run_k = [&](auto pro_issued) __attribute__((always_inline)) {
+  auto run_k = [&]() __attribute__((always_inline)) {
   // slot state (wave-uniform): tile t in (sa0, sb0), tile t+1 in (sa1, sb1), free slot sf
   int sa0 = 0, sb0 = 1, sa1 = 2, sb1 = 3, sf = 4;
-  if constexpr (!decltype(pro_issued)::value) issue_prologue();
+  issue_prologue();
   if (nk > 1) {
-    // (PO: the epilogue's stores were issued after these DMAs; counting them in too only waits
-    // longer, and the epilogue has covered the DMAs' latency)
     if constexpr (BM == 256) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   } else {
@@ -608,14 +576,14 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   for (int q = 0; q < 2 * NR; ++q) read_frag0(sa0, sb0, a0, b0, q);
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
   KFW4_PIN();
-  if (KFW4_PRIO) __builtin_amdgcn_s_setprio(1);
+  __builtin_amdgcn_s_setprio(1);
 
   // one K-tile; the slots come in as ints (rotating at run time) or integral constants (unrolled)
   auto body_g = [&](int kt, auto do_stage, auto do_next, auto sa0, auto sb0, auto sa1, auto sb1, auto sf)
       __attribute__((always_inline)) {
     constexpr bool kStage = decltype(do_stage)::value;  // tile kt+2 exists
     constexpr bool kNext = decltype(do_next)::value;    // tile kt+1 exists
-    // KFW4_ASM_DMA: the steady-state pieces as inline asm, M0 written one MFMA ahead (no s_nop for
+    // kAsmDma: the steady-state pieces as inline asm, M0 written one MFMA ahead (no s_nop for
     // the M0 -> LDS-DMA hazard, no per-piece M0 copy); waits stay the loop's explicit ones
     const unsigned lw = lds_w;  // (named here: a nested generic lambda does not capture it otherwise)
     auto m0_set = [&](int slot, int j) __attribute__((always_inline)) {
@@ -626,26 +594,11 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(v), "s"(r), "s"(so) : "memory");
     };
     auto stage_a = [&](int j) __attribute__((always_inline)) {
-      if (kAsmDma) {
-        asm_dma(dra, vpa[j], (kt + 2) * kts_a);
-      } else if (kFastK == 2) {  // per-piece voffset registers, one soffset per K-tile
-        // plain locals as the builtin's operands (see the soffset note above dma_a)
-        const unsigned v = vpa[j];
-        const int so = (kt + 2) * kts_a;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, KFW4_LDS_PTR(smem + sf * TILE + (wid * PIECES + j) * 1024), 16,
-                                                 v, so, 0, 0);
-      }
+      if (kAsmDma) asm_dma(dra, vpa[j], (kt + 2) * kts_a);
       else dma_a(kt + 2, sf, j, false);
     };
     auto stage_b = [&](int j) __attribute__((always_inline)) {
-      if (kAsmDma) {
-        asm_dma(drb, vpb[j], (kt + 2) * kts_b);
-      } else if (kFastK == 2) {
-        const unsigned v = vpb[j];
-        const int so = (kt + 2) * kts_b;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, KFW4_LDS_PTR(smem + sa0 * TILE + (wid * PIECES + j) * 1024), 16,
-                                                 v, so, 0, 0);
-      }
+      if (kAsmDma) asm_dma(drb, vpb[j], (kt + 2) * kts_b);
       else dma_b(kt + 2, sa0, j, false);
     };
     const unsigned long long t0 = stamp_k();
@@ -656,9 +609,9 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       if (kAsmDma && kStage && (m + 1) % DMA_EVERY == DMA_PHASE && (m + 1) / DMA_EVERY < PIECES)
         m0_set(sf, (m + 1) / DMA_EVERY);
       if (kStage && m % DMA_EVERY == DMA_PHASE && m / DMA_EVERY < PIECES) stage_a(m / DMA_EVERY);
-      if (KFW4_PIN_MFMA) KFW4_PIN();
+      KFW4_PIN();
       mfma(acc[m / NR][m % NR], b0[m % NR], a0[m / NR]);
-      if (KFW4_PIN_MFMA) KFW4_PIN();
+      KFW4_PIN();
     }
     const unsigned long long t1 = stamp_k();
     // tile kt+1 landed (only A_{kt+2} may still be in flight), F1(kt) in registers, then barrier:
@@ -669,13 +622,8 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     } else {
       __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
     }
-    // KFW4_PREBAR: the first substep-1 MFMAs (registers only) issue between the wait and the barrier,
-    // so the matrix pipe has work while the waves meet; the reads of tile kt+1 start after it
-#ifndef KFW4_PREBAR
-#define KFW4_PREBAR 1
-#endif
-    constexpr int PB = KFW4_PREBAR;
-    static_assert(PB + RG * (2 * NR - 1) < MF && PB <= DMA_PHASE, "pre-barrier MFMAs");
+    // the first PB substep-1 MFMAs (registers only) issue between the wait and the barrier, so the
+    // matrix pipe has work while the waves meet; the reads of tile kt+1 start after it
 #pragma unroll
     for (int m = 0; m < PB; ++m) {
       KFW4_PIN();
@@ -695,9 +643,9 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       if (kAsmDma && kStage && (m + 1) % DMA_EVERY == DMA_PHASE && (m + 1) / DMA_EVERY < PIECES)
         m0_set(sa0, (m + 1) / DMA_EVERY);
       if (kStage && m % DMA_EVERY == DMA_PHASE && m / DMA_EVERY < PIECES) stage_b(m / DMA_EVERY);
-      if (KFW4_PIN_MFMA) KFW4_PIN();
+      KFW4_PIN();
       mfma(acc[m / NR][m % NR], b1[m % NR], a1[m / NR]);
-      if (KFW4_PIN_MFMA) KFW4_PIN();
+      KFW4_PIN();
     }
     const unsigned long long t3 = stamp_k();
     if (kNext) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): F0(kt+1) in registers
@@ -733,7 +681,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   };
   if (DIAG) t_loop0 = stamp();
   int kt = 0;
-  if (KFW4_UNROLL5 && !SK) {  // (stream-K: the unrolled loop spills beside the persistent schedule's state)
+  if (kAsmDma) {  // (stream-K: the unrolled loop spills beside the persistent schedule's state)
     // the ring's period is 5 tiles: (sa0, sb0, sa1, sb1, sf) = (0,1,2,3,4) -> (2,3,4,0,1) -> (4,0,1,2,3)
     // -> (1,2,3,4,0) -> (3,4,0,1,2) -> (0,1,2,3,4); state 0 again after each group of five
     using C0 = std::integral_constant<int, 0>;
@@ -755,7 +703,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     ++kt;
   }
   if (kt < nk) body(kt, F{}, F{});
-  if (KFW4_PRIO) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
   if (DIAG) t_loop1 = stamp();
   // the asm MFMAs are opaque to the hazard recognizer: cover the MFMA -> v_accvgpr_read latency
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
@@ -767,56 +715,6 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
 #pragma unroll
     for (int n = 0; n < NR; ++n) asm volatile("" : "+a"(acc[i][n]));
   };  // run_k
-
-  // Successor prefetch (KFW4_PREFETCH_NEXT). One block per CU is resident, so the block that takes
-  // this CU's place is about block id + 256, which the dispatcher puts on the same XCD (b % 8), i.e.
-  // behind the same L2. While this block only stores, touch one dword of every 128-B row of the
-  // successor's first two K-tiles of A and B (thread t: row t of each 256-row panel; four loads per
-  // wave), so the successor's prologue finds them in L2 instead of fetching them cold with every other
-  // CU of the XCD at the same moment. The dword is the LAST of the row's K-tile: with a partial first
-  // K-tile (koff < 0) its k < 0 part is never addressed. The descriptors start at the successor's
-  // panel and end with the operand, so an address outside A / B would read as zero, never fault.
-  // The loads are ordinary counted loads whose results nobody reads: they stay live up to the end of
-  // the epilogue (keep_prefetch), whose wait sits right before s_endpgm (which waits for the wave's
-  // memory operations anyway).
-  // OFF in production (tools/w4_ab.py builds it as `prefetch`): the successor's prologue gets ~650
-  // cycles shorter, but the 1024 scattered line requests per block queue ahead of this block's stores
-  // and its epilogue gets ~2000 cycles longer: 8192^3 level, the K = 2048 shapes 1-2 % slower
-  // (profiles/w4_prefetch).
-#ifndef KFW4_PREFETCH_NEXT
-#define KFW4_PREFETCH_NEXT 0
-#endif
-  constexpr int kResident = 256;  // blocks between a block and its successor on the same CU / XCD
-  constexpr bool kPrefetch = KFW4_PREFETCH_NEXT && BM == 256 && LA == 0 && LB == 0 && !SPLIT && !SK && !PO &&
-                             !GRP && !DACT && ABL == 0;
-  int pf[4] = {0, 0, 0, 0};
-  auto prefetch_next = [&]() __attribute__((always_inline)) {
-    if constexpr (kPrefetch) {
-      const int nb = blockIdx.x + kResident;
-      if (nb < (int)gridDim.x) {  // (uniform; grid == tile count here, so the successor has a tile)
-        const TileId s = tile_of_block<BM, false>(nb, gridDim.x, M, N, K, 0, 0);
-        const long long pa = (long long)min(s.tm * BM, M - BM) * lda, pb = (long long)min(s.tn * BN, N - BN) * ldb;
-        // bytes from the panel's first element to the operand's last (this batch entry)
-        const long long ea = (((long long)(M - 1) * lda + K) - pa) * 2, eb = (((long long)(N - 1) * ldb + K) - pb) * 2;
-        __amdgpu_buffer_rsrc_t sra = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(A_in + bz * sa + pa), (short)0, (int)min(ea, (long long)kNumRecords), kRsrcWord3);
-        __amdgpu_buffer_rsrc_t srb = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(B_in + bz * sb + pb), (short)0, (int)min(eb, (long long)kNumRecords), kRsrcWord3);
-        const int klast = (koff + kBK - 2) * 2;  // byte offset of K-tile 0's last dword in a row (>= 0: K % 8 == 0)
-        const int va = (int)(tid * lda * 2) + klast, vb = (int)(tid * ldb * 2) + klast;
-        pf[0] = __builtin_amdgcn_raw_buffer_load_b32(sra, va, 0, 0);
-        pf[1] = __builtin_amdgcn_raw_buffer_load_b32(srb, vb, 0, 0);
-        if (nk > 1) {  // (a one-tile K has no second K-tile: nothing past the row's end is touched)
-          pf[2] = __builtin_amdgcn_raw_buffer_load_b32(sra, va + kBK * 2, 0, 0);
-          pf[3] = __builtin_amdgcn_raw_buffer_load_b32(srb, vb + kBK * 2, 0, 0);
-        }
-        KFW4_FENCE();  // the loads issue here: nothing sinks them towards keep_prefetch
-      }
-    }
-  };
-  auto keep_prefetch = [&]() __attribute__((always_inline)) {
-    if constexpr (kPrefetch) asm volatile("" ::"v"(pf[0]), "v"(pf[1]), "v"(pf[2]), "v"(pf[3]));
-  };
 
   // Epilogue. Lane (lr, lh) holds row lr, columns 4lh..4lh+3 of every 16x16 block n. For each pair
   // of blocks (n, n+1) one v_permlane16_swap per dword trades rows 1<->0 and 3<->2 of the lane
@@ -845,9 +743,6 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
 #pragma unroll
     for (int n = 0; n < NR; ++n) bpre[n] = *reinterpret_cast<const bf16x4*>(bias + n0 + wn * WT + n * 16 + elh * 4);
   }
-  // behind the bias loads in the in-order load counter (their wait does not cover these), ahead of
-  // every store; a residual's rows are loaded span by span later, so the first of their waits does
-  prefetch_next();
   // VEC (compile time): bias / residual as 8-B vector loads (the fast path) or element loads
   // UNIT (compile time): alpha == 1, the scale is skipped (128 v_pk_mul_f32 per wave)
   auto finish = [&](auto VEC, auto UNIT, int i, int n, int m, uint2& pre_out) -> uint2 {
@@ -864,7 +759,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     }
     if constexpr (SK) {
       // stream-K owner: add the producers' fp32 partials (same fragment layout as acc)
-      for (unsigned long long mk = (KFW4_SK_AB & 1) ? 0ull : sk_mask; mk; mk &= mk - 1) {
+      for (unsigned long long mk = sk_mask; mk; mk &= mk - 1) {
         const int slot = sk_base + __builtin_ctzll(mk) * sk_stride;
         // agent-coherent (sc1) loads: a producer on another XCD wrote them through its L2
         unsigned long long* pp = reinterpret_cast<unsigned long long*>(
@@ -897,7 +792,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       for (int r = 0; r < 4; ++r) p[r] = (__bf16)v[r];
       pre_out = __builtin_bit_cast(uint2, p);
     }
-    if constexpr (KFW4_ACT_PK && (ACT == KFAMD_ACT_GELU_TANH || ACT == KFAMD_ACT_SILU)) {
+    if constexpr (ACT == KFAMD_ACT_GELU_TANH || ACT == KFAMD_ACT_SILU) {
       const kf32x2 lo = act2<ACT>(kf32x2{v[0], v[1]}), hi = act2<ACT>(kf32x2{v[2], v[3]});
       v[0] = lo.x;
       v[1] = lo.y;
@@ -928,15 +823,12 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   if constexpr (SPLIT == 1) {
     // raw fp32 partials, 4 consecutive columns per lane per block: W[z][m][n], ld N
     float* Wz = W + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * (long long)M * N;
-#ifndef KFW4_FULLLINE
-#define KFW4_FULLLINE 1
-#endif
-    if (KFW4_FULLLINE && m0 == m_lo && n0 == n_lo) {
+    if (m0 == m_lo && n0 == n_lo) {
       // interior tile: whole 128-B lines per store, as the bf16 epilogue below. A block pair (n, n+1)
       // is 16 rows x 32 fp32; lane (lh, lr) holds row lr, 16 B at slot (n & 1) * 4 + lh; staged in the
       // wave's 2 KiB of the idle ring (slot c of row r at r * 128 + 16 * (c ^ ((r >> 1) & 7))) and read
       // back by rows (8 lanes per row)
-      char* stage = smem + kEpiBase + wid * 2048;
+      char* stage = smem + wid * 2048;
       const int wsw = (elr >> 1) & 7;
       const int w0 = elr * 128 + 16 * (elh ^ wsw), w1 = elr * 128 + 16 * ((4 + elh) ^ wsw);
       const int rr = elane >> 3, rc = elane & 7;
@@ -1027,23 +919,16 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   // (no wave reads the ring after the last tile's mid barrier) and reads back row-major. Row r's 16-B
   // slot c sits at r * 128 + 16 * (c ^ ((r >> 1) & 7)): the writes (16 rows, one slot each per 16
   // lanes) and the reads (two rows of 8 slots per 16 lanes) both cover 16 distinct bank quads.
-  // KFW4_STORE_NT: these C stores, whole lines nobody reads again in this GEMM, with the non-temporal
-  // policy (global_store_dwordx4 ... nt), so the 128 KiB a block writes (4 MiB, a whole L2, per XCD and
+  // These C stores, whole lines nobody reads again in this GEMM, go out with the non-temporal policy
+  // (global_store_dwordx4 ... nt), so the 128 KiB a block writes (4 MiB, a whole L2, per XCD and
   // tile wave) stop displacing the A / B panels its neighbours re-read: 8192^3 +1.9 % against plain
-  // stores in interleaved rounds (profiles/w4_prefetch; tools/w4_ab.py `r4` = plain, `storent`)
-#ifndef KFW4_STORE_NT
-#define KFW4_STORE_NT 1
-#endif
+  // stores in interleaved rounds (profiles/w4_prefetch)
   auto store_line = [&](__bf16* p, uint4 v) __attribute__((always_inline)) {
-    if constexpr (KFW4_STORE_NT) {
-      __builtin_nontemporal_store(i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w}, reinterpret_cast<i32x4*>(p));
-    } else {
-      *reinterpret_cast<uint4*>(p) = v;
-    }
+    __builtin_nontemporal_store(i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w}, reinterpret_cast<i32x4*>(p));
   };
   auto emit_fullline = [&](auto UNIT) {
     static_assert(NR % 4 == 0, "full-line stores: two block pairs per span");
-    char* stage = smem + kEpiBase + wid * 2048;
+    char* stage = smem + wid * 2048;
     // write side: this lane's row lr, slots ch(lh) (pair n) and 4 + ch(lh) (pair n+2); ch = 2*(lh&1) + (lh>>1)
     const int ch = 2 * (elh & 1) + (elh >> 1);
     const int wsw = (elr >> 1) & 7;
@@ -1121,7 +1006,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   };
   auto emit_fullline_res = [&](auto UNIT) {
     static_assert(NR % 4 == 0, "full-line stores: four blocks per span");
-    char* stage = smem + kEpiBase + wid * 4096;
+    char* stage = smem + wid * 4096;
     const int rr = elane >> 3, rc = elane & 7;
     const int ra0 = rr * 256 + 16 * ((2 * rc) ^ rr), ra1 = rr * 256 + 16 * ((2 * rc + 1) ^ rr);
     const int rb0 = (rr + 8) * 256 + 16 * ((2 * rc) ^ (rr + 8)), rb1 = (rr + 8) * 256 + 16 * ((2 * rc + 1) ^ (rr + 8));
@@ -1132,12 +1017,9 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
 #pragma unroll
       for (int e = 0; e < 8; ++e) csum[h][e] = 0.f;
     // R (residual / pre-activation) rows of span sp = (fragment row i, 64-column half n / 4), issued
-    // KFW4_RES_PD spans ahead of their use: one span's loads per use left the HBM latency exposed
-    // once per span, 16 times per wave and tile (profiles/r5zg_dact2)
-#ifndef KFW4_RES_PD
-#define KFW4_RES_PD 2
-#endif
-    constexpr int SPW = NR / 4, NS = NR * SPW, PD = KFW4_RES_PD;
+    // PD spans ahead of their use: one span's loads per use left the HBM latency exposed once per
+    // span, 16 times per wave and tile (profiles/r5zg_dact2)
+    constexpr int SPW = NR / 4, NS = NR * SPW, PD = 2;
     bf16x8 rbuf[PD + 1][2];
     auto rload = [&](int sp) __attribute__((always_inline)) {
       const int i = sp / SPW, n = (sp % SPW) * 4;
@@ -1226,9 +1108,6 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   };
   // the residual as 16-B rows (its own alignment; vec_in only asks for 8 B)
   const bool res16 = HAS_RES && !(reinterpret_cast<uintptr_t>(HAS_RES ? R : nullptr) & 15) && !((ldr | sr) & 7);
-#ifndef KFW4_FULLLINE
-#define KFW4_FULLLINE 1
-#endif
   // uniform branches: interior tiles store unmasked straight-line 16-B stores, shifted edge tiles
   // mask per lane, an odd output takes the og path; only the path that runs is fetched
   if constexpr (DACT) {  // interior tiles only (host contract): one path
@@ -1236,19 +1115,16 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     else emit_fullline_res(F{});
   } else if (og == 8 && vec_in) {
     if (m0 == m_lo && n0 == n_lo) {
-      if constexpr (KFW4_FULLLINE && HAS_RES && !HAS_AUX && !SK) {  // (the stream-K owner adds partials in finish())
+      if constexpr (HAS_RES && !HAS_AUX && !SK) {  // (the stream-K owner adds partials in finish())
         if (res16) {
           if (alpha == 1.f) emit_fullline_res(T{});
           else emit_fullline_res(F{});
         } else {
           emit(T{}, store_all, F{});
         }
-      } else if constexpr (KFW4_FULLLINE) {
+      } else {
         if (alpha == 1.f) emit_fullline(T{});
         else emit_fullline(F{});
-      } else {
-        if (alpha == 1.f) emit(T{}, store_all, T{});
-        else emit(T{}, store_all, F{});
       }
     } else {
       emit(T{}, store16, F{});
@@ -1256,7 +1132,6 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
   } else {
     emit(F{}, store_og, F{});
   }
-  keep_prefetch();
   };  // epilogue
 
   if constexpr (SK) {
@@ -1277,6 +1152,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       const __bf16* b = B_in + (LB == 0 ? (long long)n0 * ldb + kofs : (long long)n0 + kofs * ldb);
       ra = __builtin_amdgcn_make_buffer_rsrc((void*)a, (short)0, nrec, kRsrcWord3);
       rb = __builtin_amdgcn_make_buffer_rsrc((void*)b, (short)0, nrec, kRsrcWord3);
+      // never taken under SK; kept: without it set_k captures less and the stream-K kernels' SGPR allocation moves
       if (kAsmDma) {
         dra = make_desc(a);
         drb = make_desc(b);
@@ -1377,7 +1253,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
       }
       zero_acc_if(zero);
       __syncthreads();  // the previous item's fragment reads are done before the ring refills
-      run_k(std::false_type{});
+      run_k();
       if (role == 1) {
 #pragma unroll
         for (int i = 0; i < NR; ++i)
@@ -1388,12 +1264,10 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
             for (int r = 0; r < 4; ++r) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v[r]) : "a"(acc[i][n][r]));
             typedef float f32x2 __attribute__((ext_vector_type(2)));
             unsigned long long* pp = reinterpret_cast<unsigned long long*>(partial_at(cur_u, i, n));
-            if (!(KFW4_SK_AB & 1)) {
-              __hip_atomic_store(pp, __builtin_bit_cast(unsigned long long, (f32x2{v[0], v[1]})), __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-              __hip_atomic_store(pp + 1, __builtin_bit_cast(unsigned long long, (f32x2{v[2], v[3]})), __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-            }
+            __hip_atomic_store(pp, __builtin_bit_cast(unsigned long long, (f32x2{v[0], v[1]})), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(pp + 1, __builtin_bit_cast(unsigned long long, (f32x2{v[2], v[3]})), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
           }
         // The partials and flags move as agent-scope relaxed atomics (sc1: written through / read past
         // the XCD's L2), so no agent-scope fence is needed: a release / acquire fence writes back /
@@ -1413,8 +1287,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
             int ok = 0;
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             while (true) {
-              if ((KFW4_SK_AB & 2) ||
-                  __hip_atomic_load(sk_flags + ob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sk_epoch) {
+              if (__hip_atomic_load(sk_flags + ob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sk_epoch) {
                 ok = 1;
                 break;
               }
@@ -1439,78 +1312,10 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     }
     return;
   }
-  if constexpr (PO) {
-    // ---- persistent, overlapped (batch 1, whole K): block b runs tiles b, b + G, b + 2G, ... of the
-    // XCD-remapped order (G % 8 == 0 keeps every tile of a block on its XCD's contiguous chunk). The
-    // next tile's first two K tiles are DMA'd before this tile's epilogue, so their latency and the
-    // ring refill hide under its stores; no block boundary between tiles.
-    const int G = gridDim.x;
-    auto set_tile = [&](int w) __attribute__((always_inline)) {
-      int tm_, tn_;
-      raster_tile(w, tiles_m, tiles_n, tm_, tn_);
-      m_lo = tm_ * BM;
-      n_lo = tn_ * BN;
-      m0 = min(m_lo, M - BM);
-      n0 = min(n_lo, N - BN);
-    };
-    auto set_operands = [&]() __attribute__((always_inline)) {
-      const __bf16* a = A_in + (LA == 0 ? (long long)m0 * lda + ka : (long long)m0 + ka * lda);
-      const __bf16* b = B_in + (LB == 0 ? (long long)n0 * ldb + ka : (long long)n0 + ka * ldb);
-      ra = __builtin_amdgcn_make_buffer_rsrc((void*)a, (short)0, nrec, kRsrcWord3);
-      rb = __builtin_amdgcn_make_buffer_rsrc((void*)b, (short)0, nrec, kRsrcWord3);
-      if (kAsmDma) {
-        dra = make_desc(a);
-        drb = make_desc(b);
-      }
-    };
-    static_assert(NR % 4 == 0, "zero_acc: 4 accumulators per asm");
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-      // an MFMA of zero fragments with C = 0 writes each AGPR (one unconditional def per tile, so the
-      // loop-carried accumulators stay in AGPRs); the asm pads the VALU -> MFMA operand hazard of the
-      // zero fragment's v_mov (invisible to the hazard recognizer) and its own write latency
-      const bf16x8 z = {};
-#pragma unroll
-      for (int i = 0; i < NR; ++i)
-#pragma unroll
-        for (int n = 0; n < NR; n += 4)
-          asm volatile(
-              "s_nop 4\n\tv_mfma_f32_16x16x32_bf16 %0, %4, %4, 0\n\tv_mfma_f32_16x16x32_bf16 %1, %4, %4, 0\n\t"
-              "v_mfma_f32_16x16x32_bf16 %2, %4, %4, 0\n\tv_mfma_f32_16x16x32_bf16 %3, %4, %4, 0\n\t"
-              "s_nop 7\n\ts_nop 7\n\ts_nop 7"
-              : "=a"(acc[i][n]), "=a"(acc[i][n + 1]), "=a"(acc[i][n + 2]), "=a"(acc[i][n + 3])
-              : "v"(z));
-    };
-    int j = blockIdx.x;  // the kernel prologue set this block's first tile (wg = xcd_remap(j, nwg))
-    issue_prologue();
-    while (true) {
-      run_k(std::true_type{});
-      const int jn = j + G;
-      const bool more = jn < nwg;
-      const int cm0 = m0, cn0 = n0, cmlo = m_lo, cnlo = n_lo;
-      int nm0 = 0, nn0 = 0, nmlo = 0, nnlo = 0;
-      if (more) {
-        set_tile(xcd_remap(jn, nwg));
-        set_operands();
-        nm0 = m0, nn0 = n0, nmlo = m_lo, nnlo = n_lo;
-        m0 = cm0, n0 = cn0, m_lo = cmlo, n_lo = cnlo;
-        __syncthreads();  // every wave's last fragment reads of this tile are done before the ring refills
-        issue_prologue();
-      }
-      epilogue();
-      if (!more) break;
-      m0 = nm0, n0 = nn0, m_lo = nmlo, n_lo = nnlo;
-      j = jn;
-      zero_acc();
-    }
-    return;
-  }
-  run_k(std::false_type{});
+  run_k();
   if constexpr (SPLIT == 2) {
     // ---- split-K fixup: publish this split's partial, the last split to arrive finishes the tile ----
-#ifndef KFW4_FIX_AB
-#define KFW4_FIX_AB 0  // timing ablations (tools/fix_ab.py builds): 1 no partial stores, 2 no partial reads, 4 no sc1
-#endif
-    constexpr int kFixPol = (KFW4_FIX_AB & 4) ? 0 : 16;  // sc1
+    constexpr int kFixPol = 16;  // sc1: the partials' stores and loads go through to the agent's coherence point
     const int el = lane_id_fresh();
     const long long tile_id = (long long)blockIdx.y * nwg_all + grp_base + wg;
     constexpr long long kPerTile = (long long)BM * BN;  // floats
@@ -1531,7 +1336,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
             v[r] = __builtin_bit_cast(int, a);
           }
           // sc1: written through to the agent's coherence point, visible to a reader on another XCD
-          if (!(KFW4_FIX_AB & 1)) __builtin_amdgcn_raw_buffer_store_b128(v, rw, lane_off, (i * NR + n) * 1024, kFixPol);
+          __builtin_amdgcn_raw_buffer_store_b128(v, rw, lane_off, (i * NR + n) * 1024, kFixPol);
         }
     }
     // this block's partial is complete at agent scope before it counts itself in
@@ -1548,7 +1353,7 @@ void gemm_w4(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16*
     // one split at a time, two fragment rows of loads in flight (row i + 1 is requested before row i
     // is added); the scheduling barriers keep the compiler from hoisting every row's loads at once,
     // which spilled them to scratch behind vmcnt(0) waits
-    for (int z = 0; z < ((KFW4_FIX_AB & 2) ? 0 : (int)gridDim.z); ++z) {
+    for (int z = 0; z < (int)gridDim.z; ++z) {
       if (z == (int)blockIdx.z) continue;
       __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(W + (long long)z * zstride + tile_id * kPerTile), (short)0, kNumRecords, kRsrcWord3);

@@ -6,12 +6,10 @@
 
 using namespace kfw4;
 
-// KFW4_DACT_BM: the tile. 128 runs two workgroups per CU, so one workgroup's epilogue (the
-// pre-activation reads and the G stores) overlaps the other's K loop (A/B runs, profiles/r5ze_mlp)
-#ifndef KFW4_DACT_BM
-#define KFW4_DACT_BM 256
-#endif
-constexpr int kDactBM = KFW4_DACT_BM;
+// The tile. 128 would run two workgroups per CU, so that one workgroup's epilogue (the pre-activation
+// reads and the G stores) overlaps the other's K loop; measured against 256 and not adopted
+// (profiles/r5ze_mlp)
+constexpr int kDactBM = 256;
 
 extern "C" long long kfamd_w4_dgrad_act_workspace(int M, int N) {
   return (long long)((M + kDactBM / 2 - 1) / (kDactBM / 2)) * N * (long long)sizeof(float);
@@ -34,7 +32,7 @@ extern "C" int kfamd_w4_dgrad_act(const void* dy, const void* w, void* g, const 
   __bf16* c = static_cast<__bf16*>(g);
   float* W = db ? ws : nullptr;
 #define DACT_GO(ACTV)                                                                                             \
-  hipLaunchKernelGGL((gemm_w4<ACTV, false, true, false, 0, 1, kDactBM, 0, false, 0, false, false, true>), grid, block, 0, \
+  hipLaunchKernelGGL((gemm_w4<ACTV, false, true, false, 0, 1, kDactBM, 0, false, 0, false, true>), grid, block, 0, \
                      s, a, b, c, nullptr, r, nullptr, M, N, K, lda, ldb, ldg, ldz, 0LL, 0LL, 0LL, 0LL, 1.0f, nullptr, W)
   switch (act) {
     case KFAMD_ACT_GELU_TANH: DACT_GO(KFAMD_ACT_GELU_TANH); break;

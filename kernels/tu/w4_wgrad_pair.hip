@@ -40,12 +40,12 @@ extern "C" int kfamd_w4_wgrad_pair_v2(const void* A1, const void* B1, void* C1, 
   if (splits > 1) {
     if (!W || !cnt || splits > 64 || kper < kBK || kper % kBK || (long long)kper * (splits - 1) >= K) return KFAMD_EINVAL;
     if ((reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(cnt) & 3)) return KFAMD_EALIGN;
-    hipLaunchKernelGGL((gemm_w4<KFAMD_ACT_NONE, false, false, false, 1, 1, 256, 2, false, 0, false, false, false, true>),
+    hipLaunchKernelGGL((gemm_w4<KFAMD_ACT_NONE, false, false, false, 1, 1, 256, 2, false, 0, false, false, true>),
                        dim3((unsigned)(t1 + t2), 1, splits), dim3(kThreads), 0, s, static_cast<const __bf16*>(A1),
                        static_cast<const __bf16*>(B1), static_cast<__bf16*>(C1), nullptr, nullptr, nullptr, M1, N, K,
                        lda1, ldb1, ldc1, 0LL, 0LL, 0LL, 0LL, 0LL, 1.0f, nullptr, W, kper, cnt, 0u, g2);
   } else {
-    hipLaunchKernelGGL((gemm_w4<KFAMD_ACT_NONE, false, false, false, 1, 1, 256, 0, false, 0, false, false, false, true>),
+    hipLaunchKernelGGL((gemm_w4<KFAMD_ACT_NONE, false, false, false, 1, 1, 256, 0, false, 0, false, false, true>),
                        dim3((unsigned)(t1 + t2)), dim3(kThreads), 0, s, static_cast<const __bf16*>(A1),
                        static_cast<const __bf16*>(B1), static_cast<__bf16*>(C1), nullptr, nullptr, nullptr, M1, N, K,
                        lda1, ldb1, ldc1, 0LL, 0LL, 0LL, 0LL, 0LL, 1.0f, nullptr, nullptr, 0, nullptr, 0u, g2);

@@ -174,7 +174,7 @@ def check_kernel_library(lib: Path) -> None:
     if missing:
         raise RuntimeError(f"{lib}: no gfx950 kernel descriptors for {missing} ({len(names)} kernels found)")
     # the other face of the dropped-stub bug: a host pass that lost a kernel's launch stub leaves an
-    # undefined __device_stub__ reference, and the library fails to load (gemm_w4.h FASTK notes)
+    # undefined __device_stub__ reference, and the library fails to load (gemm_w4.h, the notes at dma_a and kAsmDma)
     nm = subprocess.run(["nm", "-D", "--undefined-only", str(lib)], capture_output=True, text=True)
     stubs = [ln.split()[-1] for ln in nm.stdout.splitlines() if "__device_stub__" in ln]
     if stubs:

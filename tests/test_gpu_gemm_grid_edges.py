@@ -1,10 +1,10 @@
-"""The w4 GEMM's successor prefetch (gemm_w4.h KFW4_PREFETCH_NEXT): during its epilogue block b
-touches the first two K-tiles of the tile block b + 256 will compute. The prefetch changes no
-result; what can go wrong is its address computation at the grid's edges, so these are the smallest
-shapes with more than 256 tiles of 256 x 256, against an fp32 reference with test_gpu_kernels.py's
-gemm_nt tolerance. They passed with the prefetch compiled in; production builds it out
-(profiles/w4_prefetch), and the same shapes then cover the non-temporal C stores on interior tiles next
-to the masked stores of the shifted edge tiles."""
+"""The w4 GEMM at the edges of a grid of more than 256 tiles (more tiles than the chip has CUs, so blocks
+follow one another on a CU): interior tiles leave as whole 128-B lines with non-temporal stores
+(gemm_w4.h emit_fullline) right next to the masked stores of the shifted last tile row and column.
+These are the smallest shapes with more than 256 tiles of 256 x 256, against an fp32 reference with
+test_gpu_kernels.py's gemm_nt tolerance. The shapes come from the successor prefetch they were first
+written for (profiles/w4_prefetch; that code is gone): a shifted last tile row and column, a partial
+first K-tile, a single K-tile, and operands that end where their allocations end."""
 import pytest
 import torch
 
@@ -32,11 +32,11 @@ def _assert_close(out, ref, K):
     assert err <= 1e-2 * scale + 1e-2, f"max err {err} vs scale {scale} (K={K})"
 
 
-# 4352 x 4096: 17 x 16 = 272 tiles, successors for blocks 0-15 only
+# 4352 x 4096: 17 x 16 = 272 tiles, 16 more than one wave of 256 CUs
 # 4392 x 4136 x 200: shifted last tile row and column, partial first K-tile (koff = -56)
-# K = 64: one K-tile, the successor's second K-tile does not exist
+# K = 64: one K-tile, no second one for the prologue to stage
 @pytest.mark.parametrize("M,N,K", [(4352, 4096, 192), (4392, 4136, 200), (4352, 4096, 64)])
-def test_prefetch_grid_edges(M, N, K):
+def test_grid_edges(M, N, K):
     from kubeflow_rm_amd.ops import gemm_nt
     a, b = _rand(M, K, seed=41), _rand(N, K, seed=42)
     out = gemm_nt(a, b, variant="w4")
@@ -45,8 +45,8 @@ def test_prefetch_grid_edges(M, N, K):
 
 
 @pytest.mark.parametrize("batch", [1, 2])
-def test_prefetch_with_bias_and_residual(batch):
-    """The bias and residual loads share the load counter with the prefetch."""
+def test_grid_edges_with_bias_and_residual(batch):
+    """The bias and residual loads of the full-line residual epilogue, with and without a batch."""
     from kubeflow_rm_amd.ops import gemm_nt
     M, N, K = 4352, 4096, 64
     lead = (batch,) if batch > 1 else ()
@@ -57,9 +57,9 @@ def test_prefetch_with_bias_and_residual(batch):
     _assert_close(out, _ref_gemm(a, b, bias, r), K)
 
 
-def test_prefetch_operands_at_the_end_of_their_allocation():
-    """A and B end where their allocations end (the prefetch's descriptors stop at the operand's last
-    element), and the elements after `out` keep their pattern."""
+def test_operands_at_the_end_of_their_allocation():
+    """A and B end where their allocations end (no load may reach past an operand's last element),
+    and the elements after `out` keep their pattern."""
     from kubeflow_rm_amd.ops import gemm_nt
     M, N, K = 4392, 4136, 200
     abuf, bbuf = _rand(4096 + M * K, seed=47), _rand(4096 + N * K, seed=48)

@@ -50,7 +50,7 @@ def test_gemm_fast_path(M, N, K, variant):
 
 @pytest.mark.parametrize("M,N,K", [(4096, 4096, 16448), (4096, 8192, 12288)])
 def test_gemm_superblock_raster_past_the_mall(M, N, K):
-    """Operands past 256 MiB take the 16 x 16-tile superblock raster (gemm_w4.h KFW4_SUPER): every
+    """Operands past 256 MiB take the 16 x 16-tile superblock raster (gemm_w4.h tile_of_block): every
     output tile written once, from the right A rows and B columns."""
     from kubeflow_rm_amd.ops import gemm_nt
     assert (M + N) * K * 2 > 256 << 20 and M % 4096 == 0 and N % 4096 == 0

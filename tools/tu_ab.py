@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Build A/B of any kernel translation units: the kernel library re-linked with the named TUs compiled
-under extra flags (-D knobs), one library per variant (kubeflow_rm_amd/lib/tuab/).
+under extra flags (compiler options, -D switches), one library per variant (kubeflow_rm_amd/lib/tuab/).
 
-  python tools/tu_ab.py --name pd0 --tus tu/w4_dgrad_act,tu/w4_nt_none --flags=-DKFW4_RES_PD=0
-  KFAMD_KERNEL_LIB=kubeflow_rm_amd/lib/tuab/libkfamd_kernels_pd0.so python tools/dact_bench.py
+  python tools/tu_ab.py --name o2 --tus tu/w4_dgrad_act,tu/w4_nt_none --flags=-O2
+  KFAMD_KERNEL_LIB=kubeflow_rm_amd/lib/tuab/libkfamd_kernels_o2.so python tools/dact_bench.py
 
 (tools/attn_ab.py is the attention-specific form with named variants.)
 """

@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
-"""A/B of w4 GEMM K-loop schedules (tools/w4_ab.hip built once per knob set) on one GPU.
+"""A/B of the w4 GEMM header (kernels/gemm_w4.h) on one GPU: tools/w4_ab.hip built once per variant.
+`prod` is the working tree's kernels/, `head` the committed kernels/ (git HEAD, extracted into the
+build directory), which is how an experiment on the header is measured against what is committed:
+edit kernels/gemm_w4.h, build both, run. The header has no build knobs; a schedule that is to be
+tried is written into the working tree.
 
-  python tools/w4_ab.py --build            # on the host: compile every variant into kubeflow_rm_amd/lib/w4ab/
-  python tools/w4_ab.py --sizes 4096,8192   # on the GPU: bitwise check vs production, interleaved timing
-                                            # rounds vs the production kernel and torch.matmul, then the
+  python tools/w4_ab.py --build            # on the host: compile both variants into kubeflow_rm_amd/lib/w4ab/
+  python tools/w4_ab.py --sizes 4096,8192   # on the GPU: bitwise check vs the loaded kernel library, interleaved
+                                            # timing rounds vs that library (`ops`) and torch.matmul, then the
                                             # variants' cheap K-loop stamps (cycles per 64-k tile by segment)
 
-Prints one JSON line per measurement. Knobs: kernels/gemm_w4.h (KFW4_RG, KFW4_DMA_EVERY, KFW4_DMA_PHASE,
-KFW4_PIN_MFMA, KFW4_PRIO, and outside the K loop KFW4_PREFETCH_NEXT, KFW4_STORE_NT); every variant also carries KFW4_CHEAP_STAMPS=1, which only touches its diag
-kernel (s_memtime with no wait of its own, read after the loop's own lgkmcnt(0)).
+Prints one JSON line per measurement. Every variant carries KFW4_CHEAP_STAMPS=1, which only touches its
+diag kernel (s_memtime with no wait of its own, read after the loop's own lgkmcnt(0)).
 """
 import argparse
 import ctypes
+import io
 import json
 import statistics
 import subprocess
 import sys
+import tarfile
 import time
 from pathlib import Path
 
@@ -23,37 +28,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 OUT = ROOT / "kubeflow_rm_amd" / "lib" / "w4ab"
 
-VARIANTS = {
-    "base": ["-DKFW4_FASTK=0", "-DKFW4_UNROLL5=0", "-DKFW4_ASM_DMA=0", "-DKFW4_PREBAR=0"],  # the round-3 K loop
-    "unroll5": ["-DKFW4_FASTK=0", "-DKFW4_UNROLL5=1"],
-    "f2u5": ["-DKFW4_FASTK=2", "-DKFW4_UNROLL5=1", "-DKFW4_ASM_DMA=0", "-DKFW4_PREBAR=0"],
-    "r4": ["-DKFW4_PREFETCH_NEXT=0", "-DKFW4_STORE_NT=0"],  # production before the non-temporal C stores
-    "prefetch": ["-DKFW4_PREFETCH_NEXT=1", "-DKFW4_STORE_NT=0"],  # successor tile's first K-tiles into L2
-    "storent": ["-DKFW4_PREFETCH_NEXT=0", "-DKFW4_STORE_NT=1"],  # non-temporal full-line C stores (production)
-    "prefetch_storent": ["-DKFW4_PREFETCH_NEXT=1", "-DKFW4_STORE_NT=1"],
-    "noful": ["-DKFW4_FULLLINE=0"],  # the half-line epilogue stores
-    "asmdma": ["-DKFW4_ASM_DMA=1"],
-    "prebar1": ["-DKFW4_PREBAR=1"],
-    "prebar2": ["-DKFW4_PREBAR=2"],
-    "asm_prebar1": ["-DKFW4_ASM_DMA=1", "-DKFW4_PREBAR=1"],
-    "prev": ["-DKFW4_FASTK=2", "-DKFW4_UNROLL5=1"],
-    "f2u5_rg4p0": ["-DKFW4_FASTK=2", "-DKFW4_UNROLL5=1", "-DKFW4_RG=4", "-DKFW4_DMA_PHASE=0"],
-    "f2u5_e4p0": ["-DKFW4_FASTK=2", "-DKFW4_UNROLL5=1", "-DKFW4_DMA_EVERY=4", "-DKFW4_DMA_PHASE=0"],
-    "u5_rg4p0": ["-DKFW4_FASTK=0", "-DKFW4_UNROLL5=1", "-DKFW4_RG=4", "-DKFW4_DMA_PHASE=0"],
-    "rg4": ["-DKFW4_RG=4"],
-    "dma_cluster": ["-DKFW4_DMA_EVERY=2", "-DKFW4_DMA_PHASE=1"],
-    "dma_spread6": ["-DKFW4_DMA_EVERY=6", "-DKFW4_DMA_PHASE=1"],
-    "nopin": ["-DKFW4_PIN_MFMA=0"],
-    "noprio": ["-DKFW4_PRIO=0"],
-    "gm2": ["-DKFW4_GROUP_M=2"],
-    "gm8": ["-DKFW4_GROUP_M=8"],
-    "gm16": ["-DKFW4_GROUP_M=16"],
-    "phase3": ["-DKFW4_DMA_PHASE=3"],
-    "gm32": ["-DKFW4_GROUP_M=32"],
-    "rg4gm16": ["-DKFW4_RG=4", "-DKFW4_GROUP_M=16"],
-    "nosuper": ["-DKFW4_SUPER=0"],  # the per-XCD row groups at every size (before r6zm_super)
-    "rg4super": ["-DKFW4_RG=4"],
-}
+VARIANTS = {"prod": None, "head": "HEAD"}  # name -> git revision of kernels/ (None: the working tree)
 
 
 def build(names):
@@ -62,8 +37,14 @@ def build(names):
 
     def one(name):
         so = OUT / f"libw4ab_{name}.so"
+        kernels = ROOT / "kernels"
+        if VARIANTS[name]:  # the committed kernels/ of that revision, extracted beside the libraries
+            tar = subprocess.run(["git", "-C", str(ROOT), "archive", VARIANTS[name], "kernels"],
+                                 capture_output=True, check=True).stdout
+            tarfile.open(fileobj=io.BytesIO(tar)).extractall(OUT / name)
+            kernels = OUT / name / "kernels"
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-               "-mcode-object-version=5", f"-I{ROOT / 'kernels'}", "-DKFW4_CHEAP_STAMPS=1", *VARIANTS[name],
+               "-mcode-object-version=5", f"-I{kernels}", "-DKFW4_CHEAP_STAMPS=1",
                str(ROOT / "tools" / "w4_ab.hip"), "-o", str(so)]
         p = subprocess.run(cmd, capture_output=True, text=True)
         if p.returncode:
@@ -84,8 +65,6 @@ def main():
     ap.add_argument("--sizes", default="4096,8192,16384")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--diag", default="8192")
-    ap.add_argument("--po-grid", type=int, default=256, help="blocks of the persistent-overlapped (PO) launch")
-    ap.add_argument("--no-po", action="store_true", help="skip the persistent-overlapped launches")
     ap.add_argument("--launches", type=int, default=0,
                     help="profiling mode (under rocprofv3): only launch each variant N times at the first size, "
                          "in --variants order (the kernel name is the same in every library)")
@@ -104,8 +83,6 @@ def main():
         L.w4ab_nt.argtypes = [vp, vp, vp, i, i, i, vp]
         L.w4ab_diag.restype = i
         L.w4ab_diag.argtypes = [vp, vp, vp, i, i, i, vp, vp]
-        L.w4ab_po.restype = i
-        L.w4ab_po.argtypes = [vp, vp, vp, i, i, i, i, vp]
         libs[n] = L
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -129,25 +106,18 @@ def main():
             assert L.w4ab_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, st) == 0
             torch.cuda.synchronize()
             same[n] = bool(torch.equal(C, ref))
-            if a.no_po:
-                continue
-            C.zero_()
-            assert L.w4ab_po(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, a.po_grid, st) == 0
-            torch.cuda.synchronize()
-            same[n + "_po"] = bool(torch.equal(C, ref))
         flop = 2.0 * M * N * K
         iters = max(5, int(3e13 / flop))
-        fns = {"prod": lambda: ops.gemm_nt(A, B, out=C), "torch": lambda: torch.matmul(A, B.t())}
+        # `ops`: the kernel library the package loaded (KFAMD_KERNEL_LIB or the in-tree build)
+        fns = {"ops": lambda: ops.gemm_nt(A, B, out=C), "torch": lambda: torch.matmul(A, B.t())}
         for n, L in libs.items():
             fns[n] = (lambda L=L: L.w4ab_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, st))
-            if not a.no_po:
-                fns[n + "_po"] = (lambda L=L: L.w4ab_po(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, a.po_grid, st))
         for fn in fns.values():  # first calls (hipBLASLt picks its algorithm) stay out of the rounds
             fn()
         torch.cuda.synchronize()
         t_end = time.perf_counter() + 1.0  # settle: 1 s of back-to-back GEMMs before round 1
         while time.perf_counter() < t_end:
-            fns["prod"]()
+            fns["ops"]()
         tf = {k: [] for k in fns}
         for _ in range(a.rounds):
             for k, fn in fns.items():
@@ -157,7 +127,7 @@ def main():
                     fn()
                 torch.cuda.synchronize()
                 tf[k].append(flop * iters / (time.perf_counter() - t0) / 1e12)
-        print(json.dumps({"size": s, "bitwise_equal_to_prod": same,
+        print(json.dumps({"size": s, "bitwise_equal_to_ops": same,
                           "median_tf": {k: round(statistics.median(v), 1) for k, v in tf.items()},
                           "best_tf": {k: round(max(v), 1) for k, v in tf.items()},
                           # (max - min) / median of each build's own rounds: what a difference has to beat
