@@ -74,6 +74,21 @@
 // here still serve every T * G <= 16. Decode time against G as routed: profiles/gqa/README.md — it does
 // not follow the K / V bytes: G = 2 is 1.2 - 1.6x and G = 4 1.1 - 2.1x faster than G = 1 on this form.
 //
+// Sliding window (the rule: the docstring of ops/decode.py): a row whose causal limit is L (nk[r] below) sees key j
+// iff max(0, L - W) <= j < L, W >= 1 a host integer, the same for every row of a call. WIN = true instantiations of
+// attn_decode_split and attn_extend_split (plain and GQ), behind the kfamd_attn_*_win_* entry points; the WIN = false
+// ones are the kernels as they were (same code, same registers: the table below). The lower bound is computed next
+// to the limit from the device-side lens, and a key below it is excluded exactly as a key at or beyond the limit is,
+// by the branch on the key index: the cache outside every row's window may hold NaN or 0x7F codes and NaN scales,
+// and addresses stay clamped to a valid key. The grid still comes from t_bound (lens stays on the device, the launch
+// stays capturable); a workgroup whose whole split lies below the lowest lower bound of its rows (the launch's first
+// row's: the limits are non-decreasing) writes the empty record and returns before any K / V load — the merges skip
+// that record by select, and with one split the case cannot arise (the lower bound lies below lens) — and the first
+// live split starts its walk at the block step that holds the lower bound, loads ahead of arithmetic as before.
+// W >= t_bound can remove no key: the launcher then runs the WIN = false kernels. Every WIN = true instantiation uses
+// the VGPRs of its WIN = false twin in the table below (66 / 84 decode; 64 / 92 / 129 / 201 and 84 / 112 / 149 / 197
+// extend, GQ alike), scratch 0. Measured: profiles/window.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): VGPRs, the same
 // at D = 64 and at D = 128 unless two are given; scratch is 0 for every instantiation. "before": the four
 // kernels this file replaced, D = 64 / 128.
@@ -131,6 +146,7 @@ struct AttnArgs {
   float scale_log2;
   int lg;  // GQ kernels only: log2 of the group size G. H is then Hkv and Tq the T * G flattened rows
   long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
+  int window;  // WIN kernels only: the sliding window W >= 1 (the rule: the header)
 };
 
 // The single-row kernel's arguments: AttnArgs without Tq, row0 and the t strides.
@@ -148,12 +164,13 @@ struct DecodeArgs {
   const float* ks;  // Fmt::kScaled only, as ksb .. vsh
   const float* vs;
   long long ksb, ksh, vsb, vsh;
+  int window;  // WIN kernel only
 };
 
 // One query row per (b, h). workspace: [B][H][nsplit][2] (m, l) then [B][H][nsplit][D] (o), fp32: the
 // extend kernel's at Tq = 1. What the extend body's comments say about key validity, clamped addresses,
-// the block-uniform early return and whole block steps holds here word for word.
-template <class Fmt, int D>
+// the block-uniform early return, whole block steps and the window's lower bound holds here word for word.
+template <class Fmt, int D, bool WIN>
 __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
@@ -173,11 +190,13 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
   len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
   const int k0 = split * kSplitKeys;
   const int k1 = min(k0 + kSplitKeys, len);  // valid keys of this split: [k0, k1)
+  int lo = 0;  // WIN: the row sees keys [lo, len)
+  if constexpr (WIN) lo = max(len - a.window, 0);
   const long long bh = ((long long)b * a.H + h);
   float* ws_ml = a.ws + (bh * a.nsplit + split) * 2;
   float* ws_o = a.ws + (long long)a.B * a.H * a.nsplit * 2 + (bh * a.nsplit + split) * D;
 
-  if (k1 <= k0) {  // empty split (only reachable with nsplit > 1 or len == 0)
+  if (k1 <= k0 || (WIN && lo >= k1)) {  // empty split (only reachable with nsplit > 1 or len == 0), or one below the window
     if (a.nsplit > 1) {
       if (tid == 0) {
         ws_ml[0] = -INFINITY;
@@ -220,9 +239,11 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
       vsn[u] = vsbase[key];
     }
   };
+  int kbeg = k0;  // WIN: the block step that holds the first key of the window
+  if constexpr (WIN) kbeg = k0 + max(lo - k0, 0) / KSTEP * KSTEP;
 #pragma unroll
-  for (int u = 0; u < kUnroll; ++u) load_ahead(u, k0 + u * NG + grp);
-  for (int kk = k0; kk < k1; kk += KSTEP) {
+  for (int u = 0; u < kUnroll; ++u) load_ahead(u, kbeg + u * NG + grp);
+  for (int kk = kbeg; kk < k1; kk += KSTEP) {
     Vec kc[kUnroll], vc[kUnroll];
     float ksc[kUnroll], vsc[kUnroll];
 #pragma unroll
@@ -248,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
       for (int i = 0; i < 8; ++i) part = fmaf(qf[i], kf[i], part);
       float s = kfw::group_sum<G>(part);
       if constexpr (Fmt::kScaled) s *= ksc[u];
-      if (key < k1) {
+      if (key < k1 && (!WIN || key >= lo)) {
         float vf[8];
         Fmt::unpack8(vc[u], vf);
         const float mn = fmaxf(m, s);
@@ -307,7 +328,11 @@ struct RowMap {
 };
 
 // workspace: [B][H][Tq][nsplit][2] (m, l) then [B][H][Tq][nsplit][D] (o), fp32
-template <class Fmt, int D, int R, bool GQ>
+// WIN: row slot r sees keys [lo[r], nk[r]) only, lo = max(0, nk - window); a key below lo is excluded as one at or
+// beyond nk is, by the branch on the key index. The limits are non-decreasing in r, so the launch's first row has
+// its lowest lower bound: a split that ends at or below it holds no key for any row, and inside the first live split
+// the walk starts at the block step that holds it.
+template <class Fmt, int D, int R, bool GQ, bool WIN>
 __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
@@ -334,8 +359,10 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   const int k1 = min(k0 + kSplitKeys, len);  // keys of this split that the last row may see: [k0, k1)
   const long long bh = (long long)b * a.H + h;
   const long long nrows = (long long)a.B * a.H * Tq;
+  int blo = 0;  // WIN: the lowest lower bound of the launch's rows, its first row's
+  if constexpr (WIN) blo = max(len - rm.T + rm.tok(row0) + 1 - a.window, 0);
 
-  if (k1 <= k0) {  // empty split for every row (block-uniform, before any barrier)
+  if (k1 <= k0 || (WIN && blo >= k1)) {  // empty split for every row (block-uniform, before any barrier)
     for (int r = row0; r < min(row0 + R, Tq); ++r) {
       const long long row = bh * Tq + r;
       if (a.nsplit > 1) {
@@ -355,6 +382,7 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   // row slot r sees keys [0, nk[r]); a padding slot (r >= Tq) and a row before the sequence's start see none
   float qf[R][8];
   int nk[R];
+  int lo[R];  // WIN only
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int gr = row0 + r;               // the slot's row of the Tq
@@ -364,6 +392,7 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) qf[r][i] *= a.scale_log2;
     nk[r] = gr < Tq ? len - rm.T + rm.tok(gr) + 1 : 0;
+    if constexpr (WIN) lo[r] = max(nk[r] - a.window, 0);
   }
 
   const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh + piece * 8;
@@ -395,9 +424,11 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
       vsn[u] = vsbase[key];
     }
   };
+  int kbeg = k0;  // WIN: the block step that holds the lowest lower bound
+  if constexpr (WIN) kbeg = k0 + max(blo - k0, 0) / KSTEP * KSTEP;
 #pragma unroll
-  for (int u = 0; u < kUnroll; ++u) load_ahead(u, k0 + u * NG + grp);
-  for (int kk = k0; kk < k1; kk += KSTEP) {
+  for (int u = 0; u < kUnroll; ++u) load_ahead(u, kbeg + u * NG + grp);
+  for (int kk = kbeg; kk < k1; kk += KSTEP) {
     Vec kc[kUnroll], vc[kUnroll];
     float ksc[kUnroll], vsc[kUnroll];
 #pragma unroll
@@ -426,7 +457,9 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
         for (int i = 0; i < 8; ++i) part = fmaf(qf[r][i], kf[i], part);
         float s = kfw::group_sum<G>(part);  // every lane of the group: scale * log2e * q_r.k
         if constexpr (Fmt::kScaled) s *= ksc[u];
-        if (key < nk[r]) {  // group-uniform; an invalid key touches no state
+        bool seen = key < nk[r];  // group-uniform; an invalid key touches no state
+        if constexpr (WIN) seen = seen && key >= lo[r];
+        if (seen) {
           const float mn = fmaxf(m[r], s);
           const float corr = exp2f(m[r] - mn);  // m = -inf on the first key: exp2(-inf) = 0
           float p = exp2f(s - mn);
@@ -555,19 +588,31 @@ __global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict
   if (d == 0 && lse) lse[bh] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
 }
 
-template <class Fmt, int D, bool GQ>
+template <class Fmt, int D, bool GQ, bool WIN>
 void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
   const dim3 block(kThreads);
-  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ>), grid, block, 0, s, a);
-  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ>), grid, block, 0, s, a);
-  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ>), grid, block, 0, s, a);
+  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ, WIN>), grid, block, 0, s, a);
+  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ, WIN>), grid, block, 0, s, a);
+  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ, WIN>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ, WIN>), grid, block, 0, s, a);
+}
+
+template <class Fmt, int D, bool WIN>
+void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
+  if (a.lg > 0) launch_split<Fmt, D, true, WIN>(a, n, grid, s);  // G = 1 through a grouped entry point: the plain kernels
+  else launch_split<Fmt, D, false, WIN>(a, n, grid, s);
 }
 
 template <class Fmt, int D>
 void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
-  if (a.lg > 0) launch_split<Fmt, D, true>(a, n, grid, s);  // G = 1 through a grouped entry point: the plain kernels
+  if (a.window > 0) launch_split<Fmt, D, true>(a, n, grid, s);
   else launch_split<Fmt, D, false>(a, n, grid, s);
+}
+
+template <class Fmt, int D>
+void launch_decode(const DecodeArgs& d, dim3 grid, hipStream_t s) {
+  if (d.window > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true>), grid, dim3(kThreads), 0, s, d);
+  else hipLaunchKernelGGL((attn_decode_split<Fmt, D, false>), grid, dim3(kThreads), 0, s, d);
 }
 
 // The one launcher behind the four attention entry points. st: the entry point's stride array, q (b, [t,]
@@ -576,12 +621,15 @@ void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
 // attn_decode_split. The grouped entry points pass G > 0: H is then Hkv, Tq the token count T, the q / o
 // strides' h runs over the Hkv * G query heads, and the kernels see T * G rows per (b, K / V head); G = 1
 // there launches what the plain entry points launch. Every KFAMD_EINVAL condition is tested before any
-// KFAMD_EALIGN one.
+// KFAMD_EALIGN one. window: 0 for the entry points without one, else W >= 1 (the windowed entry points): the WIN
+// kernels, except that W >= t_bound can remove no key (lens is clamped to t_bound) and launches the kernels
+// without a window.
 template <class Fmt>
 int attn_kv(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens, void* o,
             float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale, const long long* st,
-            bool has_t, void* stream, int G = 0) {
+            bool has_t, void* stream, int G = 0, int window = 0) {
   if (!q || !k || !v || !lens || !o || !st || B <= 0 || H <= 0 || B > 65535 || H > 65535) return KFAMD_EINVAL;
+  if (window < 0) return KFAMD_EINVAL;
   if (Fmt::kScaled && (!ks || !vs)) return KFAMD_EINVAL;
   const int lg = G > 0 ? group_log2(G) : 0;
   if (lg < 0 || Tq < 1 || Tq > (kMaxRows >> lg)) return KFAMD_EINVAL;
@@ -607,15 +655,16 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
   a.lse = lse;
   a.ws = static_cast<float*>(ws);
   a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound, a.lg = lg;
+  a.window = window >= t_bound ? 0 : window;
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)a.nsplit, (unsigned)H, (unsigned)B);
   if (!has_t) {
     const DecodeArgs d = {a.q,  a.k,  a.v,  a.lens, a.o,  a.lse, a.ws, B,    H,    t_bound, a.nsplit, a.scale_log2,
                           a.qb, a.qh, a.kb, a.kh,   a.kt, a.vb,  a.vh, a.vt, a.ob, a.oh,    a.ks,     a.vs,
-                          a.ksb, a.ksh, a.vsb, a.vsh};
-    if (D == 64) hipLaunchKernelGGL((attn_decode_split<Fmt, 64>), grid, dim3(kThreads), 0, s, d);
-    else hipLaunchKernelGGL((attn_decode_split<Fmt, 128>), grid, dim3(kThreads), 0, s, d);
+                          a.ksb, a.ksh, a.vsb, a.vsh, a.window};
+    if (D == 64) launch_decode<Fmt, 64>(d, grid, s);
+    else launch_decode<Fmt, 128>(d, grid, s);
   }
   for (a.row0 = 0; has_t && a.row0 < Tq; a.row0 += kSlotRows) {  // one K / V stream per kSlotRows query rows
     const int n = Tq - a.row0 < kSlotRows ? Tq - a.row0 : kSlotRows;
@@ -797,6 +846,42 @@ extern "C" int kfamd_attn_extend_gqa_fp8(const void* q, const void* k_codes, con
   if (G <= 0) return KFAMD_EINVAL;
   return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
                           true, stream, G);
+}
+
+// The sliding-window forms (contract: kfamd_kernels.h): the entry points above with a window of W >= 1 keys.
+// Decode is the single-row kernel; extend takes the grouped signature, G = 1 for plain rows.
+extern "C" int kfamd_attn_decode_win_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                          void* o, float* lse, void* ws, int B, int H, int D, int t_bound, int window,
+                                          float scale, const long long* st, void* stream) {
+  if (window < 1) return KFAMD_EINVAL;
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, H, D, 1, t_bound, scale, st,
+                           false, stream, 0, window);
+}
+
+extern "C" int kfamd_attn_decode_win_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                         const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                         int H, int D, int t_bound, int window, float scale, const long long* st,
+                                         void* stream) {
+  if (window < 1) return KFAMD_EINVAL;
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, H, D, 1, t_bound, scale, st,
+                          false, stream, 0, window);
+}
+
+extern "C" int kfamd_attn_extend_win_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                          void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T,
+                                          int t_bound, int window, float scale, const long long* st, void* stream) {
+  if (G <= 0 || window < 1) return KFAMD_EINVAL;
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
+                           true, stream, G, window);
+}
+
+extern "C" int kfamd_attn_extend_win_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                         const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                         int Hkv, int G, int D, int T, int t_bound, int window, float scale,
+                                         const long long* st, void* stream) {
+  if (G <= 0 || window < 1) return KFAMD_EINVAL;
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
+                          true, stream, G, window);
 }
 
 // K and V rows of a fused QKV activation [B][T][3][H][D] (element strides qb, qt; [3][H][D] dense)

@@ -65,6 +65,10 @@
 //   attn_chunk_split<Bf16Rows, 128, true>        234   65536
 //   attn_chunk_split<Fp8Rows, 64, true>          185   34304
 //   attn_chunk_split<Fp8Rows, 128, true>         255   67072
+// WIN = true (sliding window, kfamd_attn_chunk_win_*; the comment at the kernel): 125 / 233 / 184 / 254 VGPRs for
+// <Bf16Rows, 64>, <Bf16Rows, 128>, <Fp8Rows, 64>, <Fp8Rows, 128> plain and 126 / 234 / 185 / 255 grouped, the same LDS,
+// scratch 0. The zero-staging of the rows below the window is in the first tile's stage_write only: in every
+// tile's it spilled <Fp8Rows, 128> (256 VGPRs, 8 - 12 B scratch).
 // The grouped limit is no affine function of the row, and with both kept through the key loop
 // <Fp8Rows, 128, true> spilled (256 VGPRs, 8 B scratch): the masked tiles compute the limit again instead.
 #include <hip/hip_runtime.h>
@@ -102,6 +106,7 @@ struct ChunkArgs {
   float scale_log2;
   int lg;  // GQ kernels only: log2 of the group size G. H is then Hkv and Tq the T * G flattened rows
   long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
+  int window;  // WIN kernels only: the sliding window W >= 1
 };
 
 template <class Vec>
@@ -115,7 +120,12 @@ __device__ __forceinline__ Vec bload8(__amdgpu_buffer_rsrc_t r, int byte_off, in
 // flattened token-major, r = t * G + g with G = 1 << lg: token r >> lg of query head (h << lg) + (r & (G - 1)),
 // limit len - T + (r >> lg). The limit is non-decreasing in r, so the tile's last row still has the tile's
 // highest limit and a wave's first row its lowest; 32 and 128 are multiples of G.
-template <class Fmt, int D, bool GQ>
+// WIN (sliding window, the rule: ops/decode.py): a row of limit lim sees keys max(0, lim + 1 - W) .. lim. The lower
+// bound is non-decreasing in r like the limit: the tile's first row has the tile's lowest, a wave's first and last
+// real rows its lowest and highest. The key loop starts at the tile of 64 keys that holds the tile's lowest lower
+// bound blo; keys below blo may be poison and are staged as zeros (P = 0 would not keep a NaN of V out of P.V),
+// keys from blo on are some row's and finite, masked per element by select on the tiles that cross a row's bound.
+template <class Fmt, int D, bool GQ, bool WIN>
 __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
@@ -144,8 +154,10 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   const long long bh = (long long)b * a.H + h;
   const long long nrows = (long long)a.B * a.H * Tq;
   float* ws_o = a.ws + nrows * nsplit * 2;
+  int blo = 0;  // WIN: the lowest lower bound of the tile's rows, its first row's
+  if constexpr (WIN) blo = max(len - T + (q0 >> lg) + 1 - a.window, 0);
 
-  if (k1 <= k0) {  // no key for any row of the tile (block-uniform, before any barrier)
+  if (k1 <= k0 || (WIN && blo >= k1)) {  // no key for any row of the tile (block-uniform, before any barrier)
     for (int item = tid; item < (qlast - q0 + 1) * D; item += kThreads) {
       const int rr = q0 + item / D, d = item % D;
       const long long row = bh * Tq + rr;
@@ -167,6 +179,11 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   const bool wave_live = qw < Tq;                                   // wave-uniform: the wave holds a real row
   const int wave_lo = qw + 31 < Tq ? len - T + (qw >> lg) : -1;     // the wave's lowest limit
   const int wave_hi = len - T + (min(qw + 31, Tq - 1) >> lg);       // and its highest
+  int wave_blo = 0, wave_bhi = 0;  // WIN: the lowest and the highest lower bound of the wave's real rows
+  if constexpr (WIN) {
+    wave_blo = max(len - T + (qw >> lg) + 1 - a.window, 0);
+    wave_bhi = max(wave_hi + 1 - a.window, 0);
+  }
 
   bf16x8 qf[KS];
 #pragma unroll
@@ -198,17 +215,28 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
       if (w < 2) screg = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, 4 * lane, 4 * key0, 0));
     }
   };
-  auto stage_write = [&](int buf) {
+  // cut (WIN, the first tile only: every later one begins beyond blo): the tile's rows below it lie below every
+  // row's window and are staged as zeros; 0 for every other tile, a constant the selects fold away on
+  auto stage_write = [&](int buf, int cut) __attribute__((always_inline)) {
     char* kimg = smem + buf * 2 * TILE;
     char* vimg = kimg + TILE;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = tid + kThreads * i, row = c / CH, ch = c % CH;
       const int off = img_off<D>(row, ch);
-      *reinterpret_cast<u32x4*>(kimg + off) = Fmt::to_bf16(kreg[i]);
-      *reinterpret_cast<u32x4*>(vimg + off) = Fmt::to_bf16(vreg[i]);
+      if constexpr (WIN) {
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(kimg + off) = row < cut ? zero : Fmt::to_bf16(kreg[i]);
+        *reinterpret_cast<u32x4*>(vimg + off) = row < cut ? zero : Fmt::to_bf16(vreg[i]);
+      } else {  // the statements as they were: the same instruction order as before the window
+        *reinterpret_cast<u32x4*>(kimg + off) = Fmt::to_bf16(kreg[i]);
+        *reinterpret_cast<u32x4*>(vimg + off) = Fmt::to_bf16(vreg[i]);
+      }
     }
     if constexpr (Fmt::kScaled) {
+      if constexpr (WIN) {
+        if (lane < cut) screg = 0.f;  // as a row past the slice
+      }
       if (w < 2) s_sc[buf][w][lane] = screg;
       if (w == 1) s_sc[buf][2][lane] = screg != 0.f ? 1.f / screg : 0.f;  // 0: a row past the slice
     }
@@ -221,9 +249,10 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
 #pragma unroll
   for (int n = 0; n < ND; ++n) oacc[n] = (f32x16){};
 
-  const int j0 = k0 / FK, j1 = (k1 + FK - 1) / FK;  // k0 is a multiple of kSplitKeys, so of FK
+  // k0 is a multiple of kSplitKeys, so of FK. WIN: the first tile is the one that holds blo
+  const int j0 = (WIN ? max(k0, blo) : k0) / FK, j1 = (k1 + FK - 1) / FK;
   stage_load(j0 * FK);
-  stage_write(0);
+  stage_write(0, WIN ? blo - j0 * FK : 0);
   __syncthreads();
 
   // per-lane LDS offsets of every operand read, computed once; what varies per read is compile-time
@@ -248,7 +277,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
     if (more) stage_load(key0 + FK);
     const char* kimg = smem + BUF * 2 * TILE;
     const char* vimg = kimg + TILE;
-    if (wave_live && key0 <= wave_hi) {  // wave-uniform
+    if (wave_live && key0 <= wave_hi && (!WIN || key0 + FK - 1 >= wave_blo)) {  // wave-uniform
       f32x16 sacc[2] = {(f32x16){}, (f32x16){}};
 #pragma unroll
       for (int kk = 0; kk < KS; ++kk) {
@@ -269,7 +298,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) sacc[t] *= c;
       }
-      if (key0 + FK - 1 > wave_lo) {  // the tile reaches past some row's limit
+      // the tile reaches past some row's limit (WIN: or begins below some row's lower bound)
+      if (key0 + FK - 1 > wave_lo || (WIN && key0 < wave_bhi)) {
         int mlim = lim;
         if constexpr (GQ) {
           int qr = qrow;
@@ -281,7 +311,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int key = key0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            sacc[t][e] = key > mlim ? -INFINITY : sacc[t][e];
+            if constexpr (WIN) sacc[t][e] = key > mlim || key < mlim + 1 - a.window ? -INFINITY : sacc[t][e];
+            else sacc[t][e] = key > mlim ? -INFINITY : sacc[t][e];
           }
       }
       float mx = -INFINITY;
@@ -347,7 +378,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
         }
       }
     }
-    if (more) stage_write(1 - BUF);
+    if (more) stage_write(1 - BUF, 0);
     __syncthreads();
   };
   for (int j = j0; j < j1; j += 2) {
@@ -415,7 +446,15 @@ bool chunk_gqa_ok(int B, int Hkv, int G, int D, int T, int t_bound) {
   return lg >= 0 && T >= 1 && T <= (kMaxRows >> lg) && chunk_shape_ok(B, Hkv, D, T << lg, t_bound);
 }
 
-// The launcher behind kfamd_attn_chunk_bf16 / _fp8. st: q (b, t, h), k (b, h, t), v (b, h, t), o (b, t, h),
+template <class Fmt, bool WIN>
+void launch_chunk(const ChunkArgs& a, int D, dim3 grid, hipStream_t s) {
+  if (a.lg > 0 && D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true, WIN>), grid, dim3(kThreads), 0, s, a);
+  else if (a.lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true, WIN>), grid, dim3(kThreads), 0, s, a);
+  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false, WIN>), grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false, WIN>), grid, dim3(kThreads), 0, s, a);
+}
+
+// The launcher behind kfamd_attn_chunk_bf16 / _fp8. window: 0 for the entry points without one, else W >= 1. st: q (b, t, h), k (b, h, t), v (b, h, t), o (b, t, h),
 // then for a scaled format k_scale (b, h), v_scale (b, h). Every KFAMD_EINVAL condition is tested before
 // any KFAMD_EALIGN one. The grouped entry points pass G > 0: H is then Hkv, Tq the token count T, the q / o
 // strides' h runs over the Hkv * G query heads and the kernel tiles the T * G rows of a K / V head (the split
@@ -423,8 +462,8 @@ bool chunk_gqa_ok(int B, int Hkv, int G, int D, int T, int t_bound) {
 template <class Fmt>
 int attn_chunk(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens,
                void* o, float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
-               const long long* st, void* stream, int G = 0) {
-  if (G > 0 && !chunk_gqa_ok(B, H, G, D, Tq, t_bound)) return KFAMD_EINVAL;
+               const long long* st, void* stream, int G = 0, int window = 0) {
+  if (window < 0 || (G > 0 && !chunk_gqa_ok(B, H, G, D, Tq, t_bound))) return KFAMD_EINVAL;
   const int lg = G > 0 ? kfkv::group_log2(G) : 0;
   Tq <<= lg;  // rows per (b, K / V head) from here on
   if (!q || !k || !v || !lens || !o || !st || !chunk_shape_ok(B, H, D, Tq, t_bound)) return KFAMD_EINVAL;
@@ -451,15 +490,14 @@ int attn_chunk(const void* q, const void* k, const void* v, const float* ks, con
   a.lse = lse;
   a.ws = static_cast<float*>(ws);
   a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound, a.lg = lg;
+  a.window = window >= t_bound ? 0 : window;  // W >= t_bound removes no key: the kernels without a window
   const int chunks = (t_bound + kSplitKeys - 1) / kSplitKeys;
   a.split_keys = (chunks + a.nsplit - 1) / a.nsplit * kSplitKeys;
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)wgs, (unsigned)H, (unsigned)B);
-  if (lg > 0 && D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true>), grid, dim3(kThreads), 0, s, a);
-  else if (lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true>), grid, dim3(kThreads), 0, s, a);
-  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false>), grid, dim3(kThreads), 0, s, a);
+  if (a.window > 0) launch_chunk<Fmt, true>(a, D, grid, s);
+  else launch_chunk<Fmt, false>(a, D, grid, s);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && a.nsplit > 1)
     e = kfkv::launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s, lg);
@@ -519,4 +557,22 @@ extern "C" int kfamd_attn_chunk_gqa_fp8(const void* q, const void* k_codes, cons
   if (G <= 0) return KFAMD_EINVAL;
   return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound,
                                    scale, st, stream, G);
+}
+
+// The sliding-window forms (contract: kfamd_kernels.h): the grouped signature, G = 1 for plain rows.
+extern "C" int kfamd_attn_chunk_win_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                         void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T,
+                                         int t_bound, int window, float scale, const long long* st, void* stream) {
+  if (G <= 0 || window < 1) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, t_bound,
+                                    scale, st, stream, G, window);
+}
+
+extern "C" int kfamd_attn_chunk_win_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                        const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                        int Hkv, int G, int D, int T, int t_bound, int window, float scale,
+                                        const long long* st, void* stream) {
+  if (G <= 0 || window < 1) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound,
+                                   scale, st, stream, G, window);
 }

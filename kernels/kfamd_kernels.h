@@ -369,7 +369,41 @@ int kfamd_kv_append_gqa_fp8(const void* qkv, void* k_codes, void* v_codes, float
                             const int* pos, int B, int T, int Hq, int Hkv, int D, int Tcap, long long qb, long long qt,
                             const long long* cache_strides, void* stream);
 
-// ---- rotary position embeddings (rope_bf16.hip) -----------------------------------------------------
+// ---- sliding-window attention over the KV cache (attn_kv.hip, attn_kv_mfma.hip) -----------------------
+// The entry points above with a local causal mask: a row whose causal limit is L (it sees keys 0 .. L - 1 above:
+// L = lens[b] for decode, lens[b] - T + t + 1 for row t of T, the token's for a grouped row) sees key j iff
+// max(0, L - window) <= j < L: itself and the window - 1 keys before it. window >= 1 is a host value, the same
+// for every row of the call (KFAMD_EINVAL below 1). Keys below a row's lower bound are excluded as keys at or
+// beyond its limit are, by the key index: cache rows that lie outside every row's window may hold NaN (bf16) or
+// code 0x7F and NaN scales (FP8). The grid still comes from t_bound (lens is device memory); a workgroup whose
+// keys all lie below its rows' windows writes the empty split record and loads no K / V, and the first live one
+// starts at the window's first key step (VALU forms) or 64-key tile (MFMA form). window >= t_bound can remove
+// no key and launches the kernels of the entry points above: the same bits.
+//   kfamd_attn_decode_win_*: kfamd_attn_decode_bf16 / _fp8 (single-row kernel, its stride arrays and workspace).
+//   kfamd_attn_extend_win_*, kfamd_attn_chunk_win_*: the signatures of kfamd_attn_extend_gqa_* /
+//     kfamd_attn_chunk_gqa_* (G = 1 for plain rows), their stride arrays, row limits, workspaces and split counts.
+int kfamd_attn_decode_win_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                               float* lse, void* ws, int B, int H, int D, int t_bound, int window, float scale,
+                               const long long* strides, void* stream);
+int kfamd_attn_decode_win_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                              const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
+                              int t_bound, int window, float scale, const long long* strides, void* stream);
+int kfamd_attn_extend_win_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                               float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound, int window,
+                               float scale, const long long* strides, void* stream);
+int kfamd_attn_extend_win_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                              const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                              int G, int D, int T, int t_bound, int window, float scale, const long long* strides,
+                              void* stream);
+int kfamd_attn_chunk_win_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                              float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound, int window,
+                              float scale, const long long* strides, void* stream);
+int kfamd_attn_chunk_win_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                             const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                             int G, int D, int T, int t_bound, int window, float scale, const long long* strides,
+                             void* stream);
+
+// ---- rotary position embeddings (rope_bf16.hip)-----------------------------------------------------
 // table: fp32 [max_pos][D] contiguous, row p = cos(p f_i) | sin(p f_i), i < D/2 (built on the host). The
 // rotation is rotate-half: y[i] = x[i] c - x[i + D/2] s, y[i + D/2] = x[i + D/2] c + x[i] s, in fp32 without
 // FMA contraction, rounded once to bf16. The activation is [B][T][(Hq + 2 Hkv) D], q | k | v (element strides

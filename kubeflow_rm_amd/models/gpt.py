@@ -53,6 +53,18 @@ column shard of ``fc1`` keeps whole pairs) takes the configured norm and MLP. Th
 ``mlp="gelu"`` are the model as it was: same parameters, same state dict, same launches. Not built: bias-free linears
 (the biases stay, zero-initialised: a bias-free checkpoint loads with ``strict=False`` and leaves them at zero), GEGLU
 or any other gate, and a GLU epilogue in the large (more than 16 rows) GEMM.
+
+Sliding-window attention: ``GPTConfig(window=W)`` gives every layer a local causal mask: a position sees itself and the
+``W - 1`` positions before it (the rule is the docstring of ``ops/decode.py``; Mistral's ``q_pos - k_pos < W``).
+``decode_step`` / ``extend`` / ``extend(chunk=N)`` pass ``window`` to ``ops.attention_decode`` / ``attention_extend`` /
+``attention_chunk`` and are otherwise unchanged (capturable as before; GQA, rotary, FP8 cache and weights, the fused
+sampler, ``prefill_chunk`` and ``draft=``, which may have its own window or none, compose by shapes only). ``prefill``
+on the GPU cannot use the flash kernel, which has no window: it runs the prompt over the cache on
+``ops.attention_chunk`` in one step (its docstring). The training ``forward`` applies the mask on the torch path (CPU,
+``ops.torch_reference()``) and raises ``NotImplementedError`` on the native GPU path. ``KVCache`` still holds every
+position. ``window=None`` (the default) is the model as it was: same launches, same bits. Not built: a window in the
+flash forward / backward kernels (native GPU training of a windowed model), per-layer windows, attention sinks, a
+ring-buffer cache of capacity W, and a launch grid shrunk from a host-side lower bound.
 """
 from __future__ import annotations
 
@@ -83,8 +95,12 @@ class GPTConfig:
     norm: str = "layer"  # "layer": LayerNorm (weight + bias); "rms": RMSNorm (weight only)
     mlp: str = "gelu"  # "gelu": fc2(gelu_tanh(fc1 x)); "swiglu": fc1 [2 d_ff, d_model] interleaved gate / up (ops/swiglu.py)
     norm_eps: float | None = None  # None: the ops' defaults, 1e-5 (LayerNorm) / 1e-6 (RMSNorm)
+    window: int | None = None  # sliding-window attention: a position sees itself and the window - 1 before it; None: all
 
     def __post_init__(self):
+        if self.window is not None and (isinstance(self.window, bool) or not isinstance(self.window, int)
+                                        or self.window < 1):
+            raise ValueError(f"window={self.window!r}: None or an int >= 1 expected")
         if self.norm not in ("layer", "rms"):
             raise ValueError(f'norm={self.norm!r}: "layer" or "rms" expected')
         if self.mlp not in ("gelu", "swiglu"):
@@ -193,6 +209,13 @@ def Norm(cfg: "GPTConfig", device=None) -> torch.nn.Module:
     return (RMSNorm if cfg.norm == "rms" else LayerNorm)(cfg.d_model, cfg.dtype, device, cfg.eps)
 
 
+def _window_mask(T: int, window: int, device) -> torch.Tensor:
+    """The sliding-window causal mask ``[T, T]`` of a full sequence (True: seen): key j for query i iff
+    ``0 <= i - j < window`` (``ops/decode.py``'s rule with one token per position)."""
+    d = torch.arange(T, device=device).view(T, 1) - torch.arange(T, device=device).view(1, T)
+    return (d >= 0) & (d < window)
+
+
 def _qkv_shard(cfg: GPTConfig, tp: int, rank: int, seed: int, device) -> torch.Tensor:
     full = tpl.full_weight((3 * cfg.d_model, cfg.d_model), seed)
     hl, hd = cfg.n_heads // tp, cfg.head_dim
@@ -261,11 +284,30 @@ class Block(torch.nn.Module):
         y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
 
+    def _attention_window(self, x, residual, rope=None):
+        """Sliding-window attention of the training forward (``GPTConfig(window=W)``): SDPA under the windowed causal
+        mask, on torch ops only (CPU tensors, ``ops.torch_reference()``, head dims the flash kernels do not take). The
+        flash kernels have no window, so the native GPU path raises."""
+        B, T, _ = x.shape
+        h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
+        if x.is_cuda and ops.native_enabled() and ops.attention_supported(x, hd):
+            raise NotImplementedError("GPTConfig(window=...): the flash attention kernels (ops.flash_attention / "
+                                      "attention_qkv / attn_block) have no sliding window; the training forward of a "
+                                      "windowed model runs on the torch path (CPU, ops.torch_reference()) only")
+        qkv = self.qkv(x)
+        if rope is not None:
+            qkv = ops.rope_qkv(qkv, rope, h, hkv)
+        q, k, v = GPT._split_gqa(qkv, h, hkv, hd)
+        y = F.scaled_dot_product_attention(q, k, v, attn_mask=_window_mask(T, self.cfg.window, x.device))
+        return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
+
     def attention(self, x, residual=None, rope=None):
         """``rope``: the model's rotary table (``GPTConfig(pos="rope")``): q and k are rotated right after the QKV
         projection, inside ``ops.attn_block`` on the fused path, by ``ops.rope_qkv`` on the others."""
         B, T, _ = x.shape
         h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
+        if self.cfg.window is not None:
+            return self._attention_window(x, residual, rope)
         # the fused single-rank path whenever the TP layers would issue no collective; a forced-distributed
         # run at world size 1 (KFAMD_FORCE_DIST) takes the TP layers and their RCCL all-reduces (ADVICE r5)
         if x.is_cuda and ops.native_enabled() and ops.attention_supported(x, hd) and not tpl._collective(self.tp_group):
@@ -494,21 +536,30 @@ class GPT(torch.nn.Module):
         """Run the prompt ``idx [B, T0]`` into an empty ``cache``; logits ``[B, vocab]`` of the last position.
         The prompt's own attention runs on the unquantised QKV activation (the flash kernel on the GPU) and
         never reads the cache: with an FP8 cache only what is STORED is quantised, and the logits are those
-        of a bf16 cache bit for bit."""
+        of a bf16 cache bit for bit.
+
+        A windowed model (``GPTConfig(window=W)``) on the GPU kernels cannot use the flash kernel, which has no
+        window: the prompt then runs over the cache as ONE ``extend`` step of T0 rows on ``ops.attention_chunk``
+        (``generate(prefill_chunk=N)`` runs it in steps of N instead). With an FP8 cache the prompt then attends the
+        QUANTISED rows, as ``prefill_chunk`` does, and the logits are no longer those of a bf16 cache. On the torch
+        path (CPU, ``ops.torch_reference()``) the prompt's attention stays on the activation, under the windowed mask."""
         B, T = idx.shape
         self._check_cache(cache, B, T)
         if cache._bound != 0:
             raise ValueError("prefill expects an empty cache (continuing a cache takes decode_step)")
         native = self._native_decode(self.tok)
         c = self.cfg
+        if native and c.window is not None:  # the windowed MFMA kernel over the cache: one step of T rows
+            return self._extend_chunk(idx, cache, True, head="last", mfma=True)
         h, hkv, hd = self.blocks[0].local_heads, self.blocks[0].local_kv_heads, c.head_dim
         kv = {} if hkv == h else {"kv_heads": hkv}  # grouped K / V heads, read in place by the flash kernel
+        mask = {"is_causal": True} if c.window is None else {"attn_mask": _window_mask(T, c.window, idx.device)}
 
         def attend(li, qkv, native):  # over the QKV activation itself, which kv_append has rotated (rotary)
             if native:
                 return ops.attention_qkv(qkv.view(B, T, -1), h, hd, causal=True, **kv).view(B * T, h * hd)
             q, k, v = self._split_gqa(qkv, h, hkv, hd)
-            return F.scaled_dot_product_attention(q, k, v, is_causal=True).transpose(1, 2).reshape(B, T, h * hd)
+            return F.scaled_dot_product_attention(q, k, v, **mask).transpose(1, 2).reshape(B, T, h * hd)
         x = F.embedding(idx, self.tok)
         if self.pos is not None:
             x = x + self.pos[:T]
@@ -629,7 +680,7 @@ class GPT(torch.nn.Module):
         if self.pos is not None:
             x = x + F.embedding(cache.lens, self.pos)
         # the step's attention sees the row it appends: lens + 1, computed on the device
-        att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1)}
+        att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1), "window": self.cfg.window}
 
         def attend(li, qkv, native):
             q = qkv[:, :h * hd].view(B, h, hd)
@@ -705,7 +756,7 @@ class GPT(torch.nn.Module):
             pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
             x = x + F.embedding(pos, self.pos)
         # the step's attention sees the rows it appends: lens + T, computed on the device
-        att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T)}
+        att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T), "window": c.window}
         lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
         wsel = self._weight_selector(weights, B * T)
 

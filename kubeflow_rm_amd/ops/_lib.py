@@ -131,6 +131,19 @@ _SIGNATURES = {
                                           c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_attn_chunk_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                          c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    # the sliding-window forms: decode's signature / the grouped signatures with `window` after t_bound
+    "kfamd_attn_decode_win_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                           c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_decode_win_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                          c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_win_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_win_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_win_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_win_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
                                          ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,

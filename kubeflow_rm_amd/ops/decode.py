@@ -52,6 +52,19 @@ append of a rotary layer. It rotates the q and k slices of ``qkv`` in place at p
 device, and stores the rotated K (``kernels/rope_bf16.hip``: one launch, bf16 and FP8 caches); the attention call
 after it reads the rotated q slice of the same buffer. The attention kernels know nothing of it: the cache simply
 holds rotated keys.
+
+Sliding-window attention: ``attention_decode`` / ``attention_extend`` / ``attention_chunk`` take ``window=W``, a local
+causal mask. THE RULE (the kernels and the references point here): a query row whose causal limit is ``L`` sees key
+``j`` iff ``max(0, L - W) <= j < L``. ``L = lens[b] - T + i + 1`` for row ``i`` of the ``T`` new rows (``lens[b]`` for
+``attention_decode``); a grouped row takes the ``L`` of its token. The row therefore sees itself and the ``W - 1`` keys
+before it; with one token per position that is Hugging Face Mistral's ``q_pos - k_pos < W``. ``W >= 1`` is a host
+``int`` (not a ``bool``), the same for every row of a call; anything else raises. ``window=None`` is the call without
+a window, on the kernels without one. A key below a row's lower bound is excluded as a key at or beyond its limit is:
+cache rows outside every row's window may hold NaN (bf16) or ``0x7F`` codes and NaN scales (FP8). The launch grid
+still comes from ``t_bound`` (``lens`` stays on the device, the step stays capturable); workgroups whose keys all lie
+below the window write the empty split record and load nothing, so the K / V stream is bounded by about ``W`` keys
+per row block whatever the position. ``W >= t_bound`` can remove no key and launches the kernels without a window.
+The routing between the VALU and MFMA forms does not depend on the window. ``KVCache`` still holds every position.
 """
 from __future__ import annotations
 
@@ -374,22 +387,40 @@ def _dequantized_prefix(cache: KVCache, layer: int, lens, n: int, dtype):
     return k.to(dtype), v.to(dtype)
 
 
-def _attention_decode_torch(q, k, v, lens, scale):
-    """Masked SDPA of one query row over keys 0 .. lens[b]-1: fp32 on the CPU, the tensors' own dtype on
-    a GPU (the torch_reference() baseline reads the cache as it is stored)."""
+def _check_window(what: str, window) -> int | None:
+    """``window`` as the ops take it: ``None`` or an ``int >= 1`` (``bool`` rejected)."""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"{what}: window must be None or an int >= 1, got {window!r}")
+    return window
+
+
+def _attention_decode_torch(q, k, v, lens, scale, window=None):
+    """Masked SDPA of one query row over keys 0 .. lens[b]-1 (``window``: the module docstring's rule, the last
+    ``window`` of them): fp32 on the CPU, the tensors' own dtype on a GPU (the torch_reference() baseline reads
+    the cache as it is stored)."""
     Tcap = k.shape[2]
-    mask = torch.arange(Tcap, device=q.device).view(1, 1, 1, Tcap) < lens.view(-1, 1, 1, 1)
+    idx = torch.arange(Tcap, device=q.device).view(1, 1, 1, Tcap)
+    mask = idx < lens.view(-1, 1, 1, 1)
+    if window is not None:
+        mask = mask & (idx >= lens.view(-1, 1, 1, 1) - window)
+        v = torch.where(mask.transpose(2, 3), v, torch.zeros((), device=v.device, dtype=v.dtype))  # may hold NaN
     if not q.is_cuda:
         q, k, v = q.float(), k.float(), v.float()
     return F.scaled_dot_product_attention(q.unsqueeze(2), k, v, attn_mask=mask, scale=scale).squeeze(2)
 
 
-def _attention_extend_torch(q, k, v, lens, scale):
-    """Masked fp32 SDPA of T query rows per head, row i over keys 0 .. lens[b]-T+i. A row with no key
-    gives zeros and lse = -inf. Returns (o [B, T, H, D] fp32, lse [B, T, H])."""
+def _attention_extend_torch(q, k, v, lens, scale, window=None):
+    """Masked fp32 SDPA of T query rows per head, row i over keys 0 .. lens[b]-T+i (``window``: the module
+    docstring's rule, the last ``window`` of them). A row with no key gives zeros and lse = -inf. Returns
+    (o [B, T, H, D] fp32, lse [B, T, H])."""
     T, Tcap = q.shape[1], k.shape[2]
     limit = lens.view(-1, 1).long() - T + torch.arange(T, device=q.device).view(1, T)  # last visible key
-    mask = torch.arange(Tcap, device=q.device).view(1, 1, 1, Tcap) <= limit.view(-1, 1, T, 1)  # [B, 1, T, Tcap]
+    idx = torch.arange(Tcap, device=q.device).view(1, 1, 1, Tcap)
+    mask = idx <= limit.view(-1, 1, T, 1)  # [B, 1, T, Tcap]
+    if window is not None:
+        mask = mask & (idx > limit.view(-1, 1, T, 1) - window)
     s = (q.transpose(1, 2).float() @ k.float().transpose(-1, -2)) * scale  # [B, H, T, Tcap]
     s = s.masked_fill(~mask, float("-inf"))
     lse = torch.logsumexp(s, -1)
@@ -418,13 +449,14 @@ def _attend_args(what: str, q, cache: KVCache, scale, lens, t_bound, rank: int =
             cache.t_bound if t_bound is None else int(t_bound))
 
 
-def _attend_torch(reference, q, cache: KVCache, layer: int, G: int, scale, out, lens, t_bound, return_lse, dtype):
-    """The torch path (CPU tensors / ops.torch_reference()): ``reference(q, k, v, lens, scale) -> (o, lse)`` over the
-    cache's K / V expanded to q's heads, an FP8 cache's as its visible rows dequantised to ``dtype``."""
+def _attend_torch(reference, q, cache: KVCache, layer: int, G: int, scale, out, lens, t_bound, return_lse, dtype,
+                  window=None):
+    """The torch path (CPU tensors / ops.torch_reference()): ``reference(q, k, v, lens, scale, window) -> (o, lse)``
+    over the cache's K / V expanded to q's heads, an FP8 cache's as its visible rows dequantised to ``dtype``."""
     k, v = cache.k[layer], cache.v[layer]
     if cache.fp8:
         k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), dtype)
-    o, lse = reference(q, *_expand_kv(k, v, G), lens, scale)
+    o, lse = reference(q, *_expand_kv(k, v, G), lens, scale, window)
     o = o.to(q.dtype)
     if out is not None:
         out.copy_(o)
@@ -451,62 +483,70 @@ def _attend_contract(what: str, q, cache: KVCache, layer: int, lens, t_bound, ou
 
 
 def _attend_launch(what: str, name: str, q, cache: KVCache, layer: int, out, lens, ws, G: int, t_bound: int,
-                   scale: float, return_lse: bool):
+                   scale: float, return_lse: bool, window: int | None = None):
     """``name[_gqa]_{bf16,fp8}(q, k, v, *scales, lens, out, lse, ws, B, (H | Hkv, G), D, T, t_bound, scale, strides,
     stream)``: the extend and chunk entry points. A rank-3 ``q`` / ``out`` (attention_decode's G rows of a group) is
-    T = 1 with a zero t stride."""
+    T = 1 with a zero t stride. With a window: ``name_win_{bf16,fp8}``, the grouped signature (G = 1 included) with
+    ``window`` after ``t_bound``."""
     B, D, k, v = cache.B, cache.D, cache.k[layer], cache.v[layer]
     if q.dim() == 4:
         T, qs, os, dims = q.shape[1], q.stride()[:3], out.stride()[:3], f"T={q.shape[1]} H={q.shape[2]}"
     else:
         T, qs, os, dims = 1, (q.stride(0), 0, q.stride(1)), (out.stride(0), 0, out.stride(1)), f"H={q.shape[1]} G={G}"
     lse = torch.empty(q.shape[:-1], device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry(name if G == 1 else name + "_gqa", cache, layer)
+    grouped = G > 1 or window is not None
+    fn, scales, tag = _entry(name + ("_win" if window is not None else "_gqa" if grouped else ""), cache, layer)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, *((cache.H,) if G == 1 else (cache.H, G)),
-            D, T, t_bound, scale,
+            lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, *((cache.H, G) if grouped else (cache.H,)),
+            D, T, t_bound, *(() if window is None else (min(window, cache.capacity),)), scale,
             _ll(*qs, *k.stride()[:3], *v.stride()[:3], *os, *(n for s in scales for n in s.stride()[:2])),
             _stream_ptr(q))
-    _lib.check(rc, f"{what}[{tag}B={B} {dims} D={D} t_bound={t_bound}]")
+    _lib.check(rc, f"{what}[{tag}B={B} {dims} D={D} t_bound={t_bound}{'' if window is None else f' window={window}'}]")
     return (out, lse) if return_lse else out
 
 
 def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
                      out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
-                     t_bound: int | None = None, return_lse: bool = False):
+                     t_bound: int | None = None, return_lse: bool = False, window: int | None = None):
     """softmax(scale * q k^T) v for one query row per head: q ``[B, H, D]`` (any b / h strides, e.g. a
     view of the fused QKV output), keys ``0 .. lens[b]-1`` of ``cache`` layer ``layer``. ``out``:
     optional ``[B, H, D]`` view to write (e.g. of a ``[B, 1, H*D]`` buffer). ``lens`` / ``t_bound``
     default to the cache's. Grouped-query attention: ``H = G * cache.H`` query heads, head h on K / V head
     ``h // G``; on a GPU G > 1 runs the group's G rows as ``attention_extend`` does at T = 1: the extend kernel's
     row slots for G < ``GQA_MFMA_MIN_ROWS``, the MFMA kernel for G = 8 and 16 (K / V streamed once per group; the
-    extend / chunk workspace, allocated on first use and never inside a capture)."""
+    extend / chunk workspace, allocated on first use and never inside a capture). ``window=W``: the last W of those
+    keys only (the module docstring's rule), on the windowed kernels of the same routing."""
     what = "attention_decode"
+    window = _check_window(what, window)
     _, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound, rank=3)
     if not _native(q):
-        def reference(q, k, v, lens, scale):  # its own SDPA, not attention_extend's at T = 1; lse only on request
-            o = _attention_decode_torch(q, k, v, lens, scale)
+        def reference(q, k, v, lens, scale, window):  # its own SDPA, not attention_extend's at T = 1; lse on request
+            o = _attention_decode_torch(q, k, v, lens, scale, window)
             if not return_lse:
                 return o, None
             s = (q.float().unsqueeze(2) @ k.float().transpose(-1, -2)).squeeze(2) * scale
-            dead = torch.arange(k.shape[2], device=q.device).view(1, 1, -1) >= lens.view(-1, 1, 1)
+            idx = torch.arange(k.shape[2], device=q.device).view(1, 1, -1)
+            dead = idx >= lens.view(-1, 1, 1)
+            if window is not None:
+                dead = dead | (idx < lens.view(-1, 1, 1) - window)
             return o, torch.logsumexp(s.masked_fill(dead, float("-inf")), -1)
         return _attend_torch(reference, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
-                             q.dtype if q.is_cuda else torch.float32)
+                             q.dtype if q.is_cuda else torch.float32, window)
     out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if _gqa_mfma(1, G):  # the group's G rows on an MFMA tile
         res = attention_chunk(q.unsqueeze(1), cache, layer, scale=scale, out=out.unsqueeze(1), lens=lens,
-                              t_bound=t_bound, return_lse=return_lse)
+                              t_bound=t_bound, return_lse=return_lse, window=window)
         return (out, res[1].squeeze(1)) if return_lse else out
     if G > 1:  # the group's G rows on the extend kernel's row slots: T = 1, no t stride
         return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(), G, t_bound,
-                              scale, return_lse)
+                              scale, return_lse, window)
     B, H, D = q.shape
     k, v = cache.k[layer], cache.v[layer]
     lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry("kfamd_attn_decode", cache, layer)
+    fn, scales, tag = _entry("kfamd_attn_decode" if window is None else "kfamd_attn_decode_win", cache, layer)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound, scale,
+            lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound,
+            *(() if window is None else (min(window, cache.capacity),)), scale,
             _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
                 *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
     _lib.check(rc, f"attention_decode[{tag}B={B} H={H} D={D} t_bound={t_bound}]")
@@ -515,7 +555,7 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
 
 def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
                      out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
-                     t_bound: int | None = None, return_lse: bool = False):
+                     t_bound: int | None = None, return_lse: bool = False, window: int | None = None):
     """softmax(scale * q k^T) v for T new query rows per head (1 <= T <= 16 on a GPU): q ``[B, T, H, D]``
     (any b / t / h strides, e.g. ``qkv.view(B, T, 3, H, D)[:, :, 0]``), already appended to ``cache``
     layer ``layer``. ``lens[b]`` counts the keys INCLUDING the T new rows; row i attends keys
@@ -523,26 +563,28 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     ``[B, T, H, D]`` view to write. ``lens`` / ``t_bound`` default to the cache's. K and V are read once
     per 8 query rows (``kernels/attn_kv.hip``). Grouped-query attention: ``H = G * cache.H`` query heads; the
     rows of a K / V head are then the ``T * G`` (token, head-in-group) pairs, and the GPU limit is
-    ``T * G <= MAX_EXTEND_ROWS``; with G > 1, ``GQA_MFMA_MIN_ROWS`` rows or more run ``attention_chunk``'s kernel."""
+    ``T * G <= MAX_EXTEND_ROWS``; with G > 1, ``GQA_MFMA_MIN_ROWS`` rows or more run ``attention_chunk``'s kernel.
+    ``window=W``: each row sees the last W keys up to its own only (the module docstring's rule)."""
     what = "attention_extend"
+    window = _check_window(what, window)
     T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
     if not _native(q):
         return _attend_torch(_attention_extend_torch, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
-                             torch.float32)
+                             torch.float32, window)
     if T * G > MAX_EXTEND_ROWS:
         raise ValueError(f"attention_extend: 1 <= T * G <= {MAX_EXTEND_ROWS} query rows per K / V head expected on a "
                          f"GPU, got T = {T}, G = {G}")
     out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if _gqa_mfma(T, G):
         return attention_chunk(q, cache, layer, scale=scale, out=out, lens=lens, t_bound=t_bound,
-                               return_lse=return_lse)
+                               return_lse=return_lse, window=window)
     return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(), G, t_bound, scale,
-                          return_lse)
+                          return_lse, window)
 
 
 def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
                     out: torch.Tensor | None = None, lens: torch.Tensor | None = None,
-                    t_bound: int | None = None, return_lse: bool = False):
+                    t_bound: int | None = None, return_lse: bool = False, window: int | None = None):
     """``attention_extend`` without the row limit: softmax(scale * q k^T) v for T new query rows per head
     (1 <= T <= capacity on a GPU), q ``[B, T, H, D]`` (any b / t / h strides), already appended to ``cache``
     layer ``layer``; ``lens[b]`` counts the keys INCLUDING the T new rows, row i attends keys
@@ -552,12 +594,14 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     for T <= 16 it agrees with ``attention_extend`` within the kernels' bounds, not bit for bit. On CPU
     tensors and under ``ops.torch_reference()`` it is the same torch code as ``attention_extend``. Grouped-query
     attention: ``H = G * cache.H`` query heads; the kernel tiles the ``T * G`` rows of a K / V head
-    (``T * G <= 65535``)."""
+    (``T * G <= 65535``). ``window=W``: each row sees the last W keys up to its own only (the module docstring's
+    rule); the key tiles below the lowest lower bound of a query tile's rows are not read."""
     what = "attention_chunk"
+    window = _check_window(what, window)
     T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
     if not _native(q):
         return _attend_torch(_attention_extend_torch, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
-                             torch.float32)
+                             torch.float32, window)
     if T > cache.capacity:
         raise ValueError(f"attention_chunk: 1 <= T <= capacity ({cache.capacity}) query rows expected on a GPU, "
                          f"got {T}")
@@ -565,4 +609,4 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     if G > 1 and T * G > 65535:
         raise ValueError(f"attention_chunk: T * G <= 65535 query rows per K / V head expected, got T = {T}, G = {G}")
     return _attend_launch(what, "kfamd_attn_chunk", q, cache, layer, out, lens, cache._chunk_ws(T, G), G, t_bound,
-                          scale, return_lse)
+                          scale, return_lse, window)

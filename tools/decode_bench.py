@@ -66,6 +66,13 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         gated GEMM against the two-launch MLP in the same model (its _fc1 shadowed by this tool), B in {1, 16}, position
         about 2048, graphed and eager, 7 interleaved runs: ms/token. RMSNorm backward with dres at 8192 x 2048: the
         kernel against the fp32 torch arithmetic it replaced.
+  window (not in the default list) sliding-window attention. Kernel: D = 128, capacity 4096, 4096 keys, B x 16 heads
+        with B in {1, 8} (B * H = 16, 128), bf16 and FP8 caches rotated past the last-level cache: ops.attention_decode,
+        ops.attention_extend at Tq = 4 and ops.attention_chunk at T = 128, each with window in {256, 1024, 4095, 4096}
+        against window=None (the kernels without a window) interleaved in one process, medians of 7 blocks with min
+        and max. 4096 removes nothing and, being t_bound, launches the kernels without a window; 4095 removes one key
+        and runs the windowed ones. Model: gpt-1b (gpt-small with --quick), B in {1, 8}, a graphed decode step at
+        position about 4000 with GPTConfig(window=1024) against none, 7 interleaved runs: ms/token.
 """
 from __future__ import annotations
 
@@ -83,7 +90,8 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
-                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600}
+                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600}
+WINDOW_WS = (256, 1024, 4095, 4096)
 GQA_GS = (1, 2, 4, 8, 16)
 GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
 CHUNK_TS = (16, 32, 64, 128, 256, 512)
@@ -1155,7 +1163,86 @@ def step_glu(quick: bool):
     return {"kernel": _glu_kernel_rows(quick), "rmsnorm_bwd": _glu_rmsnorm_rows(quick), "model": _glu_model_rows(quick)}
 
 
-STEPS = {"glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+def _window_kernel_rows(quick: bool):
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    H, D, cap, n = 16, 128, 4096, 4096
+    blocks = 5 if quick else 7
+    for B in (1, 8):
+        caches, ncopy = _gqa_caches(B, H, H, D, cap, quick)
+        shapes = {"decode": (B, H, D), "extend_T4": (B, 4, H, D), "chunk_T128": (B, 128, H, D)}
+        calls = {"decode": ops.attention_decode, "extend_T4": ops.attention_extend, "chunk_T128": ops.attention_chunk}
+        for kind, c in caches.items():
+            c.set_lens([n] * B)
+            for name, shape in shapes.items():
+                q = torch.randn(*shape, device="cuda").to(torch.bfloat16)
+                out = torch.empty_like(q)
+                fn = calls[name]
+                fns = {"none": (lambda i: fn(q, c, i % ncopy, out=out, t_bound=n))}
+                for W in WINDOW_WS:
+                    fns[f"W{W}"] = (lambda i, W=W: fn(q, c, i % ncopy, out=out, t_bound=n, window=W))
+                r = _time_blocks(fns, blocks=blocks, iters=20)
+                row = {"op": name, "kind": kind, "B": B, "H": H, "D": D, "len": n, "cache_copies": ncopy, "none": r["none"]}
+                for W in WINDOW_WS:
+                    t = r[f"W{W}"]
+                    sep = _sep({"min": t["min_us"], "max": t["max_us"]},
+                               {"min": r["none"]["min_us"], "max": r["none"]["max_us"]})
+                    row[f"W{W}"] = {**t, "none_over_this": r["none"]["median_us"] / t["median_us"], "separated": sep}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+        del caches
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _window_model_rows(quick: bool):
+    import dataclasses
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    rows = []
+    base = CONFIGS["gpt-small" if quick else "gpt-1b"]
+    new = 64
+    prompt = base.max_seq - 2 * new
+    models = {"none": GPT(base, device="cuda").eval(),
+              "W1024": GPT(dataclasses.replace(base, window=1024), device="cuda").eval()}
+    for B in (1, 8):
+        idx = torch.randint(0, base.vocab_size, (B, prompt), device="cuda")
+        toks = torch.randint(0, base.vocab_size, (new, B), device="cuda")
+
+        def run(key):
+            model = models[key]
+            cache = model.new_cache(B, prompt + new)
+            model.prefill(idx, cache)
+            step = model.graphed_decode_step(cache)
+            step(toks[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(1, new):
+                step(toks[i])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+        res = {k: [] for k in models}
+        for _ in range(3 if quick else 7):  # interleaved
+            for k in models:
+                res[k].append(run(k))
+        row = {"model": "gpt-small" if quick else "gpt-1b", "B": B, "position": f"{prompt + 1} .. {prompt + new - 1}",
+               "mode": "graph"}
+        for k, v in res.items():
+            row[k] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+        row["none_over_W1024"] = row["none"]["ms_per_token"] / row["W1024"]["ms_per_token"]
+        row["separated"] = _sep(row["none"], row["W1024"])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def step_window(quick: bool):
+    return {"kernel": _window_kernel_rows(quick), "model": _window_model_rows(quick)}
+
+
+STEPS = {"window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
