@@ -89,6 +89,20 @@
 // the VGPRs of its WIN = false twin in the table below (66 / 84 decode; 64 / 92 / 129 / 201 and 84 / 112 / 149 / 197
 // extend, GQ alike), scratch 0. Measured: profiles/window.
 //
+// Ring-buffer cache (the rule: the docstring of ops/decode.py): key j lives in slot j % C, C a multiple of kSplitKeys,
+// lens absolute and unbounded. RING = true instantiations of attn_decode_split and attn_extend_split (plain and GQ, all
+// row slots; RING implies WIN), behind the kfamd_attn_*_ring_* entry points; the RING = false ones are the kernels as
+// they were (the 103 kernels of this file, attn_kv_mfma.hip and rope_bf16.hip compared as ISA with the previous build:
+// identical). The grid is ceil((W + T - 1) / 256) + 1 splits per (b, h), a function of W and T alone; split s of batch
+// row b covers absolute keys from base_b + 256 s on, base_b = (max(lens[b] - T + 1 - W, 0) / 256) * 256 computed on the
+// device, so the partition stays the absolute 256-aligned one and every early return stays block-uniform. A split is
+// one contiguous run of slots: its slot base comes once per workgroup from the scalar k0 % C and is folded into the
+// K / V / scale pointers, the in-split addressing stays key - k0, and the look-ahead address is clamped as an absolute
+// key index (min(key, last)) before it is mapped to the slot. No key index is ever multiplied by a stride. Slots
+// outside every row's window, those after key lens[b] - 1 included, are excluded by the key index and may hold NaN.
+// VGPRs: those of the WIN twins in the table below (66 / 84 decode; 64 / 92 / 129 / 201 and 84 / 112 / 149 / 197
+// extend, GQ alike), scratch 0. kv_append<true> / kv_append_fp8<D, true> write slot (lens[b] + t) % C: 20 / 32 (D = 64), 31 (D = 128) VGPRs.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): VGPRs, the same
 // at D = 64 and at D = 128 unless two are given; scratch is 0 for every instantiation. "before": the four
 // kernels this file replaced, D = 64 / 128.
@@ -104,6 +118,20 @@
 //   attn_extend_split<Fp8Rows, D, 4>    149   150 / 150
 //   attn_extend_split<Fp8Rows, D, 8>    197   198 / 198
 //   kv_append / kv_append_fp8<D>     21 / 39   21 /  39
+// RING = true (kfamd_attn_*_ring_*, kfamd_kv_append_ring_*), D = 64 / 128 alike unless two are given, GQ alike, scratch 0:
+//   attn_decode_split<Bf16Rows, D, true, true>             66
+//   attn_decode_split<Fp8Rows, D, true, true>              84
+//   attn_extend_split<Bf16Rows, D, 1, GQ, true, true>      64
+//   attn_extend_split<Bf16Rows, D, 2, GQ, true, true>      92
+//   attn_extend_split<Bf16Rows, D, 4, GQ, true, true>     129
+//   attn_extend_split<Bf16Rows, D, 8, GQ, true, true>     201
+//   attn_extend_split<Fp8Rows, D, 1, GQ, true, true>       84
+//   attn_extend_split<Fp8Rows, D, 2, GQ, true, true>      112
+//   attn_extend_split<Fp8Rows, D, 4, GQ, true, true>      149
+//   attn_extend_split<Fp8Rows, D, 8, GQ, true, true>      197
+//   kv_append<true>                                        20
+//   kv_append_fp8<D, true>                            32 / 31
+// The comparison with the previous build and these counts: tools/kernel_isa_diff.py (two directories of hipcc -S output).
 // The GQ = true instantiations of attn_extend_split use the same VGPRs as the GQ = false rows above, R for R
 // (64 / 92 / 129 / 201 and 84 / 112 / 149 / 197), the same LDS, scratch 0; attn_kv_combine<D> and
 // attn_kv_combine_gqa<D> 12 VGPRs each.
@@ -147,6 +175,7 @@ struct AttnArgs {
   int lg;  // GQ kernels only: log2 of the group size G. H is then Hkv and Tq the T * G flattened rows
   long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
   int window;  // WIN kernels only: the sliding window W >= 1 (the rule: the header)
+  int cap;     // RING kernels only: the ring's capacity C, a multiple of kSplitKeys
 };
 
 // The single-row kernel's arguments: AttnArgs without Tq, row0 and the t strides.
@@ -165,13 +194,15 @@ struct DecodeArgs {
   const float* vs;
   long long ksb, ksh, vsb, vsh;
   int window;  // WIN kernel only
+  int cap;     // RING kernel only
 };
 
 // One query row per (b, h). workspace: [B][H][nsplit][2] (m, l) then [B][H][nsplit][D] (o), fp32: the
 // extend kernel's at Tq = 1. What the extend body's comments say about key validity, clamped addresses,
 // the block-uniform early return, whole block steps and the window's lower bound holds here word for word.
-template <class Fmt, int D, bool WIN>
+template <class Fmt, int D, bool WIN, bool RING>
 __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
+  static_assert(WIN || !RING, "a ring always has a window");
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
   constexpr int kUnroll = Fmt::unroll(1);
@@ -187,8 +218,10 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
   __shared__ float s_o[NG][D + 4];
 
   int len = a.lens[b];
-  len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
-  const int k0 = split * kSplitKeys;
+  if constexpr (RING) len = max(len, 0);  // absolute, not bounded by the capacity
+  else len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
+  int k0 = split * kSplitKeys;
+  if constexpr (RING) k0 += max(len - a.window, 0) / kSplitKeys * kSplitKeys;  // + base_b: the split that holds lo
   const int k1 = min(k0 + kSplitKeys, len);  // valid keys of this split: [k0, k1)
   int lo = 0;  // WIN: the row sees keys [lo, len)
   if constexpr (WIN) lo = max(len - a.window, 0);
@@ -222,6 +255,12 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
     ksbase = a.ks + b * a.ksb + h * a.ksh;
     vsbase = a.vs + b * a.vsb + h * a.vsh;
   }
+  if constexpr (RING) {  // the split's 256 keys are one run of slots from k0 % C on: what follows indexes it by key - k0
+    const int s0 = k0 % a.cap;
+    kbase += s0 * a.kt;
+    vbase += s0 * a.vt;
+    if constexpr (Fmt::kScaled) ksbase += s0, vsbase += s0;
+  }
   const int last = k1 - 1;
 
   float m = -INFINITY, l = 0.f, acc[8];
@@ -232,6 +271,7 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
   float ksn[kUnroll], vsn[kUnroll];  // Fmt::kScaled only
   auto load_ahead = [&](int u, int key) {
     key = min(key, last);
+    if constexpr (RING) key -= k0;  // clamped as an absolute index, then mapped to the slot
     kn[u] = *reinterpret_cast<const Vec*>(kbase + key * a.kt);
     vn[u] = *reinterpret_cast<const Vec*>(vbase + key * a.vt);
     if constexpr (Fmt::kScaled) {
@@ -332,8 +372,9 @@ struct RowMap {
 // beyond nk is, by the branch on the key index. The limits are non-decreasing in r, so the launch's first row has
 // its lowest lower bound: a split that ends at or below it holds no key for any row, and inside the first live split
 // the walk starts at the block step that holds it.
-template <class Fmt, int D, int R, bool GQ, bool WIN>
+template <class Fmt, int D, int R, bool GQ, bool WIN, bool RING>
 __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
+  static_assert(WIN || !RING, "a ring always has a window");
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
   constexpr int kUnroll = Fmt::unroll(R);
@@ -354,8 +395,11 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   __shared__ float s_o[NG][RC][D + 4];
 
   int len = a.lens[b];
-  len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
-  const int k0 = split * kSplitKeys;
+  if constexpr (RING) len = max(len, 0);  // absolute, not bounded by the capacity
+  else len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
+  int k0 = split * kSplitKeys;
+  // + base_b, from the call's first token (the same for the launches of rows 0 .. 7 and 8 .. 15)
+  if constexpr (RING) k0 += max(len - rm.T + 1 - a.window, 0) / kSplitKeys * kSplitKeys;
   const int k1 = min(k0 + kSplitKeys, len);  // keys of this split that the last row may see: [k0, k1)
   const long long bh = (long long)b * a.H + h;
   const long long nrows = (long long)a.B * a.H * Tq;
@@ -402,6 +446,12 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
     ksbase = a.ks + b * a.ksb + h * a.ksh;
     vsbase = a.vs + b * a.vsb + h * a.vsh;
   }
+  if constexpr (RING) {  // the split's 256 keys are one run of slots from k0 % C on: what follows indexes it by key - k0
+    const int s0 = k0 % a.cap;
+    kbase += s0 * a.kt;
+    vbase += s0 * a.vt;
+    if constexpr (Fmt::kScaled) ksbase += s0, vsbase += s0;
+  }
   const int last = k1 - 1;  // addresses are clamped to a valid key; the key index decides validity
 
   float m[R], l[R], acc[R][8];
@@ -417,6 +467,7 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   float ksn[kUnroll], vsn[kUnroll];  // Fmt::kScaled only
   auto load_ahead = [&](int u, int key) {
     key = min(key, last);
+    if constexpr (RING) key -= k0;  // clamped as an absolute index, then mapped to the slot
     kn[u] = *reinterpret_cast<const Vec*>(kbase + key * a.kt);
     vn[u] = *reinterpret_cast<const Vec*>(vbase + key * a.vt);
     if constexpr (Fmt::kScaled) {
@@ -588,32 +639,39 @@ __global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict
   if (d == 0 && lse) lse[bh] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
 }
 
-template <class Fmt, int D, bool GQ, bool WIN>
-void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
+template <class Fmt, int D, bool GQ, bool WIN, bool RING>
+void launch_rows(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
   const dim3 block(kThreads);
-  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ, WIN>), grid, block, 0, s, a);
-  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ, WIN>), grid, block, 0, s, a);
-  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ, WIN>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ, WIN>), grid, block, 0, s, a);
+  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ, WIN, RING>), grid, block, 0, s, a);
+  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ, WIN, RING>), grid, block, 0, s, a);
+  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ, WIN, RING>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ, WIN, RING>), grid, block, 0, s, a);
 }
 
-template <class Fmt, int D, bool WIN>
-void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
-  if (a.lg > 0) launch_split<Fmt, D, true, WIN>(a, n, grid, s);  // G = 1 through a grouped entry point: the plain kernels
-  else launch_split<Fmt, D, false, WIN>(a, n, grid, s);
+template <class Fmt, int D, bool WIN, bool RING>
+void launch_group(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
+  if (a.lg > 0) launch_rows<Fmt, D, true, WIN, RING>(a, n, grid, s);  // G = 1 through a grouped entry point: the plain kernels
+  else launch_rows<Fmt, D, false, WIN, RING>(a, n, grid, s);
 }
 
 template <class Fmt, int D>
 void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
-  if (a.window > 0) launch_split<Fmt, D, true>(a, n, grid, s);
-  else launch_split<Fmt, D, false>(a, n, grid, s);
+  if (a.cap > 0) launch_group<Fmt, D, true, true>(a, n, grid, s);
+  else if (a.window > 0) launch_group<Fmt, D, true, false>(a, n, grid, s);
+  else launch_group<Fmt, D, false, false>(a, n, grid, s);
 }
 
 template <class Fmt, int D>
 void launch_decode(const DecodeArgs& d, dim3 grid, hipStream_t s) {
-  if (d.window > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true>), grid, dim3(kThreads), 0, s, d);
-  else hipLaunchKernelGGL((attn_decode_split<Fmt, D, false>), grid, dim3(kThreads), 0, s, d);
+  if (d.cap > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true, true>), grid, dim3(kThreads), 0, s, d);
+  else if (d.window > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true, false>), grid, dim3(kThreads), 0, s, d);
+  else hipLaunchKernelGGL((attn_decode_split<Fmt, D, false, false>), grid, dim3(kThreads), 0, s, d);
 }
+
+// Splits of a ring launch: the absolute 256-aligned partition rebased per batch row at base_b = the split that holds
+// the first token's lower bound. The rows of a call see at most W + T - 1 keys from there on, which begin up to 255
+// keys into their split: ceil((W + T - 1) / 256) + 1 splits always suffice, whatever the position.
+int ring_splits(int window, int T) { return (int)(((long long)window + T - 1 + kSplitKeys - 1) / kSplitKeys) + 1; }
 
 // The one launcher behind the four attention entry points. st: the entry point's stride array, q (b, [t,]
 // h), k (b, h, t), v (b, h, t), o (b, [t,] h), then for a scaled format k_scale (b, h), v_scale (b, h);
@@ -627,9 +685,13 @@ void launch_decode(const DecodeArgs& d, dim3 grid, hipStream_t s) {
 template <class Fmt>
 int attn_kv(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens, void* o,
             float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale, const long long* st,
-            bool has_t, void* stream, int G = 0, int window = 0) {
+            bool has_t, void* stream, int G = 0, int window = 0, bool ring = false) {
   if (!q || !k || !v || !lens || !o || !st || B <= 0 || H <= 0 || B > 65535 || H > 65535) return KFAMD_EINVAL;
   if (window < 0) return KFAMD_EINVAL;
+  // ring: t_bound is the capacity C. W + T - 1 <= C: the step's appends overwrite nothing its first row sees
+  if (ring && (window < 1 || t_bound < 1 || t_bound % kSplitKeys || Tq < 1 || (long long)window + Tq - 1 > t_bound))
+    return KFAMD_EINVAL;
+  const int ring_nsplit = ring ? ring_splits(window, Tq) : 0;
   if (Fmt::kScaled && (!ks || !vs)) return KFAMD_EINVAL;
   const int lg = G > 0 ? group_log2(G) : 0;
   if (lg < 0 || Tq < 1 || Tq > (kMaxRows >> lg)) return KFAMD_EINVAL;
@@ -643,7 +705,7 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
   if (a.kt < D || a.vt < D) return KFAMD_EINVAL;
   const long long lim = (1ll << 31) / (long long)sizeof(typename Fmt::Elem);  // a (b, h) slice stays below 2^31 bytes
   if ((long long)t_bound * a.kt >= lim || (long long)t_bound * a.vt >= lim) return KFAMD_EINVAL;
-  a.nsplit = (t_bound + kSplitKeys - 1) / kSplitKeys;
+  a.nsplit = ring ? ring_nsplit : (t_bound + kSplitKeys - 1) / kSplitKeys;
   if (a.nsplit > 1 && !ws) return KFAMD_EINVAL;
   if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || (ws && !al16(ws))) return KFAMD_EALIGN;
   if (Fmt::kScaled && (!al4(ks) || !al4(vs))) return KFAMD_EALIGN;
@@ -655,14 +717,15 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
   a.lse = lse;
   a.ws = static_cast<float*>(ws);
   a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound, a.lg = lg;
-  a.window = window >= t_bound ? 0 : window;
+  a.window = ring ? window : window >= t_bound ? 0 : window;
+  a.cap = ring ? t_bound : 0;
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)a.nsplit, (unsigned)H, (unsigned)B);
   if (!has_t) {
     const DecodeArgs d = {a.q,  a.k,  a.v,  a.lens, a.o,  a.lse, a.ws, B,    H,    t_bound, a.nsplit, a.scale_log2,
                           a.qb, a.qh, a.kb, a.kh,   a.kt, a.vb,  a.vh, a.vt, a.ob, a.oh,    a.ks,     a.vs,
-                          a.ksb, a.ksh, a.vsb, a.vsh, a.window};
+                          a.ksb, a.ksh, a.vsb, a.vsh, a.window, a.cap};
     if (D == 64) launch_decode<Fmt, 64>(d, grid, s);
     else launch_decode<Fmt, 128>(d, grid, s);
   }
@@ -687,6 +750,9 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
 }
 
 // ---- append ------------------------------------------------------------------------------------
+// RING (both append kernels): row lens[b] + t goes to slot (lens[b] + t) % Tcap and no row is dropped (T <= Tcap on
+// the host, so no slot is written twice).
+template <bool RING>
 __global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv, __bf16* __restrict__ kc,
                                                  __bf16* __restrict__ vc, const int* __restrict__ pos, int B, int T,
                                                  int H, int D8, int Tcap, long long qb, long long qt, long long kb,
@@ -704,8 +770,13 @@ __global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv,
   r /= 2;
   const int t = (int)(r % T);
   const int b = (int)(r / T);
-  const long long row = (long long)pos[b] + t;
-  if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, never written
+  long long row = (long long)pos[b] + t;
+  if constexpr (RING) {
+    if (row < 0) return;
+    row = (unsigned)row % (unsigned)Tcap;  // below 2^32: an int32 length plus t
+  } else {
+    if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, never written
+  }
   const u32x4 val =
       *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)Hq + s * H + h) * (D8 * 8) + d8 * 8);
   __bf16* dst = s == 0 ? kc + b * kb + h * kh + row * kt : vc + b * vb + h * vh + row * vt;
@@ -716,7 +787,7 @@ __global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv,
 // amax by the group reduction, one scale store by the group's first lane, one 8-B code store per lane.
 // Groups are whole: the thread count is a multiple of D / 8 and so is the block size, and both early
 // returns are group-uniform.
-template <int D>
+template <int D, bool RING>
 __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
                                                      uint8_t* __restrict__ vc, float* __restrict__ ks,
                                                      float* __restrict__ vs, const int* __restrict__ pos, int B, int T,
@@ -737,8 +808,13 @@ __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ 
   r /= 2;
   const int t = (int)(r % T);
   const int b = (int)(r / T);
-  const long long row = (long long)pos[b] + t;
-  if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, neither codes nor scale written
+  long long row = (long long)pos[b] + t;
+  if constexpr (RING) {
+    if (row < 0) return;
+    row = (unsigned)row % (unsigned)Tcap;
+  } else {
+    if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, neither codes nor scale written
+  }
   float x[8];
   Bf16Rows::unpack8(
       *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)Hq + s * H + h) * D + piece * 8), x);
@@ -888,7 +964,9 @@ extern "C" int kfamd_attn_extend_win_fp8(const void* q, const void* k_codes, con
 // into the caches [B][H][Tcap][D] (strides b, h, t) at rows pos[b] .. pos[b] + T - 1. pos: device
 // int32 [B], not advanced here. Rows at or beyond Tcap are dropped.
 static int kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int Hq, int H,
-                          int D, int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream) {
+                          int D, int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream,
+                          bool ring = false) {
+  if (ring && (Tcap <= 0 || Tcap % kSplitKeys || T > Tcap)) return KFAMD_EINVAL;
   if (!qkv || !k_cache || !v_cache || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 || D <= 0 || D % 8 ||
       Tcap <= 0 || Hq < H || Hq % H || group_log2(Hq / H) < 0)
     return KFAMD_EINVAL;
@@ -897,9 +975,16 @@ static int kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const i
   if ((qb | qt | c[0] | c[1] | c[2] | c[3] | c[4] | c[5]) & 7) return KFAMD_EALIGN;
   const long long n = (long long)B * T * 2 * H * (D / 8);
   if ((n + 255) / 256 > 0x7fffffffll) return KFAMD_EINVAL;
-  hipLaunchKernelGGL(kv_append, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     static_cast<const __bf16*>(qkv), static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos,
-                     B, T, H, D / 8, Tcap, qb, qt, c[0], c[1], c[2], c[3], c[4], c[5], Hq);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (ring)
+    hipLaunchKernelGGL(kv_append<true>, grid, dim3(256), 0, s, static_cast<const __bf16*>(qkv),
+                       static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos, B, T, H, D / 8, Tcap, qb, qt,
+                       c[0], c[1], c[2], c[3], c[4], c[5], Hq);
+  else
+    hipLaunchKernelGGL(kv_append<false>, grid, dim3(256), 0, s, static_cast<const __bf16*>(qkv),
+                       static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos, B, T, H, D / 8, Tcap, qb, qt,
+                       c[0], c[1], c[2], c[3], c[4], c[5], Hq);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
@@ -923,7 +1008,8 @@ extern "C" int kfamd_kv_append_gqa_bf16(const void* qkv, void* k_cache, void* v_
 // cache_strides = {kb, kh, kt, vb, vh, vt, ksb, ksh, vsb, vsh}.
 static int kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale, const int* pos,
                          int B, int T, int Hq, int H, int D, int Tcap, long long qb, long long qt,
-                         const long long* cache_strides, void* stream) {
+                         const long long* cache_strides, void* stream, bool ring = false) {
+  if (ring && (Tcap <= 0 || Tcap % kSplitKeys || T > Tcap)) return KFAMD_EINVAL;
   if (!qkv || !k_codes || !v_codes || !k_scale || !v_scale || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 ||
       Tcap <= 0 || Hq < H || Hq % H || group_log2(Hq / H) < 0)
     return KFAMD_EINVAL;
@@ -940,12 +1026,14 @@ static int kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k
   const __bf16* x = static_cast<const __bf16*>(qkv);
   uint8_t* kc = static_cast<uint8_t*>(k_codes);
   uint8_t* vc = static_cast<uint8_t*>(v_codes);
-  if (D == 64)
-    hipLaunchKernelGGL(kv_append_fp8<64>, grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, qb, qt,
-                       c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq);
-  else
-    hipLaunchKernelGGL(kv_append_fp8<128>, grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, qb,
-                       qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq);
+#define KF_APPEND_FP8(DD, RR)                                                                                         \
+  hipLaunchKernelGGL((kv_append_fp8<DD, RR>), grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, \
+                     qb, qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq)
+  if (D == 64 && ring) KF_APPEND_FP8(64, true);
+  else if (D == 64) KF_APPEND_FP8(64, false);
+  else if (ring) KF_APPEND_FP8(128, true);
+  else KF_APPEND_FP8(128, false);
+#undef KF_APPEND_FP8
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
@@ -963,4 +1051,67 @@ extern "C" int kfamd_kv_append_gqa_fp8(const void* qkv, void* k_codes, void* v_c
   if (Hkv <= 0) return KFAMD_EINVAL;
   return kv_append_fp8(qkv, k_codes, v_codes, k_scale, v_scale, pos, B, T, Hq, Hkv, D, Tcap, qb, qt, cache_strides,
                        stream);
+}
+
+// The ring forms (contract: kfamd_kernels.h; the rule: the docstring of ops/decode.py). The attention entry points take
+// the windowed signatures with the ring's capacity C in t_bound's place; the appends the grouped signatures.
+extern "C" int kfamd_attn_ring_nsplit(int window, int T) {
+  return window >= 1 && T >= 1 ? ring_splits(window, T) : 0;
+}
+
+extern "C" long long kfamd_attn_decode_ring_workspace(int B, int H, int D, int window) {
+  if (window < 1) return 0;
+  return kfamd_attn_decode_workspace(B, H, D, ring_splits(window, 1) * kSplitKeys);
+}
+
+extern "C" long long kfamd_attn_extend_ring_workspace(int B, int Hkv, int G, int D, int T, int window) {
+  if (window < 1 || T < 1) return 0;
+  return kfamd_attn_extend_gqa_workspace(B, Hkv, G, D, T, ring_splits(window, T) * kSplitKeys);
+}
+
+extern "C" int kfamd_attn_decode_ring_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                           void* o, float* lse, void* ws, int B, int H, int D, int cap, int window,
+                                           float scale, const long long* st, void* stream) {
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, H, D, 1, cap, scale, st, false,
+                           stream, 0, window, true);
+}
+
+extern "C" int kfamd_attn_decode_ring_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                          const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                          int H, int D, int cap, int window, float scale, const long long* st,
+                                          void* stream) {
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, H, D, 1, cap, scale, st, false,
+                          stream, 0, window, true);
+}
+
+extern "C" int kfamd_attn_extend_ring_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                           void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T, int cap,
+                                           int window, float scale, const long long* st, void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_kv<Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, cap, scale, st, true,
+                           stream, G, window, true);
+}
+
+extern "C" int kfamd_attn_extend_ring_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                          const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                          int Hkv, int G, int D, int T, int cap, int window, float scale,
+                                          const long long* st, void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_kv<Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, cap, scale, st, true,
+                          stream, G, window, true);
+}
+
+extern "C" int kfamd_kv_append_ring_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T,
+                                         int Hq, int Hkv, int D, int cap, long long qb, long long qt,
+                                         const long long* cache_strides, void* stream) {
+  if (Hkv <= 0) return KFAMD_EINVAL;
+  return kv_append_bf16(qkv, k_cache, v_cache, pos, B, T, Hq, Hkv, D, cap, qb, qt, cache_strides, stream, true);
+}
+
+extern "C" int kfamd_kv_append_ring_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                        const int* pos, int B, int T, int Hq, int Hkv, int D, int cap, long long qb,
+                                        long long qt, const long long* cache_strides, void* stream) {
+  if (Hkv <= 0) return KFAMD_EINVAL;
+  return kv_append_fp8(qkv, k_codes, v_codes, k_scale, v_scale, pos, B, T, Hq, Hkv, D, cap, qb, qt, cache_strides,
+                       stream, true);
 }

@@ -69,6 +69,15 @@
 // <Bf16Rows, 64>, <Bf16Rows, 128>, <Fp8Rows, 64>, <Fp8Rows, 128> plain and 126 / 234 / 185 / 255 grouped, the same LDS,
 // scratch 0. The zero-staging of the rows below the window is in the first tile's stage_write only: in every
 // tile's it spilled <Fp8Rows, 128> (256 VGPRs, 8 - 12 B scratch).
+// RING = true (ring-buffer cache, kfamd_attn_chunk_ring_*; the comment at the kernel), scratch 0 for all:
+//   attn_chunk_split<Bf16Rows, 64, false, true, true>      125   32768
+//   attn_chunk_split<Bf16Rows, 128, false, true, true>     233   65536
+//   attn_chunk_split<Fp8Rows, 64, false, true, true>       184   34304
+//   attn_chunk_split<Fp8Rows, 128, false, true, true>      254   67072
+//   attn_chunk_split<Bf16Rows, 64, true, true, true>       126   32768
+//   attn_chunk_split<Bf16Rows, 128, true, true, true>      234   65536
+//   attn_chunk_split<Fp8Rows, 64, true, true, true>        185   34304
+//   attn_chunk_split<Fp8Rows, 128, true, true, true>       255   67072
 // The grouped limit is no affine function of the row, and with both kept through the key loop
 // <Fp8Rows, 128, true> spilled (256 VGPRs, 8 B scratch): the masked tiles compute the limit again instead.
 #include <hip/hip_runtime.h>
@@ -107,6 +116,7 @@ struct ChunkArgs {
   int lg;  // GQ kernels only: log2 of the group size G. H is then Hkv and Tq the T * G flattened rows
   long long qb, qt, qh, kb, kh, kt, vb, vh, vt, ob, ot, oh, ksb, ksh, vsb, vsh;
   int window;  // WIN kernels only: the sliding window W >= 1
+  int cap;     // RING kernels only: the ring's capacity C, a multiple of kSplitKeys
 };
 
 template <class Vec>
@@ -125,8 +135,18 @@ __device__ __forceinline__ Vec bload8(__amdgpu_buffer_rsrc_t r, int byte_off, in
 // real rows its lowest and highest. The key loop starts at the tile of 64 keys that holds the tile's lowest lower
 // bound blo; keys below blo may be poison and are staged as zeros (P = 0 would not keep a NaN of V out of P.V),
 // keys from blo on are some row's and finite, masked per element by select on the tiles that cross a row's bound.
-template <class Fmt, int D, bool GQ, bool WIN>
+// RING (a ring-buffer cache, the rule: ops/decode.py): key j lives in slot j % C, lens is absolute, and the split
+// partition is rebased at base_b, the 256-aligned split that holds the call's lowest lower bound. C is a multiple of
+// 256, so a 64-key tile is one run of slots: the tile's scalar row offset advances by 64 with a conditional subtract
+// of C. The slice is all C rows, and the slots after key len - 1 hold the oldest live keys, or stale or poisoned rows:
+// the rows of the LAST tile at or beyond len (only the last tile can hold them) must reach LDS as zeros, for K, V and
+// the FP8 scales. That tile is one run of slots that ends inside the slice, so its loads go through descriptors whose
+// range ends at its row len - key0: the address unit returns zeros beyond it, as it does past row len of a flat cache,
+// at the cost of scalar registers only. (A select in stage_write, as for the first tile's rows below blo, spilled
+// <Fp8Rows, 128>: 256 VGPRs, 24 - 32 B scratch.)
+template <class Fmt, int D, bool GQ, bool WIN, bool RING>
 __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
+  static_assert(WIN || !RING, "a ring always has a window");
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
   constexpr int KS = D / 16;               // k-steps of the Q K^T product
@@ -146,10 +166,12 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   const int T = Tq >> lg, Hq = a.H << lg, h0 = h << lg;  // tokens, query heads, the group's first query head
 
   int len = a.lens[b];
-  len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
+  if constexpr (RING) len = max(len, 0);  // absolute, not bounded by the capacity
+  else len = len < 0 ? 0 : (len > a.t_bound ? a.t_bound : len);
   const int q0 = tile * kTileRows, qw = q0 + 32 * w, qrow = qw + r;
   const int qlast = min(q0 + kTileRows, Tq) - 1;  // the tile's last row
-  const int k0 = split * a.split_keys;
+  int k0 = split * a.split_keys;
+  if constexpr (RING) k0 += max(len - T + 1 - a.window, 0) / kSplitKeys * kSplitKeys;  // + base_b
   const int k1 = min(k0 + a.split_keys, len - T + (qlast >> lg) + 1);  // keys of this split that the last row sees: [k0, k1)
   const long long bh = (long long)b * a.H + h;
   const long long nrows = (long long)a.B * a.H * Tq;
@@ -197,13 +219,25 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh;
   const Elem* vbase = static_cast<const Elem*>(a.v) + b * a.vb + h * a.vh;
   const int kt = (int)a.kt, vt = (int)a.vt;
-  const auto rk = slice_rsrc(kbase, (long long)len * kt * ES), rv = slice_rsrc(vbase, (long long)len * vt * ES);
-  const auto rs = slice_rsrc(Fmt::kScaled ? (w == 0 ? a.ks + b * a.ksb + h * a.ksh : a.vs + b * a.vsb + h * a.vsh)
+  const auto rk0 = slice_rsrc(kbase, (long long)len * kt * ES), rv0 = slice_rsrc(vbase, (long long)len * vt * ES);
+  const auto rs0 = slice_rsrc(Fmt::kScaled ? (w == 0 ? a.ks + b * a.ksb + h * a.ksh : a.vs + b * a.vsb + h * a.vsh)
                                           : nullptr,
                              Fmt::kScaled ? 4LL * len : 0);
+  int slot = 0;  // RING: the slot of the next tile staged (block-uniform); tiles are staged in order
   Vec kreg[NCH], vreg[NCH];
   float screg = 0.f;  // Fmt::kScaled: wave 0 carries the tile's 64 K scales, wave 1 its V scales
   auto stage_load = [&](int key0) {
+    auto rk = rk0, rv = rv0, rs = rs0;  // the flat cache's descriptors: their range ends at row len
+    if constexpr (RING) {  // the tile's offsets come from the slot, never from the absolute key index
+      // the slice's rows in range: all C, but for the last tile those below slot + (len - key0)
+      const int rows = key0 + FK > len ? slot + len - key0 : a.cap;
+      rk = slice_rsrc(kbase, (long long)rows * kt * ES), rv = slice_rsrc(vbase, (long long)rows * vt * ES);
+      if constexpr (Fmt::kScaled)
+        rs = slice_rsrc(w == 0 ? a.ks + b * a.ksb + h * a.ksh : a.vs + b * a.vsb + h * a.vsh, 4LL * rows);
+      key0 = slot;
+      slot += FK;
+      if (slot >= a.cap) slot -= a.cap;
+    }
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = tid + kThreads * i, row = c / CH, ch = c % CH;
@@ -251,6 +285,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
 
   // k0 is a multiple of kSplitKeys, so of FK. WIN: the first tile is the one that holds blo
   const int j0 = (WIN ? max(k0, blo) : k0) / FK, j1 = (k1 + FK - 1) / FK;
+  if constexpr (RING) slot = j0 * FK % a.cap;
   stage_load(j0 * FK);
   stage_write(0, WIN ? blo - j0 * FK : 0);
   __syncthreads();
@@ -446,12 +481,18 @@ bool chunk_gqa_ok(int B, int Hkv, int G, int D, int T, int t_bound) {
   return lg >= 0 && T >= 1 && T <= (kMaxRows >> lg) && chunk_shape_ok(B, Hkv, D, T << lg, t_bound);
 }
 
-template <class Fmt, bool WIN>
+template <class Fmt, bool WIN, bool RING>
 void launch_chunk(const ChunkArgs& a, int D, dim3 grid, hipStream_t s) {
-  if (a.lg > 0 && D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true, WIN>), grid, dim3(kThreads), 0, s, a);
-  else if (a.lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true, WIN>), grid, dim3(kThreads), 0, s, a);
-  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false, WIN>), grid, dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false, WIN>), grid, dim3(kThreads), 0, s, a);
+  const dim3 block(kThreads);
+  if (a.lg > 0 && D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true, WIN, RING>), grid, block, 0, s, a);
+  else if (a.lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true, WIN, RING>), grid, block, 0, s, a);
+  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false, WIN, RING>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false, WIN, RING>), grid, block, 0, s, a);
+}
+
+// keys a ring launch partitions: the ceil((W + T - 1) / 256) + 1 splits of 256 from base_b on (attn_kv.hip's count)
+int ring_span(int window, int T) {
+  return (int)((((long long)window + T - 1 + kSplitKeys - 1) / kSplitKeys + 1) * kSplitKeys);
 }
 
 // The launcher behind kfamd_attn_chunk_bf16 / _fp8. window: 0 for the entry points without one, else W >= 1. st: q (b, t, h), k (b, h, t), v (b, h, t), o (b, t, h),
@@ -462,7 +503,12 @@ void launch_chunk(const ChunkArgs& a, int D, dim3 grid, hipStream_t s) {
 template <class Fmt>
 int attn_chunk(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens,
                void* o, float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
-               const long long* st, void* stream, int G = 0, int window = 0) {
+               const long long* st, void* stream, int G = 0, int window = 0, bool ring = false) {
+  // ring: t_bound is the capacity C (the limit checks below then bound the slice of C rows), and the split count and
+  // the keys per split come from the span of W and T, never from a position
+  if (ring && (window < 1 || t_bound < 1 || t_bound % kSplitKeys || Tq < 1 || (long long)window + Tq - 1 > t_bound))
+    return KFAMD_EINVAL;
+  const int span = ring ? ring_span(window, Tq) : t_bound;
   if (window < 0 || (G > 0 && !chunk_gqa_ok(B, H, G, D, Tq, t_bound))) return KFAMD_EINVAL;
   const int lg = G > 0 ? kfkv::group_log2(G) : 0;
   Tq <<= lg;  // rows per (b, K / V head) from here on
@@ -476,7 +522,7 @@ int attn_chunk(const void* q, const void* k, const void* v, const float* ks, con
   if (a.kt < D || a.vt < D) return KFAMD_EINVAL;
   const long long lim = (1ll << 31) / (long long)sizeof(typename Fmt::Elem);  // a (b, h) slice stays below 2^31 bytes
   if ((long long)t_bound * a.kt >= lim || (long long)t_bound * a.vt >= lim) return KFAMD_EINVAL;
-  a.nsplit = chunk_nsplit(B, H, Tq, t_bound);
+  a.nsplit = chunk_nsplit(B, H, Tq, span);
   const long long wgs = (long long)chunk_tiles(Tq) * a.nsplit;
   if (wgs > 0x7fffffffll || (a.nsplit > 1 && !ws)) return KFAMD_EINVAL;
   if (!kfkv::al16(q) || !kfkv::al16(k) || !kfkv::al16(v) || !kfkv::al16(o) || (ws && !kfkv::al16(ws)))
@@ -490,14 +536,16 @@ int attn_chunk(const void* q, const void* k, const void* v, const float* ks, con
   a.lse = lse;
   a.ws = static_cast<float*>(ws);
   a.B = B, a.H = H, a.Tq = Tq, a.t_bound = t_bound, a.lg = lg;
-  a.window = window >= t_bound ? 0 : window;  // W >= t_bound removes no key: the kernels without a window
-  const int chunks = (t_bound + kSplitKeys - 1) / kSplitKeys;
+  a.window = ring ? window : window >= t_bound ? 0 : window;  // W >= t_bound removes no key: the kernels without a window
+  a.cap = ring ? t_bound : 0;
+  const int chunks = (span + kSplitKeys - 1) / kSplitKeys;
   a.split_keys = (chunks + a.nsplit - 1) / a.nsplit * kSplitKeys;
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)wgs, (unsigned)H, (unsigned)B);
-  if (a.window > 0) launch_chunk<Fmt, true>(a, D, grid, s);
-  else launch_chunk<Fmt, false>(a, D, grid, s);
+  if (ring) launch_chunk<Fmt, true, true>(a, D, grid, s);
+  else if (a.window > 0) launch_chunk<Fmt, true, false>(a, D, grid, s);
+  else launch_chunk<Fmt, false, false>(a, D, grid, s);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && a.nsplit > 1)
     e = kfkv::launch_kv_combine(D, a.ws, a.o, lse, B, H, Tq, a.nsplit, a.ob, a.ot, a.oh, s, lg);
@@ -575,4 +623,32 @@ extern "C" int kfamd_attn_chunk_win_fp8(const void* q, const void* k_codes, cons
   if (G <= 0 || window < 1) return KFAMD_EINVAL;
   return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound,
                                    scale, st, stream, G, window);
+}
+
+// The ring forms (contract: kfamd_kernels.h): the windowed signatures with the ring's capacity C in t_bound's place.
+extern "C" int kfamd_attn_chunk_ring_nsplit(int B, int Hkv, int G, int T, int window) {
+  if (window < 1 || T < 1) return 0;
+  return kfamd_attn_chunk_gqa_nsplit(B, Hkv, G, T, ring_span(window, T));
+}
+
+extern "C" long long kfamd_attn_chunk_ring_workspace(int B, int Hkv, int G, int D, int T, int window) {
+  if (window < 1 || T < 1) return 0;
+  return kfamd_attn_chunk_gqa_workspace(B, Hkv, G, D, T, ring_span(window, T));
+}
+
+extern "C" int kfamd_attn_chunk_ring_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens,
+                                          void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T, int cap,
+                                          int window, float scale, const long long* st, void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Bf16Rows>(q, k_cache, v_cache, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, cap, scale,
+                                    st, stream, G, window, true);
+}
+
+extern "C" int kfamd_attn_chunk_ring_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                                         const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                         int Hkv, int G, int D, int T, int cap, int window, float scale,
+                                         const long long* st, void* stream) {
+  if (G <= 0) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, cap, scale,
+                                   st, stream, G, window, true);
 }

@@ -403,6 +403,60 @@ int kfamd_attn_chunk_win_fp8(const void* q, const void* k_codes, const void* v_c
                              int G, int D, int T, int t_bound, int window, float scale, const long long* strides,
                              void* stream);
 
+// ---- ring-buffer KV cache (attn_kv.hip, attn_kv_mfma.hip, rope_bf16.hip) -------------------------------
+// The rule is stated once, in the docstring of kubeflow_rm_amd/ops/decode.py. A ring of capacity cap (a positive
+// multiple of 256, KFAMD_EINVAL otherwise) holds key j in slot j % cap, for K, V and the FP8 scales; lens[b] is the
+// absolute length and is not bounded by cap; the live keys of row b are max(0, lens[b] - cap) <= j < lens[b].
+// Attention: the windowed entry points' signatures with cap in t_bound's place; window >= 1 and
+// window + T - 1 <= cap (T = 1 for decode), KFAMD_EINVAL otherwise. The window rule is unchanged. The grid depends on
+// (window, T, G, B, H) only: kfamd_attn_ring_nsplit(window, T) = ceil((window + T - 1) / 256) + 1 splits of 256 keys
+// (VALU forms) from base_b = (max(lens[b] - T + 1 - window, 0) / 256) * 256 on, rebased per batch row on the device;
+// the MFMA form applies its nsplit / split_keys rule to that span (kfamd_attn_chunk_ring_nsplit). The *_ring_workspace
+// functions give the bytes of ws for those counts (layouts as for the flat forms). Slots outside every row's window,
+// the ones after key lens[b] - 1 included, may hold NaN / 0x7F codes and NaN scales. Positions up to 2^24 are covered.
+// Appends: the grouped signatures; position lens[b] + t goes to slot (lens[b] + t) % cap, never dropped; T <= cap.
+// The rotary form rotates by the absolute position: the table needs max_pos > the largest lens[b] + T - 1 (the
+// caller's check; a position at or beyond max_pos is neither rotated nor stored).
+// VGPRs of the RING instantiations (scratch 0 for all): see the tables in attn_kv.hip and attn_kv_mfma.hip.
+int kfamd_attn_ring_nsplit(int window, int T);
+long long kfamd_attn_decode_ring_workspace(int B, int H, int D, int window);
+long long kfamd_attn_extend_ring_workspace(int B, int Hkv, int G, int D, int T, int window);
+int kfamd_attn_chunk_ring_nsplit(int B, int Hkv, int G, int T, int window);
+long long kfamd_attn_chunk_ring_workspace(int B, int Hkv, int G, int D, int T, int window);
+int kfamd_attn_decode_ring_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                                float* lse, void* ws, int B, int H, int D, int cap, int window, float scale,
+                                const long long* strides, void* stream);
+int kfamd_attn_decode_ring_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                               const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H, int D,
+                               int cap, int window, float scale, const long long* strides, void* stream);
+int kfamd_attn_extend_ring_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                                float* lse, void* ws, int B, int Hkv, int G, int D, int T, int cap, int window,
+                                float scale, const long long* strides, void* stream);
+int kfamd_attn_extend_ring_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                               const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                               int G, int D, int T, int cap, int window, float scale, const long long* strides,
+                               void* stream);
+int kfamd_attn_chunk_ring_bf16(const void* q, const void* k_cache, const void* v_cache, const int* lens, void* o,
+                               float* lse, void* ws, int B, int Hkv, int G, int D, int T, int cap, int window,
+                               float scale, const long long* strides, void* stream);
+int kfamd_attn_chunk_ring_fp8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale,
+                              const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                              int G, int D, int T, int cap, int window, float scale, const long long* strides,
+                              void* stream);
+int kfamd_kv_append_ring_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int Hq,
+                              int Hkv, int D, int cap, long long qb, long long qt, const long long* cache_strides,
+                              void* stream);
+int kfamd_kv_append_ring_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                             const int* pos, int B, int T, int Hq, int Hkv, int D, int cap, long long qb, long long qt,
+                             const long long* cache_strides, void* stream);
+int kfamd_kv_append_rope_ring_bf16(void* qkv, void* k_cache, void* v_cache, const int* lens, const float* table,
+                                   int max_pos, int B, int T, int Hq, int Hkv, int D, int cap, long long qb,
+                                   long long qt, const long long* cache_strides, void* stream);
+int kfamd_kv_append_rope_ring_fp8(void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                  const int* lens, const float* table, int max_pos, int B, int T, int Hq, int Hkv,
+                                  int D, int cap, long long qb, long long qt, const long long* cache_strides,
+                                  void* stream);
+
 // ---- rotary position embeddings (rope_bf16.hip)-----------------------------------------------------
 // table: fp32 [max_pos][D] contiguous, row p = cos(p f_i) | sin(p f_i), i < D/2 (built on the host). The
 // rotation is rotate-half: y[i] = x[i] c - x[i + D/2] s, y[i + D/2] = x[i + D/2] c + x[i] s, in fp32 without

@@ -61,10 +61,17 @@ Sliding-window attention: ``GPTConfig(window=W)`` gives every layer a local caus
 sampler, ``prefill_chunk`` and ``draft=``, which may have its own window or none, compose by shapes only). ``prefill``
 on the GPU cannot use the flash kernel, which has no window: it runs the prompt over the cache on
 ``ops.attention_chunk`` in one step (its docstring). The training ``forward`` applies the mask on the torch path (CPU,
-``ops.torch_reference()``) and raises ``NotImplementedError`` on the native GPU path. ``KVCache`` still holds every
-position. ``window=None`` (the default) is the model as it was: same launches, same bits. Not built: a window in the
-flash forward / backward kernels (native GPU training of a windowed model), per-layer windows, attention sinks, a
-ring-buffer cache of capacity W, and a launch grid shrunk from a host-side lower bound.
+``ops.torch_reference()``) and raises ``NotImplementedError`` on the native GPU path. A flat ``KVCache`` still holds
+every position (the ring below does not). ``window=None`` (the default) is the model as it was: same launches, same
+bits. Not built: a window in the flash forward / backward kernels (native GPU training of a windowed model), per-layer
+windows, attention sinks.
+
+Ring-buffer cache: ``new_cache(..., ring=True)`` / ``generate(..., ring=True)`` of a windowed model keep the last
+``capacity`` positions only (``ops/decode.py``'s ring rule): the cache's memory is O(window), the positions run to
+``max_seq``, and ``decode_step``, ``extend``, ``extend(chunk=N)`` and the graphed steps run on it with a launch grid that
+depends on the window and the step's token count alone (no ``pin_bound``). A step of T tokens needs ``window + T - 1 <=
+capacity``. Not built: a ring without a window, a capacity that is no multiple of 256, tensor-parallel sharding of a
+ring.
 """
 from __future__ import annotations
 
@@ -407,13 +414,14 @@ class _GraphedDecodeStep:
     host-side bound of ``decode_step`` are kept here (``cache.lens`` may never pass the capacity: the
     position embedding is gathered by it)."""
 
-    def __init__(self, graphed, cache):
+    def __init__(self, graphed, cache, limit: int | None = None):
         self.graphed, self.cache = graphed, cache
+        self.limit = cache.capacity if limit is None else limit  # a ring cache: the model's max_seq
 
     def __call__(self, tok: torch.Tensor) -> torch.Tensor:
         c = self.cache
-        if c._bound + 1 > c.capacity:
-            raise ValueError(f"cache capacity {c.capacity} exceeded")
+        if c._bound + 1 > self.limit:
+            raise ValueError(f"max_seq {self.limit} exceeded" if c.ring else f"cache capacity {c.capacity} exceeded")
         out = self.graphed(tok)
         c._bound += 1
         return out
@@ -424,13 +432,14 @@ class _GraphedGenerateStep:
     ``replay()`` per generated token and no other host work. As in ``_GraphedDecodeStep`` the capacity check
     and the host-side bound of ``decode_step`` are kept here."""
 
-    def __init__(self, graphed, cache, keep):
+    def __init__(self, graphed, cache, keep, limit: int | None = None):
         self.graphed, self.cache, self._keep = graphed, cache, keep  # the captured kernels read `keep`
+        self.limit = cache.capacity if limit is None else limit  # a ring cache: the model's max_seq
 
     def replay(self) -> None:
         c = self.cache
-        if c._bound + 1 > c.capacity:
-            raise ValueError(f"cache capacity {c.capacity} exceeded")
+        if c._bound + 1 > self.limit:
+            raise ValueError(f"max_seq {self.limit} exceeded" if c.ring else f"cache capacity {c.capacity} exceeded")
         self.graphed.graph.replay()
         c._bound += 1
 
@@ -476,16 +485,23 @@ class GPT(torch.nn.Module):
     # prefill(), decode_step() and extend()'s _extend_chunk() keep the embedding, the positions and cache.advance;
     # the layer itself is _cache_layer() and the LM head _lm_head(), each written once per path.
 
-    def new_cache(self, B: int, capacity: int, device=None, kv_dtype: torch.dtype | None = None) -> "ops.KVCache":
+    def new_cache(self, B: int, capacity: int, device=None, kv_dtype: torch.dtype | None = None,
+                  ring: bool = False) -> "ops.KVCache":
         """A cache for B sequences of up to ``capacity`` tokens. ``kv_dtype``: what the cache stores;
         ``None`` is the model's dtype, ``torch.float8_e4m3fn`` the 8-bit cache (codes plus one fp32 scale
-        per row: about half the bytes, see ``KVCache.nbytes``)."""
+        per row: about half the bytes, see ``KVCache.nbytes``). ``ring=True`` (a windowed model only): a ring buffer of
+        the last ``capacity`` positions (``ops/decode.py``'s ring rule): ``capacity`` is a multiple of 256 and need
+        neither exceed the window nor reach ``max_seq``; a step of T tokens needs ``window + T - 1 <= capacity``, and
+        the positions stay bounded by ``max_seq`` (the position or rotary table)."""
         c = self.cfg
-        if capacity > c.max_seq:
+        if ring and c.window is None:
+            raise ValueError("new_cache(ring=True): a ring cache needs a windowed model (GPTConfig(window=W))")
+        if not ring and capacity > c.max_seq:
             raise ValueError(f"cache capacity {capacity} exceeds max_seq {c.max_seq}")
         return ops.KVCache(c.n_layers, B, self.blocks[0].local_kv_heads, c.head_dim, capacity,
                            device=device if device is not None else self.tok.device,
-                           dtype=kv_dtype if kv_dtype is not None else c.dtype)
+                           dtype=kv_dtype if kv_dtype is not None else c.dtype,
+                           **({"ring": True, "window": c.window} if ring else {}))
 
     def _native_decode(self, x: torch.Tensor) -> bool:
         # both paths read the sharded weights without the TP layers' all-reduces: refuse, on any device
@@ -498,11 +514,27 @@ class GPT(torch.nn.Module):
                              f"got {self.cfg.dtype}, head dim {self.cfg.head_dim}")
         return True
 
-    def _check_cache(self, cache, B: int, T: int) -> None:
+    def _check_cache(self, cache, B: int, T: int, step: int | None = None) -> None:
+        """``T`` new tokens fit; ``step``: the tokens per attention call when the T run in several steps."""
         if cache.B != B or cache.n_layers != len(self.blocks):
             raise ValueError("cache does not match the batch / model")
-        if cache._bound + T > cache.capacity:
+        if cache.ring:  # positions are bounded by the tables, a step by the ring rule
+            W, n = self.cfg.window, min(T, step or T)
+            if W is None:
+                raise ValueError("a ring cache needs a windowed model (GPTConfig(window=W))")
+            if cache._bound + T > self.cfg.max_seq:
+                raise ValueError(f"max_seq {self.cfg.max_seq} exceeded")
+            if W + n - 1 > cache.capacity:
+                raise ValueError(f"a step of {n} tokens with window {W} needs a ring of capacity >= {W + n - 1}, got "
+                                 f"{cache.capacity}")
+        elif cache._bound + T > cache.capacity:
             raise ValueError(f"cache capacity {cache.capacity} exceeded")
+
+    @staticmethod
+    def _att(cache, T: int, window) -> dict:
+        """What a step of T appended tokens hands to its attention: the lengths including them, the host bound that
+        goes with them (none on a ring: its grid does not come from it) and the window."""
+        return {"lens": cache.lens_after(T), "t_bound": None if cache.ring else cache.bound_after(T), "window": window}
 
     def _cache_layer(self, blk, li: int, x, cache, *, native: bool, lin, w, attend):
         """One layer against ``cache``, the body ``prefill``, ``decode_step`` and ``_extend_chunk`` share. They vary
@@ -544,6 +576,9 @@ class GPT(torch.nn.Module):
         QUANTISED rows, as ``prefill_chunk`` does, and the logits are no longer those of a bf16 cache. On the torch
         path (CPU, ``ops.torch_reference()``) the prompt's attention stays on the activation, under the windowed mask."""
         B, T = idx.shape
+        if cache.ring and self.cfg.window is not None and self.cfg.window + T - 1 > cache.capacity:
+            raise ValueError(f"prefill: a prompt of {T} tokens with window {self.cfg.window} needs a ring of capacity >= "
+                             f"{self.cfg.window + T - 1}, got {cache.capacity}: run it in steps with extend(chunk=N)")
         self._check_cache(cache, B, T)
         if cache._bound != 0:
             raise ValueError("prefill expects an empty cache (continuing a cache takes decode_step)")
@@ -680,7 +715,7 @@ class GPT(torch.nn.Module):
         if self.pos is not None:
             x = x + F.embedding(cache.lens, self.pos)
         # the step's attention sees the row it appends: lens + 1, computed on the device
-        att = {"lens": cache.lens_after(1), "t_bound": cache.bound_after(1), "window": self.cfg.window}
+        att = self._att(cache, 1, self.cfg.window)
 
         def attend(li, qkv, native):
             q = qkv[:, :h * hd].view(B, h, hd)
@@ -723,7 +758,8 @@ class GPT(torch.nn.Module):
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError(f"extend: idx [B, T >= 1] expected, got {tuple(idx.shape)}")
         B, T = idx.shape
-        self._check_cache(cache, B, T)
+        if not cache.ring:
+            self._check_cache(cache, B, T)
         native = self._native_decode(self.tok)
         R = ops.decode.MAX_EXTEND_ROWS
         if chunk is None and native:  # the kernel takes 16 ROWS per K / V head: 16 // G tokens of a grouped-query model
@@ -733,6 +769,8 @@ class GPT(torch.nn.Module):
                 raise ValueError(f"extend(chunk=...): an int in {R + 1} .. the cache's capacity ({cache.capacity}) "
                                  f"expected, got {chunk!r}")
             R = chunk
+        if cache.ring:  # the ring rule bounds a step, not the whole input
+            self._check_cache(cache, B, T, step=R)
         outs = []
         for t0 in range(0, T, R):
             final = t0 + R >= T
@@ -756,7 +794,7 @@ class GPT(torch.nn.Module):
             pos = cache.lens.unsqueeze(1) + torch.arange(T, device=idx.device, dtype=cache.lens.dtype)  # [B, T], device
             x = x + F.embedding(pos, self.pos)
         # the step's attention sees the rows it appends: lens + T, computed on the device
-        att = {"lens": cache.lens_after(T), "t_bound": cache.bound_after(T), "window": c.window}
+        att = self._att(cache, T, c.window)
         lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
         wsel = self._weight_selector(weights, B * T)
 
@@ -784,19 +822,32 @@ class GPT(torch.nn.Module):
             return self._lm_head(x, head_w, head_lin, False)
         return self._lm_head(x.reshape(rows, c.d_model), head_w, head_lin, True).view(*x.shape[:-1], c.vocab_size)
 
+    def _ring_capacity(self, step: int) -> int:
+        """The capacity ``generate(ring=True)`` gives a ring whose largest step is ``step`` tokens: ``window + step - 1``
+        rounded up to a multiple of 256."""
+        return -(-(self.cfg.window + step - 1) // ops.decode.RING_ALIGN) * ops.decode.RING_ALIGN
+
     def _generate_draft(self, idx, max_new_tokens: int, draft: "GPT", lookahead: int, kv_dtype=None, tw=None,
-                        dw=None):
+                        dw=None, ring_chunk: int | None = None):
         """Greedy draft-and-verify for one sequence: per round the draft proposes up to ``lookahead``
         tokens (``decode_step`` on its own cache), the target scores ``[last accepted, proposals...]`` in
         ONE ``extend`` and keeps the longest prefix that equals its own argmax, plus its own next token
         (the correction at the first mismatch, or the extra token after a full acceptance)."""
         T0 = idx.shape[1]
         total = T0 + max_new_tokens
-        tc = self.new_cache(1, total, device=idx.device, kv_dtype=kv_dtype)
-        dc = draft.new_cache(1, total, device=idx.device, kv_dtype=kv_dtype)
-        if T0 > 1:  # both caches hold the prompt but its last token: every new token comes from a round
-            self.prefill(idx[:, :-1], tc)
-            draft.prefill(idx[:, :-1], dc)
+        def cache_and_prompt(m):  # ring_chunk=N: a ring where the model has a window, its prompt in steps of N
+            if ring_chunk is None or m.cfg.window is None:
+                c = m.new_cache(1, total, device=idx.device, kv_dtype=kv_dtype)
+                if T0 > 1:
+                    m.prefill(idx[:, :-1], c)
+                return c
+            c = m.new_cache(1, m._ring_capacity(max(ring_chunk, 16, lookahead + 1)), device=idx.device,
+                            kv_dtype=kv_dtype, ring=True)
+            if T0 > 1:
+                m.extend(idx[:, :-1], c, last_only=True, chunk=ring_chunk)
+            return c
+        # both caches hold the prompt but its last token: every new token comes from a round
+        tc, dc = cache_and_prompt(self), cache_and_prompt(draft)
         seq = idx[0].tolist()
         stats = {"target_steps": 0, "proposed": 0, "accepted": 0}
         while len(seq) < total:
@@ -828,7 +879,7 @@ class GPT(torch.nn.Module):
                  generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
                  lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None,
                  weight_dtype: torch.dtype | None = None, top_p: float | None = None, stop_token: int | None = None,
-                 sampler: str = "torch", prefill_chunk: int | None = None):
+                 sampler: str = "torch", prefill_chunk: int | None = None, ring: bool = False):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -863,8 +914,20 @@ class GPT(torch.nn.Module):
         ``ops.attention_chunk``, so the prompt's activation memory is bounded by N rows whatever its length.
         Each step attends the cache, not the QKV activation: with ``kv_dtype=torch.float8_e4m3fn`` the prompt
         then attends the QUANTISED K / V it has stored, where ``prefill`` attends the unquantised rows, so the
-        logits differ from a bf16 cache's from the first token on. It raises with ``draft``."""
-        if prefill_chunk is not None and draft is not None:
+        logits differ from a bf16 cache's from the first token on. It raises with ``draft`` (unless ``ring``).
+
+        ``ring=True`` (a windowed model: it raises without ``GPTConfig(window=W)``): the cache is a ring buffer
+        (``new_cache(ring=True)``), so the memory is O(window) whatever ``max_new_tokens`` is. The prompt runs through
+        ``prefill_chunk=N`` (default 256) on every device, and the capacity is ``W + max(N, 16, lookahead + 1) - 1``
+        rounded up to a multiple of 256. With ``draft=`` the target's cache is a ring, and the draft's is one iff the
+        draft has a window. It composes with ``kv_dtype``, ``weight_dtype``, ``sampler="fused"``, ``graph=True``, grouped
+        K / V heads and ``pos="rope"`` by shapes only."""
+        if ring:
+            if self.cfg.window is None:
+                raise ValueError("generate(ring=True) needs a windowed model (GPTConfig(window=W))")
+            if prefill_chunk is None:
+                prefill_chunk = 256
+        if prefill_chunk is not None and draft is not None and not ring:
             raise ValueError("generate(prefill_chunk=...) cannot be combined with draft=")
         if sampler not in ("torch", "fused"):
             raise ValueError(f'generate(sampler=...): "torch" or "fused" expected, got {sampler!r}')
@@ -889,7 +952,8 @@ class GPT(torch.nn.Module):
             out, stats = ((idx.clone(), {"target_steps": 0, "proposed": 0, "accepted": 0}) if max_new_tokens == 0
                           else self._generate_draft(idx, max_new_tokens, draft, int(lookahead), kv_dtype,
                                                     self.decode_weights() if weight_dtype is not None else None,
-                                                    draft.decode_weights() if weight_dtype is not None else None))
+                                                    draft.decode_weights() if weight_dtype is not None else None,
+                                                    prefill_chunk if ring else None))
             return (out, stats) if return_stats else out
         if return_stats:
             raise ValueError("generate(return_stats=True) reports draft decoding: pass draft=")
@@ -897,7 +961,11 @@ class GPT(torch.nn.Module):
             return idx.clone()
         if graph and not idx.is_cuda:
             raise ValueError("generate(graph=True) needs GPU tensors")
-        cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
+        if ring:
+            cache = self.new_cache(B, self._ring_capacity(max(prefill_chunk, 16, lookahead + 1)), device=idx.device,
+                                   kv_dtype=kv_dtype, ring=True)
+        else:
+            cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
         if prefill_chunk is None:
             logits = self.prefill(idx, cache)
         else:  # the bf16 weights, as prefill: a prompt is not a decode step
@@ -957,9 +1025,11 @@ class GPT(torch.nn.Module):
         ``decode_step``). The cache needs one free row, and ``step`` one free row of ``u``, for the warm-up
         step, whose effects (``lens``, ``step``, ``tok``, ``seq``, ``done``) are undone here. The graph holds the
         tensors' addresses: the returned object keeps them (and ``weights``) alive."""
-        if cache._bound + 1 > cache.capacity:
+        limit = self.cfg.max_seq if cache.ring else cache.capacity
+        if cache._bound + 1 > limit:
             raise ValueError("graphed_generate_step needs a free cache row")
-        cache.pin_bound()
+        if not cache.ring:  # a ring's grid does not come from the bound
+            cache.pin_bound()
         bound = cache._bound
         state = [t for t in (cache.lens, step, tok, seq, done) if t is not None]
         saved = [t.clone() for t in state]
@@ -975,7 +1045,7 @@ class GPT(torch.nn.Module):
         for t, s0 in zip(state, saved):
             t.copy_(s0)
         cache._bound = bound
-        return _GraphedGenerateStep(g, cache, (weights, u, step, tok, seq, done))
+        return _GraphedGenerateStep(g, cache, (weights, u, step, tok, seq, done), limit)
 
     def graphed_decode_step(self, cache, weights: "DecodeWeights | None" = None) -> "_GraphedDecodeStep":
         """``decode_step`` on ``cache`` captured once into a hipGraph (its attention grid sized for the
@@ -984,9 +1054,11 @@ class GPT(torch.nn.Module):
         the host-side bound follows, and a call with no free cache row raises like ``decode_step``. The
         cache needs one free row for the warm-up step, whose effect on ``lens`` is undone here. ``weights``: as
         ``decode_step``; the graph holds the quantised tensors' addresses, so keep the object alive."""
-        if cache._bound + 1 > cache.capacity:
+        limit = self.cfg.max_seq if cache.ring else cache.capacity
+        if cache._bound + 1 > limit:
             raise ValueError("graphed_decode_step needs a free cache row")
-        cache.pin_bound()
+        if not cache.ring:  # a ring's grid does not come from the bound
+            cache.pin_bound()
         saved, bound = cache.lens.clone(), cache._bound
 
         def step(t):  # warm-up and capture both start from the same host bound
@@ -997,7 +1069,7 @@ class GPT(torch.nn.Module):
         torch.cuda.current_stream().synchronize()
         cache.lens.copy_(saved)
         cache._bound = bound
-        gs = _GraphedDecodeStep(g, cache)
+        gs = _GraphedDecodeStep(g, cache, limit)
         gs.weights = weights  # the captured kernels read these tensors: they live as long as the step
         return gs
 

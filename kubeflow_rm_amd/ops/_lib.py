@@ -144,6 +144,32 @@ _SIGNATURES = {
                                           c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_attn_chunk_win_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                          c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    # the ring-buffer forms: the windowed signatures with the capacity in t_bound's place; grouped appends
+    "kfamd_attn_ring_nsplit": (c_int, [c_int, c_int]),
+    "kfamd_attn_decode_ring_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
+    "kfamd_attn_extend_ring_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_chunk_ring_nsplit": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_chunk_ring_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "kfamd_attn_decode_ring_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                            c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_decode_ring_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                           c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_ring_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_extend_ring_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                           c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_ring_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_chunk_ring_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_int, c_float, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_ring_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
+                                          ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_ring_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_rope_ring_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_int, c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_kv_append_rope_ring_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                              c_int, c_int, c_int, c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
                                          ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -64,7 +64,33 @@ cache rows outside every row's window may hold NaN (bf16) or ``0x7F`` codes and 
 still comes from ``t_bound`` (``lens`` stays on the device, the step stays capturable); workgroups whose keys all lie
 below the window write the empty split record and load nothing, so the K / V stream is bounded by about ``W`` keys
 per row block whatever the position. ``W >= t_bound`` can remove no key and launches the kernels without a window.
-The routing between the VALU and MFMA forms does not depend on the window. ``KVCache`` still holds every position.
+The routing between the VALU and MFMA forms does not depend on the window. A flat ``KVCache`` still holds every position.
+
+Ring-buffer cache: ``KVCache(..., ring=True)`` holds the last ``capacity`` positions of every row, so a windowed
+sequence runs in O(window) memory and to any position. THE RING RULE (the kernels and the references point here):
+``capacity`` (``C``) is a positive multiple of ``SPLIT_KEYS`` (256; anything else raises ``ValueError``); ``lens[b]`` is
+the ABSOLUTE number of tokens of row ``b`` and is not bounded by ``C``; key ``j`` lives in slot ``j % C``, for K, V and
+the FP8 scales alike; the live keys of row ``b`` are ``max(0, lens[b] - C) <= j < lens[b]``, and anything else a slot
+might stand for is gone. ``kv_append`` writes position ``lens[b] + t`` to slot ``(lens[b] + t) % C`` and never drops a
+row; it needs ``T <= C``; ``rope=table`` rotates by the absolute position, so the table needs ``_bound + T`` rows (not
+``capacity``), and the FP8 append still stores exactly ``quantize_rows`` of the (rotated) row. The three attention ops
+on a ring require ``window=W`` and ``W + T - 1 <= C`` (``T`` new tokens of the call, 1 for ``attention_decode``), on
+every path; either failing raises ``ValueError`` naming both numbers. That condition is the whole safety argument: a
+step that appends positions ``L .. L+T-1`` overwrites positions ``L-C .. L+T-1-C``, row 0 of the step sees keys down to
+``L + 1 - W``, so nothing seen is overwritten iff ``C >= W + T - 1``. The window rule itself is unchanged. An explicit
+``t_bound=`` raises: the grid of a ring launch is a function of ``(W, T, G, B, H)`` only, never of the position. The
+kernels keep the absolute 256-aligned split partition and rebase it per batch row on the device at ``base_b =
+(max(lens[b] - T + 1 - W, 0) // 256) * 256`` (``lens[b]`` including the new rows): split ``s`` covers absolute keys from
+``base_b + 256 s``, and ``ceil((W + T - 1) / 256) + 1`` splits always suffice; the MFMA form applies its ``nsplit`` /
+``split_keys`` formula to that span. Every split and every 64-key tile is one contiguous run of slots, so no kernel
+takes a modulo per key. A captured step needs no ``pin_bound()`` and carries no empty splits from the position.
+``set_lens`` accepts any lengths ``>= 0`` (the slots are taken to hold the last ``C`` positions before each length),
+``advance`` does not clamp, ``rewind(n)`` raises for ``n > C - W + 1`` (``W``: the ``window=`` the cache was built with,
+as ``GPT.new_cache`` does; 1 without it, the widest limit any window allows), where the needed keys are certainly gone,
+and is valid for ``n <= T`` of the step before it (draft-and-verify). ``t_bound`` / ``bound_after`` / ``pin_bound`` keep working for callers that read
+them; nothing on the ring path depends on them. The torch path gathers the live slots into absolute order and applies
+the masked softmax above. Positions up to 2^24 are covered. ``ring=False`` is the cache as it was: same launches, same
+bits. Not built: a ring without a window, a capacity that is no multiple of 256.
 """
 from __future__ import annotations
 
@@ -88,6 +114,7 @@ GROUP_SIZES = (1, 2, 4, 8, 16)  # query heads per K / V head the kernels take
 # bf16 and FP8): at 8 rows the MFMA form is 1.5 - 2.0x faster, at 16 rows 2.5 - 3.7x, every case beyond the
 # blocks' spread; below 8 rows the forms were not compared and the VALU form stays.
 GQA_MFMA_MIN_ROWS: int | None = 8
+RING_ALIGN = 256  # a ring's capacity is a multiple of the kernels' SPLIT_KEYS (a constant: importing needs no library)
 
 
 def _gqa_mfma(T: int, G: int) -> bool:
@@ -170,12 +197,20 @@ class KVCache:
     number of K / V heads: a grouped-query model's cache holds ``n_kv_heads`` and the attention functions take a
     ``q`` of ``G * H`` heads.
     ``dtype=torch.float8_e4m3fn``: ``k`` / ``v`` hold codes and ``k_scale`` / ``v_scale`` ``[B, H, capacity]``
-    fp32 the per-row scales (``None`` for every other dtype)."""
+    fp32 the per-row scales (``None`` for every other dtype).
+    ``ring=True``: a ring buffer of the last ``capacity`` positions (the module docstring's ring rule): ``capacity`` a
+    multiple of 256, ``lens`` absolute and unbounded, key ``j`` in slot ``j % capacity``. ``window``: optional, the
+    window the cache will be attended with: only ``rewind`` reads it, for its limit ``capacity - window + 1`` (without
+    it the limit is ``capacity``, what a window of 1 allows). No call changes it."""
 
     def __init__(self, n_layers: int, B: int, H: int, D: int, capacity: int, device=None,
-                 dtype: torch.dtype = torch.bfloat16):
+                 dtype: torch.dtype = torch.bfloat16, ring: bool = False, window: int | None = None):
         if min(n_layers, B, H, D, capacity) < 1:
             raise ValueError("KVCache: positive sizes expected")
+        if ring and capacity % RING_ALIGN:
+            raise ValueError(f"KVCache(ring=True): the capacity must be a multiple of {RING_ALIGN}, got {capacity}")
+        self.ring = bool(ring)
+        self.window = _check_window("KVCache", window) if ring else None
         self.n_layers, self.B, self.H, self.D, self.capacity = n_layers, B, H, D, capacity
         self.device, self.dtype = torch.device(device if device is not None else "cpu"), dtype
         self.k = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
@@ -190,6 +225,8 @@ class KVCache:
         self.workspace = None
         self.extend_workspace = None  # attention_extend's, allocated on its first use
         self.chunk_workspace = None  # attention_chunk's, allocated on its first use, grown when a call needs more
+        if self.ring:  # the ring's workspaces follow the window: all three are allocated on first use
+            return
         if self.device.type == "cuda" and dtype in CACHE_DTYPES and D in HEAD_DIMS:  # the kernels' shapes
             nbytes = _lib.lib().kfamd_attn_decode_workspace(B, H, D, capacity)
             self.workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
@@ -209,7 +246,7 @@ class KVCache:
     @property
     def t_bound(self) -> int:
         """Host-side upper bound of every ``lens[b]`` (sizes the attention grid)."""
-        return self.capacity if self._pinned else self._bound
+        return self.capacity if self._pinned else min(self._bound, self.capacity)
 
     def lens_after(self, T: int = 1) -> torch.Tensor:
         """``lens + T`` on the device (one buffer per cache, capturable): the lengths a step that
@@ -223,12 +260,15 @@ class KVCache:
     def advance(self, T: int = 1) -> None:
         """``lens += T`` on the device (capturable); the host bound follows."""
         self.lens.add_(T)
-        self._bound = min(self._bound + T, self.capacity)
+        self._bound = self._bound + T if self.ring else min(self._bound + T, self.capacity)
 
     def set_lens(self, lens) -> None:
         """Set per-row lengths from the host (a sync: not for a captured step)."""
         vals = [int(x) for x in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-        if len(vals) != self.B or min(vals) < 0 or max(vals) > self.capacity:
+        if self.ring:  # absolute lengths: the slots are taken to hold the last `capacity` positions before each
+            if len(vals) != self.B or min(vals) < 0 or max(vals) >= 2 ** 31:
+                raise ValueError(f"set_lens: {self.B} lengths >= 0 expected")
+        elif len(vals) != self.B or min(vals) < 0 or max(vals) > self.capacity:
             raise ValueError(f"set_lens: {self.B} lengths in 0..{self.capacity} expected")
         self.lens.copy_(torch.tensor(vals, dtype=torch.int32))
         self._bound = max(vals)
@@ -243,6 +283,10 @@ class KVCache:
         by the next append."""
         if n < 0:
             raise ValueError("rewind: n >= 0 expected")
+        if self.ring and n > self.capacity - (self.window or 1) + 1:
+            raise ValueError(f"rewind: on a ring of capacity {self.capacity} with window {self.window or 1} at most "
+                             f"{self.capacity - (self.window or 1) + 1} rows can be dropped (the keys before them are "
+                             f"overwritten), got {n}")
         self.lens.sub_(n).clamp_(min=0)
         self._bound = max(self._bound - n, 0)
 
@@ -250,9 +294,24 @@ class KVCache:
         self.lens.zero_()
         self._bound = 0
 
-    def _extend_ws(self) -> torch.Tensor:
+    def _ring_ws(self, attr: str, nbytes: int, what: str) -> torch.Tensor:
+        """A ring's workspace ``attr`` of at least ``nbytes`` (the size follows the window and the row count, never the
+        position): allocated on first use, replaced by a larger one when a call needs more, never inside a capture."""
+        ws = getattr(self, attr)
+        if ws is None or ws.numel() < nbytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{what}: run one step before capturing (the workspace is allocated on first use)")
+            ws = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
+            setattr(self, attr, ws)
+        return ws
+
+    def _extend_ws(self, window: int | None = None) -> torch.Tensor:
         """attention_extend's split workspace: MAX_EXTEND_ROWS times decode's (rows of a K / V head, whatever
-        the group size), allocated on first use (outside any capture) and kept."""
+        the group size), allocated on first use (outside any capture) and kept. A ring's: for the splits of
+        ``window`` and MAX_EXTEND_ROWS tokens."""
+        if self.ring:
+            return self._ring_ws("extend_workspace", _lib.lib().kfamd_attn_extend_ring_workspace(
+                self.B, self.H, 1, self.D, MAX_EXTEND_ROWS, window), "attention_extend")
         if self.extend_workspace is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("attention_extend: run one step before capturing (the workspace is allocated "
@@ -261,12 +320,15 @@ class KVCache:
             self.extend_workspace = torch.empty(max(int(nbytes), 16), device=self.device, dtype=torch.uint8)
         return self.extend_workspace
 
-    def _chunk_ws(self, T: int, G: int = 1) -> torch.Tensor:
+    def _chunk_ws(self, T: int, G: int = 1, window: int | None = None) -> torch.Tensor:
         """attention_chunk's split workspace for T tokens of G query heads per K / V head:
         ``kfamd_attn_chunk_gqa_workspace`` at the capacity (the split count does not fall when t_bound grows, so
         it serves every t_bound), allocated on first use and replaced by a larger one when a later call needs
         more, never inside a capture."""
         L = _lib.lib()
+        if self.ring:  # the split count comes from the window and T
+            return self._ring_ws("chunk_workspace", L.kfamd_attn_chunk_ring_workspace(self.B, self.H, G, self.D, T,
+                                                                                      window), "attention_chunk")
         nbytes = int(L.kfamd_attn_chunk_workspace(self.B, self.H, self.D, T, self.capacity) if G == 1 else
                      L.kfamd_attn_chunk_gqa_workspace(self.B, self.H, G, self.D, T, self.capacity))
         if self.chunk_workspace is None or self.chunk_workspace.numel() < nbytes:
@@ -294,15 +356,19 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None
     G = _group("kv_append", Hq, cache, native)
     if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != (Hq + 2 * H) * D:
         raise ValueError(f"kv_append: qkv [B={B}, T, {(Hq + 2 * H) * D}] expected, got {tuple(qkv.shape)}")
+    if cache.ring and qkv.shape[1] > cache.capacity:
+        raise ValueError(f"kv_append: T = {qkv.shape[1]} rows exceed the ring's capacity {cache.capacity}")
     if rope is not None:
-        if rope.dim() != 2 or rope.shape[1] != D or rope.shape[0] < cache.capacity or rope.dtype != torch.float32:
-            raise ValueError(f"kv_append: rope must be an fp32 [max_pos >= {cache.capacity}, {D}] table, got "
+        # a ring rotates by the absolute position: a table row for every position of the step, whatever the capacity
+        need = cache._bound + qkv.shape[1] if cache.ring else cache.capacity
+        if rope.dim() != 2 or rope.shape[1] != D or rope.shape[0] < need or rope.dtype != torch.float32:
+            raise ValueError(f"kv_append: rope must be an fp32 [max_pos >= {need}, {D}] table, got "
                              f"{tuple(rope.shape)} {rope.dtype}")
         if native:
             _kv_append_rope_native(qkv, cache, layer, Hq, rope)
             return
         from .rope import rotate_torch  # rows at or beyond the capacity have no table row here: left as they are
-        qkv.copy_(rotate_torch(qkv, rope[:cache.capacity], Hq, H, positions=cache.lens))
+        qkv.copy_(rotate_torch(qkv, rope if cache.ring else rope[:cache.capacity], Hq, H, positions=cache.lens))
     if native:
         _kv_append_native(qkv, cache, layer, Hq, G)
     else:
@@ -319,7 +385,9 @@ def _kv_append_torch(qkv, cache: KVCache, layer: int, Hq: int) -> None:
         _kv_append_fp8_torch(x, cache, layer)
         return
     rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=qkv.device).unsqueeze(0)  # [B, T]
-    if cache._bound + T <= cache.capacity:  # no row can fall off the end: one index_put per tensor
+    if cache.ring:
+        rows = rows % cache.capacity  # T <= capacity: no slot twice
+    if cache.ring or cache._bound + T <= cache.capacity:  # no row can fall off the end: one index_put per tensor
         bidx = torch.arange(B, device=qkv.device).unsqueeze(1).expand(B, T)
         k[bidx, :, rows] = x[:, :, 1].to(k.dtype)
         v[bidx, :, rows] = x[:, :, 2].to(v.dtype)
@@ -338,9 +406,10 @@ def _kv_append_native(qkv, cache: KVCache, layer: int, Hq: int, G: int) -> None:
         raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
     if cache.fp8 and D not in HEAD_DIMS:
         raise ValueError(f"kv_append: head dim in {HEAD_DIMS} expected for an FP8 cache on a GPU, got {D}")
-    fn, scales, tag = _entry("kfamd_kv_append" if G == 1 else "kfamd_kv_append_gqa", cache, layer)
+    fn, scales, tag = _entry("kfamd_kv_append_ring" if cache.ring else "kfamd_kv_append" if G == 1 else
+                             "kfamd_kv_append_gqa", cache, layer)  # the ring form takes the grouped signature
     rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(), B, T,
-            *((H,) if G == 1 else (Hq, H)), D, cache.capacity, qkv.stride(0), qkv.stride(1),
+            *((H,) if G == 1 and not cache.ring else (Hq, H)), D, cache.capacity, qkv.stride(0), qkv.stride(1),
             _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
     _lib.check(rc, f"kv_append[{tag}B={B} T={T} Hq={Hq} H={H} D={D}]")
 
@@ -356,7 +425,7 @@ def _kv_append_rope_native(qkv, cache: KVCache, layer: int, Hq: int, rope: torch
                          f"a GPU, got {D}, {k.dtype}")
     if not rope.is_cuda or rope.device != qkv.device or not rope.is_contiguous():
         raise ValueError("kv_append: rope must be a contiguous table on the activation's device")
-    fn, scales, tag = _entry("kfamd_kv_append_rope", cache, layer)
+    fn, scales, tag = _entry("kfamd_kv_append_rope_ring" if cache.ring else "kfamd_kv_append_rope", cache, layer)
     rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(),
             rope.data_ptr(), rope.shape[0], B, T, Hq, H, D, cache.capacity, qkv.stride(0), qkv.stride(1),
             _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
@@ -368,6 +437,8 @@ def _kv_append_fp8_torch(x, cache: KVCache, layer: int) -> None:
     views (torch has no index_copy for float8). Rows at or beyond the capacity are dropped."""
     B, T = x.shape[:2]
     rows = cache.lens.long().unsqueeze(1) + torch.arange(T, device=x.device).unsqueeze(0)  # [B, T]
+    if cache.ring:
+        rows = rows % cache.capacity  # every row has a slot
     for s, codes, scales in ((1, cache.k[layer], cache.k_scale[layer]), (2, cache.v[layer], cache.v_scale[layer])):
         c, sc = quantize_rows(x[:, :, s])  # [B, T, H, D], [B, T, H]
         c = c.view(torch.uint8)
@@ -385,6 +456,47 @@ def _dequantized_prefix(cache: KVCache, layer: int, lens, n: int, dtype):
     k = torch.where(live, dequantize_rows(cache.k[layer][:, :, :n], cache.k_scale[layer][:, :, :n]), zero)
     v = torch.where(live, dequantize_rows(cache.v[layer][:, :, :n], cache.v_scale[layer][:, :, :n]), zero)
     return k.to(dtype), v.to(dtype)
+
+
+def _ring_view(cache: KVCache, layer: int, lens, dtype):
+    """The torch path's view of a ring (the ring rule): ``(k, v, lens')`` with the slots gathered into absolute order
+    from ``off[b] = max(lens[b] - C, 0)`` on, index ``i`` standing for key ``off[b] + i`` (slot ``(off[b] + i) % C``),
+    and ``lens' = lens - off`` (at most C). Every key of a row's window keeps its distance to the row's limit, so the
+    masked softmax of the flat references applies unchanged. An FP8 ring is dequantised to ``dtype``, the rows at or
+    beyond ``lens'`` zeroed (dead codes and scales may be NaN)."""
+    C = cache.capacity
+    off = (lens.long() - C).clamp(min=0)  # [B]
+    slot = (off.view(-1, 1) + torch.arange(C, device=lens.device).view(1, C)) % C  # [B, C]
+    rows = slot.view(cache.B, 1, C).expand(cache.B, cache.H, C)
+
+    def gather(t):
+        if t.dim() == 3:
+            return t.gather(2, rows)
+        idx = rows.unsqueeze(-1).expand(cache.B, cache.H, C, cache.D)
+        if t.dtype == FP8:
+            return t.view(torch.uint8).gather(2, idx).view(FP8)
+        return t.gather(2, idx)
+    k, v = gather(cache.k[layer]), gather(cache.v[layer])
+    lens_g = (lens.long() - off).to(lens.dtype)
+    if cache.fp8:
+        live = (torch.arange(C, device=lens.device).view(1, 1, C) < lens_g.view(-1, 1, 1)).unsqueeze(-1)
+        zero = torch.zeros((), device=lens.device)
+        k = torch.where(live, dequantize_rows(k, gather(cache.k_scale[layer])), zero).to(dtype)
+        v = torch.where(live, dequantize_rows(v, gather(cache.v_scale[layer])), zero).to(dtype)
+    return k, v, lens_g
+
+
+def _ring_check(what: str, cache: KVCache, window, T: int, t_bound) -> int:
+    """The ring rule's conditions on an attention call of T new tokens, on every path; returns the window."""
+    if window is None:
+        raise ValueError(f"{what}: a ring cache needs window=W (capacity {cache.capacity}, window None)")
+    if window + T - 1 > cache.capacity:
+        raise ValueError(f"{what}: W + T - 1 <= capacity expected on a ring, got W = {window}, T = {T} "
+                         f"(W + T - 1 = {window + T - 1}) and capacity {cache.capacity}")
+    if t_bound is not None:
+        raise ValueError(f"{what}: t_bound= cannot be given on a ring cache (the grid comes from the window, "
+                         f"got t_bound = {t_bound})")
+    return window
 
 
 def _check_window(what: str, window) -> int | None:
@@ -454,7 +566,9 @@ def _attend_torch(reference, q, cache: KVCache, layer: int, G: int, scale, out, 
     """The torch path (CPU tensors / ops.torch_reference()): ``reference(q, k, v, lens, scale, window) -> (o, lse)``
     over the cache's K / V expanded to q's heads, an FP8 cache's as its visible rows dequantised to ``dtype``."""
     k, v = cache.k[layer], cache.v[layer]
-    if cache.fp8:
+    if cache.ring:  # the live slots in absolute order, then the same masked softmax
+        k, v, lens = _ring_view(cache, layer, lens, dtype)
+    elif cache.fp8:
         k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), dtype)
     o, lse = reference(q, *_expand_kv(k, v, G), lens, scale, window)
     o = o.to(q.dtype)
@@ -495,7 +609,8 @@ def _attend_launch(what: str, name: str, q, cache: KVCache, layer: int, out, len
         T, qs, os, dims = 1, (q.stride(0), 0, q.stride(1)), (out.stride(0), 0, out.stride(1)), f"H={q.shape[1]} G={G}"
     lse = torch.empty(q.shape[:-1], device=q.device, dtype=torch.float32) if return_lse else None
     grouped = G > 1 or window is not None
-    fn, scales, tag = _entry(name + ("_win" if window is not None else "_gqa" if grouped else ""), cache, layer)
+    fn, scales, tag = _entry(name + ("_ring" if cache.ring else "_win" if window is not None else "_gqa" if grouped
+                                     else ""), cache, layer)  # a ring: t_bound is the capacity
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
             lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, *((cache.H, G) if grouped else (cache.H,)),
             D, T, t_bound, *(() if window is None else (min(window, cache.capacity),)), scale,
@@ -518,6 +633,8 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     keys only (the module docstring's rule), on the windowed kernels of the same routing."""
     what = "attention_decode"
     window = _check_window(what, window)
+    if cache.ring:
+        window, t_bound = _ring_check(what, cache, window, 1, t_bound), cache.capacity
     _, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound, rank=3)
     if not _native(q):
         def reference(q, k, v, lens, scale, window):  # its own SDPA, not attention_extend's at T = 1; lse on request
@@ -535,17 +652,20 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if _gqa_mfma(1, G):  # the group's G rows on an MFMA tile
         res = attention_chunk(q.unsqueeze(1), cache, layer, scale=scale, out=out.unsqueeze(1), lens=lens,
-                              t_bound=t_bound, return_lse=return_lse, window=window)
+                              t_bound=None if cache.ring else t_bound, return_lse=return_lse, window=window)
         return (out, res[1].squeeze(1)) if return_lse else out
     if G > 1:  # the group's G rows on the extend kernel's row slots: T = 1, no t stride
-        return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(), G, t_bound,
-                              scale, return_lse, window)
+        return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(window), G,
+                              t_bound, scale, return_lse, window)
     B, H, D = q.shape
     k, v = cache.k[layer], cache.v[layer]
     lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry("kfamd_attn_decode" if window is None else "kfamd_attn_decode_win", cache, layer)
+    fn, scales, tag = _entry("kfamd_attn_decode_ring" if cache.ring else "kfamd_attn_decode" if window is None else
+                             "kfamd_attn_decode_win", cache, layer)
+    ws = cache.workspace if not cache.ring else cache._ring_ws(
+        "workspace", _lib.lib().kfamd_attn_decode_ring_workspace(B, H, D, window), what)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
-            lse.data_ptr() if lse is not None else None, cache.workspace.data_ptr(), B, H, D, t_bound,
+            lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, H, D, t_bound,
             *(() if window is None else (min(window, cache.capacity),)), scale,
             _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
                 *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
@@ -567,6 +687,8 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     ``window=W``: each row sees the last W keys up to its own only (the module docstring's rule)."""
     what = "attention_extend"
     window = _check_window(what, window)
+    if cache.ring:
+        window, t_bound = _ring_check(what, cache, window, q.shape[1] if q.dim() == 4 else 1, t_bound), cache.capacity
     T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
     if not _native(q):
         return _attend_torch(_attention_extend_torch, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
@@ -576,10 +698,10 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
                          f"GPU, got T = {T}, G = {G}")
     out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if _gqa_mfma(T, G):
-        return attention_chunk(q, cache, layer, scale=scale, out=out, lens=lens, t_bound=t_bound,
-                               return_lse=return_lse, window=window)
-    return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(), G, t_bound, scale,
-                          return_lse, window)
+        return attention_chunk(q, cache, layer, scale=scale, out=out, lens=lens,
+                               t_bound=None if cache.ring else t_bound, return_lse=return_lse, window=window)
+    return _attend_launch(what, "kfamd_attn_extend", q, cache, layer, out, lens, cache._extend_ws(window), G, t_bound,
+                          scale, return_lse, window)
 
 
 def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | None = None,
@@ -598,6 +720,8 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     rule); the key tiles below the lowest lower bound of a query tile's rows are not read."""
     what = "attention_chunk"
     window = _check_window(what, window)
+    if cache.ring:
+        window, t_bound = _ring_check(what, cache, window, q.shape[1] if q.dim() == 4 else 1, t_bound), cache.capacity
     T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
     if not _native(q):
         return _attend_torch(_attention_extend_torch, q, cache, layer, G, scale, out, lens, t_bound, return_lse,
@@ -608,5 +732,5 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     out = _attend_contract(what, q, cache, layer, lens, t_bound, out)
     if G > 1 and T * G > 65535:
         raise ValueError(f"attention_chunk: T * G <= 65535 query rows per K / V head expected, got T = {T}, G = {G}")
-    return _attend_launch(what, "kfamd_attn_chunk", q, cache, layer, out, lens, cache._chunk_ws(T, G), G, t_bound,
-                          scale, return_lse, window)
+    return _attend_launch(what, "kfamd_attn_chunk", q, cache, layer, out, lens, cache._chunk_ws(T, G, window), G,
+                          t_bound, scale, return_lse, window)

@@ -73,6 +73,12 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         and max. 4096 removes nothing and, being t_bound, launches the kernels without a window; 4095 removes one key
         and runs the windowed ones. Model: gpt-1b (gpt-small with --quick), B in {1, 8}, a graphed decode step at
         position about 4000 with GPTConfig(window=1024) against none, 7 interleaved runs: ms/token.
+  ring  (not in the default list) the ring-buffer KV cache. Kernel: D = 128, B x 16 heads for B in {1, 8}, position
+        4000, W in {256, 1024}, bf16 and FP8, decode / extend Tq = 4 / chunk T = 128: the flat windowed launch, the
+        ring launch at the same position and the ring launch at position 2^20 + 5 (no flat cache exists there),
+        interleaved in one process, medians of 7 blocks with min and max. Model: a graphed gpt-1b step (gpt-small
+        with --quick) at position about 4000 with W = 1024, flat against ring, B in {1, 8}, 7 interleaved runs.
+        nbytes: both caches for gpt-1b shapes at max_seq = 32768, W = 4096, B in {1, 16} (meta device, no timing).
 """
 from __future__ import annotations
 
@@ -90,7 +96,7 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
-                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600}
+                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600, "ring": 900}
 WINDOW_WS = (256, 1024, 4095, 4096)
 GQA_GS = (1, 2, 4, 8, 16)
 GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
@@ -1238,11 +1244,135 @@ def _window_model_rows(quick: bool):
     return rows
 
 
+RING_WS = (256, 1024)
+RING_FAR = 2 ** 20 + 5
+
+
+def _ring_kernel_rows(quick: bool):
+    """Ring against the flat windowed launch at the same position and W, and the ring at a position no flat cache
+    reaches: three candidates interleaved per cell. Both read the same keys; the ring's grid comes from W and T."""
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    H, D, cap, n = 16, 128, 4096, 4000
+    blocks = 5 if quick else 7
+    shapes = {"decode": (1, lambda B: (B, H, D)), "extend_T4": (4, lambda B: (B, 4, H, D)),
+              "chunk_T128": (128, lambda B: (B, 128, H, D))}
+    calls = {"decode": ops.attention_decode, "extend_T4": ops.attention_extend, "chunk_T128": ops.attention_chunk}
+    for B in (1, 8):
+        flats, ncopy = _gqa_caches(B, H, H, D, cap, quick)
+        near = torch.full((B,), n, device="cuda", dtype=torch.int32)
+        far = torch.full((B,), RING_FAR, device="cuda", dtype=torch.int32)
+        for W in RING_WS:
+            C = -(-(W + 128 - 1) // 256) * 256  # the largest step here is 128 tokens
+            for kind, flat in flats.items():
+                flat.set_lens([n] * B)
+                ring = ops.KVCache(ncopy, B, H, D, C, device="cuda", dtype=flat.dtype, ring=True, window=W)
+                for layer in range(ncopy):  # every slot holds a finite row
+                    ring.reset()
+                    for t0 in range(0, C, 256):
+                        ops.kv_append(torch.randn(B, 256, 3 * H * D, device="cuda").to(torch.bfloat16), ring, layer)
+                        ring.advance(256)
+                for name, (T, shape) in shapes.items():
+                    q = torch.randn(*shape(B), device="cuda").to(torch.bfloat16)
+                    out = torch.empty_like(q)
+                    fn = calls[name]
+                    fns = {"flat": (lambda i: fn(q, flat, i % ncopy, out=out, t_bound=n, window=W)),
+                           "ring": (lambda i: fn(q, ring, i % ncopy, out=out, lens=near, window=W)),
+                           "ring_far": (lambda i: fn(q, ring, i % ncopy, out=out, lens=far, window=W))}
+                    r = _time_blocks(fns, blocks=blocks, iters=20)
+                    mm = {k: {"min": v["min_us"], "max": v["max_us"]} for k, v in r.items()}
+                    row = {"op": name, "kind": kind, "B": B, "H": H, "D": D, "W": W, "position": n, "ring_capacity": C,
+                           "far_position": RING_FAR, "cache_copies": ncopy, **r,
+                           "flat_over_ring": r["flat"]["median_us"] / r["ring"]["median_us"],
+                           "ring_vs_flat_separated": _sep(mm["ring"], mm["flat"]),
+                           "far_over_near": r["ring_far"]["median_us"] / r["ring"]["median_us"],
+                           "far_vs_near_separated": _sep(mm["ring_far"], mm["ring"])}
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+                del ring
+        del flats
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _ring_model_rows(quick: bool):
+    """A graphed decode step of the windowed model at position about 4000 (about 2000 with --quick), on a flat cache
+    (pinned bound) against a ring, interleaved runs: ms/token."""
+    import dataclasses
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    rows = []
+    base = CONFIGS["gpt-small" if quick else "gpt-1b"]
+    W, new = (256 if quick else 1024), 64
+    prompt = base.max_seq - 2 * new
+    model = GPT(dataclasses.replace(base, window=W), device="cuda").eval()
+    for B in (1, 8):
+        idx = torch.randint(0, base.vocab_size, (B, prompt), device="cuda")
+        toks = torch.randint(0, base.vocab_size, (new, B), device="cuda")
+        nbytes = {}
+
+        def run(key):
+            if key == "flat":
+                cache = model.new_cache(B, prompt + new)
+            else:
+                cache = model.new_cache(B, model._ring_capacity(256), ring=True)
+            model.extend(idx, cache, last_only=True, chunk=256)  # the same prompt path for both
+            step = model.graphed_decode_step(cache)
+            step(toks[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(1, new):
+                step(toks[i])
+            torch.cuda.synchronize()
+            nbytes[key] = cache.nbytes
+            return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+        res = {"flat": [], "ring": []}
+        for _ in range(3 if quick else 7):  # interleaved
+            for k in res:
+                res[k].append(run(k))
+        row = {"model": "gpt-small" if quick else "gpt-1b", "B": B, "W": W, "mode": "graph",
+               "position": f"{prompt + 1} .. {prompt + new - 1}", "nbytes": dict(nbytes)}
+        for k, v in res.items():
+            row[k] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+        row["flat_over_ring"] = row["flat"]["ms_per_token"] / row["ring"]["ms_per_token"]
+        row["separated"] = _sep(row["flat"], row["ring"])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def _ring_nbytes_rows():
+    """K / V bytes of a flat cache and of a ring for gpt-1b shapes at max_seq = 32768, W = 4096 (a ring of 4352 slots:
+    steps of up to 256 tokens), from ``KVCache.nbytes`` of caches built on the meta device (nothing is allocated; the
+    attention workspaces, allocated on first use on a GPU, are not in these figures)."""
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.models import CONFIGS
+    c = CONFIGS["gpt-1b"]
+    rows = []
+    W, max_seq = 4096, 32768
+    C = -(-(W + 256 - 1) // 256) * 256
+    for B in (1, 16):
+        flat = ops.KVCache(c.n_layers, B, c.kv_heads, c.head_dim, max_seq, device="meta")
+        ring = ops.KVCache(c.n_layers, B, c.kv_heads, c.head_dim, C, device="meta", ring=True, window=W)
+        row = {"model": "gpt-1b", "B": B, "max_seq": max_seq, "W": W, "ring_capacity": C, "flat_nbytes": flat.nbytes,
+               "ring_nbytes": ring.nbytes, "flat_over_ring": flat.nbytes / ring.nbytes,
+               "bytes_per_position_and_row": flat.nbytes // (B * max_seq)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def step_ring(quick: bool):
+    return {"nbytes": _ring_nbytes_rows(), "kernel": _ring_kernel_rows(quick), "model": _ring_model_rows(quick)}
+
+
 def step_window(quick: bool):
     return {"kernel": _window_kernel_rows(quick), "model": _window_model_rows(quick)}
 
 
-STEPS = {"window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+STEPS = {"ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
 
 
 def main() -> int:
