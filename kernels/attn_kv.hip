@@ -131,6 +131,19 @@
 //   attn_extend_split<Fp8Rows, D, 8, GQ, true, true>      197
 //   kv_append<true>                                        20
 //   kv_append_fp8<D, true>                            32 / 31
+// PAGED = true (a paged cache, kfamd_attn_*_paged_*, kfamd_kv_append_paged_*; the rule: the docstring of ops/decode.py):
+// the flat set only, PAGED combines with neither WIN nor RING. A live workgroup reads its split's one page id as a
+// block-uniform scalar after the empty-split return (an absent entry is never dereferenced), clamps it into
+// [0, n_pages - 1], forms the K / V / scale bases from pool + page * page_stride + h * kh and indexes by key - k0 as the
+// RING branch does. Same partition, same order, same arithmetic: o and lse equal the flat launch's bit for bit
+// (tests/test_gpu_paged.py). VGPRs, D = 64 / 128 and GQ alike, scratch 0; the pre-existing 154 kernels of this file,
+// attn_kv_mfma.hip and rope_bf16.hip compared as ISA with the previous build: identical.
+//   attn_decode_split<Bf16Rows, D, false, false, true>            66
+//   attn_decode_split<Fp8Rows, D, false, false, true>             84
+//   attn_extend_split<Bf16Rows, D, 1 / 2 / 4 / 8, GQ, false, false, true>    64 /  92 / 129 / 201
+//   attn_extend_split<Fp8Rows, D, 1 / 2 / 4 / 8, GQ, false, false, true>     84 / 112 / 149 / 197
+//   kv_append_paged                                               20
+//   kv_append_fp8_paged<D>                                        37
 // The comparison with the previous build and these counts: tools/kernel_isa_diff.py (two directories of hipcc -S output).
 // The GQ = true instantiations of attn_extend_split use the same VGPRs as the GQ = false rows above, R for R
 // (64 / 92 / 129 / 201 and 84 / 112 / 149 / 197), the same LDS, scratch 0; attn_kv_combine<D> and
@@ -146,6 +159,7 @@
 // bf16 copy at T = 2048 (8 IEEE divisions per lane): 63 us per layer of a 2048-token prefill.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "attn_kv_rows.h"
 #include "kfamd_kernels.h"
 #include "wave_ops.h"
@@ -197,12 +211,32 @@ struct DecodeArgs {
   int cap;     // RING kernel only
 };
 
+// PAGED kernels (the page rule: the docstring of ops/decode.py): the flat arguments, with the page stride of K, V and
+// the scales in kb, vb, ksb, vsb, plus the page table. Types of their own, so that the flat kernels' argument blocks
+// (and with them their code) stay as they were.
+struct PagedAttnArgs : AttnArgs {
+  const int* pt;  // device int32 [B][pts]: the page of keys 256 c .. 256 c + 255 of row b, -1 for none
+  long long pts;
+  int n_pages;
+};
+struct PagedDecodeArgs : DecodeArgs {
+  const int* pt;
+  long long pts;
+  int n_pages;
+};
+
+// A page id read from the table, for a LOAD: clamped into [0, n_pages - 1] whatever the table holds.
+__device__ __forceinline__ int load_page(const int* pt, long long at, int n_pages) {
+  return min(max(pt[at], 0), n_pages - 1);
+}
+
 // One query row per (b, h). workspace: [B][H][nsplit][2] (m, l) then [B][H][nsplit][D] (o), fp32: the
 // extend kernel's at Tq = 1. What the extend body's comments say about key validity, clamped addresses,
 // the block-uniform early return, whole block steps and the window's lower bound holds here word for word.
-template <class Fmt, int D, bool WIN, bool RING>
-__global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
+template <class Fmt, int D, bool WIN, bool RING, bool PAGED>
+__global__ __launch_bounds__(kThreads) void attn_decode_split(std::conditional_t<PAGED, PagedDecodeArgs, DecodeArgs> a) {
   static_assert(WIN || !RING, "a ring always has a window");
+  static_assert(!PAGED || !WIN, "a paged cache has neither a window nor a ring");
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
   constexpr int kUnroll = Fmt::unroll(1);
@@ -248,12 +282,16 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) qf[i] *= a.scale_log2;
 
-  const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh + piece * 8;
-  const Elem* vbase = static_cast<const Elem*>(a.v) + b * a.vb + h * a.vh + piece * 8;
+  // PAGED: the split's 256 keys are one page, its id a block-uniform scalar read after the early return above (an
+  // absent entry is never dereferenced) and clamped; kb, vb, ksb, vsb are then the page strides
+  long long sl = b;  // the slice of the cache's first dimension
+  if constexpr (PAGED) sl = load_page(a.pt, b * a.pts + k0 / kSplitKeys, a.n_pages);
+  const Elem* kbase = static_cast<const Elem*>(a.k) + sl * a.kb + h * a.kh + piece * 8;
+  const Elem* vbase = static_cast<const Elem*>(a.v) + sl * a.vb + h * a.vh + piece * 8;
   const float *ksbase = nullptr, *vsbase = nullptr;
   if constexpr (Fmt::kScaled) {
-    ksbase = a.ks + b * a.ksb + h * a.ksh;
-    vsbase = a.vs + b * a.vsb + h * a.vsh;
+    ksbase = a.ks + sl * a.ksb + h * a.ksh;
+    vsbase = a.vs + sl * a.vsb + h * a.vsh;
   }
   if constexpr (RING) {  // the split's 256 keys are one run of slots from k0 % C on: what follows indexes it by key - k0
     const int s0 = k0 % a.cap;
@@ -271,7 +309,7 @@ __global__ __launch_bounds__(kThreads) void attn_decode_split(DecodeArgs a) {
   float ksn[kUnroll], vsn[kUnroll];  // Fmt::kScaled only
   auto load_ahead = [&](int u, int key) {
     key = min(key, last);
-    if constexpr (RING) key -= k0;  // clamped as an absolute index, then mapped to the slot
+    if constexpr (RING || PAGED) key -= k0;  // clamped as an absolute index, then mapped to the slot (the page's row)
     kn[u] = *reinterpret_cast<const Vec*>(kbase + key * a.kt);
     vn[u] = *reinterpret_cast<const Vec*>(vbase + key * a.vt);
     if constexpr (Fmt::kScaled) {
@@ -372,9 +410,10 @@ struct RowMap {
 // beyond nk is, by the branch on the key index. The limits are non-decreasing in r, so the launch's first row has
 // its lowest lower bound: a split that ends at or below it holds no key for any row, and inside the first live split
 // the walk starts at the block step that holds it.
-template <class Fmt, int D, int R, bool GQ, bool WIN, bool RING>
-__global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
+template <class Fmt, int D, int R, bool GQ, bool WIN, bool RING, bool PAGED>
+__global__ __launch_bounds__(kThreads) void attn_extend_split(std::conditional_t<PAGED, PagedAttnArgs, AttnArgs> a) {
   static_assert(WIN || !RING, "a ring always has a window");
+  static_assert(!PAGED || !WIN, "a paged cache has neither a window nor a ring");
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
   constexpr int kUnroll = Fmt::unroll(R);
@@ -439,12 +478,16 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
     if constexpr (WIN) lo[r] = max(nk[r] - a.window, 0);
   }
 
-  const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh + piece * 8;
-  const Elem* vbase = static_cast<const Elem*>(a.v) + b * a.vb + h * a.vh + piece * 8;
+  // PAGED: the split's 256 keys are one page, its id a block-uniform scalar read after the early return above (an
+  // absent entry is never dereferenced) and clamped; kb, vb, ksb, vsb are then the page strides
+  long long sl = b;  // the slice of the cache's first dimension
+  if constexpr (PAGED) sl = load_page(a.pt, b * a.pts + k0 / kSplitKeys, a.n_pages);
+  const Elem* kbase = static_cast<const Elem*>(a.k) + sl * a.kb + h * a.kh + piece * 8;
+  const Elem* vbase = static_cast<const Elem*>(a.v) + sl * a.vb + h * a.vh + piece * 8;
   const float *ksbase = nullptr, *vsbase = nullptr;
   if constexpr (Fmt::kScaled) {
-    ksbase = a.ks + b * a.ksb + h * a.ksh;
-    vsbase = a.vs + b * a.vsb + h * a.vsh;
+    ksbase = a.ks + sl * a.ksb + h * a.ksh;
+    vsbase = a.vs + sl * a.vsb + h * a.vsh;
   }
   if constexpr (RING) {  // the split's 256 keys are one run of slots from k0 % C on: what follows indexes it by key - k0
     const int s0 = k0 % a.cap;
@@ -467,7 +510,7 @@ __global__ __launch_bounds__(kThreads) void attn_extend_split(AttnArgs a) {
   float ksn[kUnroll], vsn[kUnroll];  // Fmt::kScaled only
   auto load_ahead = [&](int u, int key) {
     key = min(key, last);
-    if constexpr (RING) key -= k0;  // clamped as an absolute index, then mapped to the slot
+    if constexpr (RING || PAGED) key -= k0;  // clamped as an absolute index, then mapped to the slot (the page's row)
     kn[u] = *reinterpret_cast<const Vec*>(kbase + key * a.kt);
     vn[u] = *reinterpret_cast<const Vec*>(vbase + key * a.vt);
     if constexpr (Fmt::kScaled) {
@@ -639,13 +682,13 @@ __global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict
   if (d == 0 && lse) lse[bh] = any ? (M + log2f(L)) * kLn2 : -INFINITY;
 }
 
-template <class Fmt, int D, bool GQ, bool WIN, bool RING>
-void launch_rows(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
+template <class Fmt, int D, bool GQ, bool WIN, bool RING, bool PAGED = false, class Args = AttnArgs>
+void launch_rows(const Args& a, int n, dim3 grid, hipStream_t s) {  // n: rows of this launch, 1 .. kSlotRows
   const dim3 block(kThreads);
-  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ, WIN, RING>), grid, block, 0, s, a);
-  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ, WIN, RING>), grid, block, 0, s, a);
-  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ, WIN, RING>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ, WIN, RING>), grid, block, 0, s, a);
+  if (n == 1) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 1, GQ, WIN, RING, PAGED>), grid, block, 0, s, a);
+  else if (n == 2) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 2, GQ, WIN, RING, PAGED>), grid, block, 0, s, a);
+  else if (n <= 4) hipLaunchKernelGGL((attn_extend_split<Fmt, D, 4, GQ, WIN, RING, PAGED>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_extend_split<Fmt, D, 8, GQ, WIN, RING, PAGED>), grid, block, 0, s, a);
 }
 
 template <class Fmt, int D, bool WIN, bool RING>
@@ -661,11 +704,24 @@ void launch_split(const AttnArgs& a, int n, dim3 grid, hipStream_t s) {
   else launch_group<Fmt, D, false, false>(a, n, grid, s);
 }
 
+// a paged cache: the flat set only (neither WIN nor RING)
+template <class Fmt, int D>
+void launch_split(const PagedAttnArgs& a, int n, dim3 grid, hipStream_t s) {
+  if (a.lg > 0) launch_rows<Fmt, D, true, false, false, true>(a, n, grid, s);
+  else launch_rows<Fmt, D, false, false, false, true>(a, n, grid, s);
+}
+
 template <class Fmt, int D>
 void launch_decode(const DecodeArgs& d, dim3 grid, hipStream_t s) {
-  if (d.cap > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true, true>), grid, dim3(kThreads), 0, s, d);
-  else if (d.window > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true, false>), grid, dim3(kThreads), 0, s, d);
-  else hipLaunchKernelGGL((attn_decode_split<Fmt, D, false, false>), grid, dim3(kThreads), 0, s, d);
+  if (d.cap > 0) hipLaunchKernelGGL((attn_decode_split<Fmt, D, true, true, false>), grid, dim3(kThreads), 0, s, d);
+  else if (d.window > 0)
+    hipLaunchKernelGGL((attn_decode_split<Fmt, D, true, false, false>), grid, dim3(kThreads), 0, s, d);
+  else hipLaunchKernelGGL((attn_decode_split<Fmt, D, false, false, false>), grid, dim3(kThreads), 0, s, d);
+}
+
+template <class Fmt, int D>
+void launch_decode(const PagedDecodeArgs& d, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((attn_decode_split<Fmt, D, false, false, true>), grid, dim3(kThreads), 0, s, d);
 }
 
 // Splits of a ring launch: the absolute 256-aligned partition rebased per batch row at base_b = the split that holds
@@ -685,9 +741,14 @@ int ring_splits(int window, int T) { return (int)(((long long)window + T - 1 + k
 template <class Fmt>
 int attn_kv(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens, void* o,
             float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale, const long long* st,
-            bool has_t, void* stream, int G = 0, int window = 0, bool ring = false) {
+            bool has_t, void* stream, int G = 0, int window = 0, bool ring = false, const int* pt = nullptr,
+            long long pts = 0, int n_pages = 0) {
   if (!q || !k || !v || !lens || !o || !st || B <= 0 || H <= 0 || B > 65535 || H > 65535) return KFAMD_EINVAL;
   if (window < 0) return KFAMD_EINVAL;
+  // paged (pt given; the page rule: ops/decode.py): the b strides are page strides, the table holds a column for
+  // every split of t_bound, and neither a window nor a ring goes with it
+  if (pt && (n_pages < 1 || window > 0 || ring || t_bound < 1 || pts < (t_bound + kSplitKeys - 1) / kSplitKeys))
+    return KFAMD_EINVAL;
   // ring: t_bound is the capacity C. W + T - 1 <= C: the step's appends overwrite nothing its first row sees
   if (ring && (window < 1 || t_bound < 1 || t_bound % kSplitKeys || Tq < 1 || (long long)window + Tq - 1 > t_bound))
     return KFAMD_EINVAL;
@@ -707,8 +768,10 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
   if ((long long)t_bound * a.kt >= lim || (long long)t_bound * a.vt >= lim) return KFAMD_EINVAL;
   a.nsplit = ring ? ring_nsplit : (t_bound + kSplitKeys - 1) / kSplitKeys;
   if (a.nsplit > 1 && !ws) return KFAMD_EINVAL;
+  if (pt && (kSplitKeys * a.kt >= lim || kSplitKeys * a.vt >= lim)) return KFAMD_EINVAL;
   if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || (ws && !al16(ws))) return KFAMD_EALIGN;
   if (Fmt::kScaled && (!al4(ks) || !al4(vs))) return KFAMD_EALIGN;
+  if (pt && !al4(pt)) return KFAMD_EALIGN;
   if ((a.qb | a.qt | a.qh | a.ob | a.ot | a.oh) & 7) return KFAMD_EALIGN;
   if ((a.kb | a.kh | a.kt | a.vb | a.vh | a.vt) & (Fmt::kStrideAlign - 1)) return KFAMD_EALIGN;
   a.q = static_cast<const __bf16*>(q);
@@ -726,13 +789,31 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
     const DecodeArgs d = {a.q,  a.k,  a.v,  a.lens, a.o,  a.lse, a.ws, B,    H,    t_bound, a.nsplit, a.scale_log2,
                           a.qb, a.qh, a.kb, a.kh,   a.kt, a.vb,  a.vh, a.vt, a.ob, a.oh,    a.ks,     a.vs,
                           a.ksb, a.ksh, a.vsb, a.vsh, a.window, a.cap};
-    if (D == 64) launch_decode<Fmt, 64>(d, grid, s);
-    else launch_decode<Fmt, 128>(d, grid, s);
+    if (pt) {
+      PagedDecodeArgs pd = {};
+      static_cast<DecodeArgs&>(pd) = d;
+      pd.pt = pt, pd.pts = pts, pd.n_pages = n_pages;
+      if (D == 64) launch_decode<Fmt, 64>(pd, grid, s);
+      else launch_decode<Fmt, 128>(pd, grid, s);
+    } else if (D == 64) {
+      launch_decode<Fmt, 64>(d, grid, s);
+    } else {
+      launch_decode<Fmt, 128>(d, grid, s);
+    }
   }
   for (a.row0 = 0; has_t && a.row0 < Tq; a.row0 += kSlotRows) {  // one K / V stream per kSlotRows query rows
     const int n = Tq - a.row0 < kSlotRows ? Tq - a.row0 : kSlotRows;
-    if (D == 64) launch_split<Fmt, 64>(a, n, grid, s);
-    else launch_split<Fmt, 128>(a, n, grid, s);
+    if (pt) {
+      PagedAttnArgs pa = {};
+      static_cast<AttnArgs&>(pa) = a;
+      pa.pt = pt, pa.pts = pts, pa.n_pages = n_pages;
+      if (D == 64) launch_split<Fmt, 64>(pa, n, grid, s);
+      else launch_split<Fmt, 128>(pa, n, grid, s);
+    } else if (D == 64) {
+      launch_split<Fmt, 64>(a, n, grid, s);
+    } else {
+      launch_split<Fmt, 128>(a, n, grid, s);
+    }
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return static_cast<int>(e);
@@ -752,12 +833,18 @@ int attn_kv(const void* q, const void* k, const void* v, const float* ks, const 
 // ---- append ------------------------------------------------------------------------------------
 // RING (both append kernels): row lens[b] + t goes to slot (lens[b] + t) % Tcap and no row is dropped (T <= Tcap on
 // the host, so no slot is written twice).
-template <bool RING>
-__global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv, __bf16* __restrict__ kc,
-                                                 __bf16* __restrict__ vc, const int* __restrict__ pos, int B, int T,
-                                                 int H, int D8, int Tcap, long long qb, long long qt, long long kb,
-                                                 long long kh, long long kt, long long vb, long long vh,
-                                                 long long vt, int Hq) {  // Hq q heads come before the H k heads
+// PAGED (both append kernels; the page rule: ops/decode.py): row p = lens[b] + t goes to page pt[b][p >> 8], row
+// p & 255; kb, vb, ksb, vsb are the page strides. A position at or beyond Tcap, or whose table entry lies outside
+// [0, n_pages), is dropped without a store.
+// The kernels' names and parameter lists are those of the flat and ring forms as they were; the paged forms are
+// kernels of their own: kv_append_paged over this body, kv_append_fp8_paged written out (the comment there).
+template <bool RING, bool PAGED>
+__device__ __forceinline__ void kv_append_rows(const __bf16* __restrict__ qkv, __bf16* __restrict__ kc,
+                                               __bf16* __restrict__ vc, const int* __restrict__ pos, int B, int T,
+                                               int H, int D8, int Tcap, long long qb, long long qt, long long kb,
+                                               long long kh, long long kt, long long vb, long long vh, long long vt,
+                                               int Hq,  // Hq q heads come before the H k heads
+                                               const int* __restrict__ pt, long long pts, int n_pages) {
   const long long n = (long long)B * T * 2 * H * D8;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
@@ -777,10 +864,35 @@ __global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv,
   } else {
     if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, never written
   }
+  int sl = b;  // the slice of the cache's first dimension
+  if constexpr (PAGED) {
+    sl = pt[b * pts + (row >> 8)];
+    if (sl < 0 || sl >= n_pages) return;  // no page: dropped
+    row &= 255;
+  }
   const u32x4 val =
       *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)Hq + s * H + h) * (D8 * 8) + d8 * 8);
-  __bf16* dst = s == 0 ? kc + b * kb + h * kh + row * kt : vc + b * vb + h * vh + row * vt;
+  __bf16* dst = s == 0 ? kc + sl * kb + h * kh + row * kt : vc + sl * vb + h * vh + row * vt;
   *reinterpret_cast<u32x4*>(dst + d8 * 8) = val;
+}
+
+template <bool RING>
+__global__ __launch_bounds__(256) void kv_append(const __bf16* __restrict__ qkv, __bf16* __restrict__ kc,
+                                                 __bf16* __restrict__ vc, const int* __restrict__ pos, int B, int T,
+                                                 int H, int D8, int Tcap, long long qb, long long qt, long long kb,
+                                                 long long kh, long long kt, long long vb, long long vh,
+                                                 long long vt, int Hq) {
+  kv_append_rows<RING, false>(qkv, kc, vc, pos, B, T, H, D8, Tcap, qb, qt, kb, kh, kt, vb, vh, vt, Hq, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void kv_append_paged(const __bf16* __restrict__ qkv, __bf16* __restrict__ kc,
+                                                       __bf16* __restrict__ vc, const int* __restrict__ pos, int B,
+                                                       int T, int H, int D8, int Tcap, long long qb, long long qt,
+                                                       long long kb, long long kh, long long kt, long long vb,
+                                                       long long vh, long long vt, int Hq,
+                                                       const int* __restrict__ pt, long long pts, int n_pages) {
+  kv_append_rows<false, true>(qkv, kc, vc, pos, B, T, H, D8, Tcap, qb, qt, kb, kh, kt, vb, vh, vt, Hq, pt, pts,
+                              n_pages);
 }
 
 // One lane group (D / 8 lanes) per (b, t, k-or-v, h) row: a 16-B load of 8 bf16 per lane, the row's
@@ -837,6 +949,62 @@ __global__ __launch_bounds__(256) void kv_append_fp8(const __bf16* __restrict__ 
   *reinterpret_cast<u32x2*>(dst + piece * 8) = w;
   if (piece == 0) {
     float* sd = s == 0 ? ks + b * ksb + h * ksh : vs + b * vsb + h * vsh;
+    sd[row] = scale;
+  }
+}
+
+// The paged form of kv_append_fp8 (the comment above kv_append): a kernel of its own with the same arithmetic, so that
+// the flat and ring kernels stay instruction for instruction what they were (as one body inlined into both, the flat
+// instantiations came out with two multiplications' operands swapped).
+template <int D>
+__global__ __launch_bounds__(256) void kv_append_fp8_paged(const __bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
+                                                     uint8_t* __restrict__ vc, float* __restrict__ ks,
+                                                     float* __restrict__ vs, const int* __restrict__ pos, int B, int T,
+                                                     int H, int Tcap, long long qb, long long qt, long long kb,
+                                                     long long kh, long long kt, long long vb, long long vh,
+                                                     long long vt, long long ksb, long long ksh, long long vsb,
+                                                     long long vsh, int Hq, const int* __restrict__ pt,
+                                                     long long pts, int n_pages) {
+  constexpr int G = D / 8;
+  const long long n = (long long)B * T * 2 * H * G;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  long long r = idx;
+  const int piece = (int)(r % G);
+  r /= G;
+  const int h = (int)(r % H);
+  r /= H;
+  const int s = (int)(r % 2);  // 0: k, 1: v
+  r /= 2;
+  const int t = (int)(r % T);
+  const int b = (int)(r / T);
+  long long row = (long long)pos[b] + t;
+  if (row < 0 || row >= Tcap) return;  // past the capacity: dropped, neither codes nor scale written
+  const int page = pt[b * pts + (row >> 8)];  // uniform over the row's lane group
+  if (page < 0 || page >= n_pages) return;    // no page: dropped
+  row &= 255;
+  float x[8];
+  Bf16Rows::unpack8(
+      *reinterpret_cast<const u32x4*>(qkv + b * qb + t * qt + ((long long)Hq + s * H + h) * D + piece * 8), x);
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(x[i]));
+  am = kfw::group_max<G>(am);
+  const float scale = am > 0.f ? am / kFp8Max : 1.f;  // IEEE division: the torch reference's scale
+  float y[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(x[i] / scale, -kFp8Max), kFp8Max);
+  u32x2 w;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * i], y[4 * i + 1], 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * i + 2], y[4 * i + 3], p, true);
+    w[i] = (unsigned)p;
+  }
+  uint8_t* dst = s == 0 ? kc + page * kb + h * kh + row * kt : vc + page * vb + h * vh + row * vt;
+  *reinterpret_cast<u32x2*>(dst + piece * 8) = w;
+  if (piece == 0) {
+    float* sd = s == 0 ? ks + page * ksb + h * ksh : vs + page * vsb + h * vsh;
     sd[row] = scale;
   }
 }
@@ -965,8 +1133,10 @@ extern "C" int kfamd_attn_extend_win_fp8(const void* q, const void* k_codes, con
 // int32 [B], not advanced here. Rows at or beyond Tcap are dropped.
 static int kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const int* pos, int B, int T, int Hq, int H,
                           int D, int Tcap, long long qb, long long qt, const long long* cache_strides, void* stream,
-                          bool ring = false) {
+                          bool ring = false, const int* pt = nullptr, long long pts = 0, int n_pages = 0) {
   if (ring && (Tcap <= 0 || Tcap % kSplitKeys || T > Tcap)) return KFAMD_EINVAL;
+  if (pt && (ring || n_pages < 1 || Tcap <= 0 || Tcap % kSplitKeys || pts < Tcap / kSplitKeys || !al4(pt)))
+    return KFAMD_EINVAL;
   if (!qkv || !k_cache || !v_cache || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 || D <= 0 || D % 8 ||
       Tcap <= 0 || Hq < H || Hq % H || group_log2(Hq / H) < 0)
     return KFAMD_EINVAL;
@@ -977,7 +1147,11 @@ static int kv_append_bf16(const void* qkv, void* k_cache, void* v_cache, const i
   if ((n + 255) / 256 > 0x7fffffffll) return KFAMD_EINVAL;
   const dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (ring)
+  if (pt)
+    hipLaunchKernelGGL(kv_append_paged, grid, dim3(256), 0, s, static_cast<const __bf16*>(qkv),
+                       static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos, B, T, H, D / 8, Tcap, qb, qt,
+                       c[0], c[1], c[2], c[3], c[4], c[5], Hq, pt, pts, n_pages);
+  else if (ring)
     hipLaunchKernelGGL(kv_append<true>, grid, dim3(256), 0, s, static_cast<const __bf16*>(qkv),
                        static_cast<__bf16*>(k_cache), static_cast<__bf16*>(v_cache), pos, B, T, H, D / 8, Tcap, qb, qt,
                        c[0], c[1], c[2], c[3], c[4], c[5], Hq);
@@ -1008,8 +1182,11 @@ extern "C" int kfamd_kv_append_gqa_bf16(const void* qkv, void* k_cache, void* v_
 // cache_strides = {kb, kh, kt, vb, vh, vt, ksb, ksh, vsb, vsh}.
 static int kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale, const int* pos,
                          int B, int T, int Hq, int H, int D, int Tcap, long long qb, long long qt,
-                         const long long* cache_strides, void* stream, bool ring = false) {
+                         const long long* cache_strides, void* stream, bool ring = false, const int* pt = nullptr,
+                         long long pts = 0, int n_pages = 0) {
   if (ring && (Tcap <= 0 || Tcap % kSplitKeys || T > Tcap)) return KFAMD_EINVAL;
+  if (pt && (ring || n_pages < 1 || Tcap <= 0 || Tcap % kSplitKeys || pts < Tcap / kSplitKeys || !al4(pt)))
+    return KFAMD_EINVAL;
   if (!qkv || !k_codes || !v_codes || !k_scale || !v_scale || !pos || !cache_strides || B <= 0 || T <= 0 || H <= 0 ||
       Tcap <= 0 || Hq < H || Hq % H || group_log2(Hq / H) < 0)
     return KFAMD_EINVAL;
@@ -1029,10 +1206,16 @@ static int kv_append_fp8(const void* qkv, void* k_codes, void* v_codes, float* k
 #define KF_APPEND_FP8(DD, RR)                                                                                         \
   hipLaunchKernelGGL((kv_append_fp8<DD, RR>), grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, \
                      qb, qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq)
-  if (D == 64 && ring) KF_APPEND_FP8(64, true);
+#define KF_APPEND_FP8_PAGED(DD)                                                                                      \
+  hipLaunchKernelGGL((kv_append_fp8_paged<DD>), grid, dim3(256), 0, s, x, kc, vc, k_scale, v_scale, pos, B, T, H, Tcap, \
+                     qb, qt, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], Hq, pt, pts, n_pages)
+  if (D == 64 && pt) KF_APPEND_FP8_PAGED(64);
+  else if (pt) KF_APPEND_FP8_PAGED(128);
+  else if (D == 64 && ring) KF_APPEND_FP8(64, true);
   else if (D == 64) KF_APPEND_FP8(64, false);
   else if (ring) KF_APPEND_FP8(128, true);
   else KF_APPEND_FP8(128, false);
+#undef KF_APPEND_FP8_PAGED
 #undef KF_APPEND_FP8
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
@@ -1114,4 +1297,63 @@ extern "C" int kfamd_kv_append_ring_fp8(const void* qkv, void* k_codes, void* v_
   if (Hkv <= 0) return KFAMD_EINVAL;
   return kv_append_fp8(qkv, k_codes, v_codes, k_scale, v_scale, pos, B, T, Hq, Hkv, D, cap, qb, qt, cache_strides,
                        stream, true);
+}
+
+// The paged forms (contract: kfamd_kernels.h; the page rule: the docstring of ops/decode.py). The attention entry
+// points take decode's / the grouped signatures, the appends the grouped ones, each with the page table before the
+// stream; the b entries of the stride arrays are the page strides.
+extern "C" int kfamd_attn_decode_paged_bf16(const void* q, const void* k_pages, const void* v_pages, const int* lens,
+                                            void* o, float* lse, void* ws, int B, int H, int D, int t_bound,
+                                            float scale, const long long* st, const int* page_table,
+                                            long long table_stride, int n_pages, void* stream) {
+  if (!page_table) return KFAMD_EINVAL;
+  return attn_kv<Bf16Rows>(q, k_pages, v_pages, nullptr, nullptr, lens, o, lse, ws, B, H, D, 1, t_bound, scale, st,
+                           false, stream, 0, 0, false, page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_attn_decode_paged_fp8(const void* q, const void* k_pages, const void* v_pages,
+                                           const float* k_scale, const float* v_scale, const int* lens, void* o,
+                                           float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
+                                           const long long* st, const int* page_table, long long table_stride,
+                                           int n_pages, void* stream) {
+  if (!page_table) return KFAMD_EINVAL;
+  return attn_kv<Fp8Rows>(q, k_pages, v_pages, k_scale, v_scale, lens, o, lse, ws, B, H, D, 1, t_bound, scale, st,
+                          false, stream, 0, 0, false, page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_attn_extend_paged_bf16(const void* q, const void* k_pages, const void* v_pages, const int* lens,
+                                            void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T,
+                                            int t_bound, float scale, const long long* st, const int* page_table,
+                                            long long table_stride, int n_pages, void* stream) {
+  if (G <= 0 || !page_table) return KFAMD_EINVAL;
+  return attn_kv<Bf16Rows>(q, k_pages, v_pages, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
+                           true, stream, G, 0, false, page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_attn_extend_paged_fp8(const void* q, const void* k_pages, const void* v_pages,
+                                           const float* k_scale, const float* v_scale, const int* lens, void* o,
+                                           float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound,
+                                           float scale, const long long* st, const int* page_table,
+                                           long long table_stride, int n_pages, void* stream) {
+  if (G <= 0 || !page_table) return KFAMD_EINVAL;
+  return attn_kv<Fp8Rows>(q, k_pages, v_pages, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound, scale, st,
+                          true, stream, G, 0, false, page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_kv_append_paged_bf16(const void* qkv, void* k_pages, void* v_pages, const int* pos, int B, int T,
+                                          int Hq, int Hkv, int D, int cap, long long qb, long long qt,
+                                          const long long* cache_strides, const int* page_table,
+                                          long long table_stride, int n_pages, void* stream) {
+  if (Hkv <= 0 || !page_table) return KFAMD_EINVAL;
+  return kv_append_bf16(qkv, k_pages, v_pages, pos, B, T, Hq, Hkv, D, cap, qb, qt, cache_strides, stream, false,
+                        page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_kv_append_paged_fp8(const void* qkv, void* k_pages, void* v_pages, float* k_scale, float* v_scale,
+                                         const int* pos, int B, int T, int Hq, int Hkv, int D, int cap, long long qb,
+                                         long long qt, const long long* cache_strides, const int* page_table,
+                                         long long table_stride, int n_pages, void* stream) {
+  if (Hkv <= 0 || !page_table) return KFAMD_EINVAL;
+  return kv_append_fp8(qkv, k_pages, v_pages, k_scale, v_scale, pos, B, T, Hq, Hkv, D, cap, qb, qt, cache_strides,
+                       stream, false, page_table, table_stride, n_pages);
 }

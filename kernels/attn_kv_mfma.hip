@@ -78,6 +78,15 @@
 //   attn_chunk_split<Bf16Rows, 128, true, true, true>      234   65536
 //   attn_chunk_split<Fp8Rows, 64, true, true, true>        185   34304
 //   attn_chunk_split<Fp8Rows, 128, true, true, true>       255   67072
+// PAGED = true (a paged cache, kfamd_attn_chunk_paged_*; the comment at the kernel), scratch 0 for all:
+//   attn_chunk_split<Bf16Rows, 64, false, false, false, true>     125   32768
+//   attn_chunk_split<Bf16Rows, 128, false, false, false, true>    233   65536
+//   attn_chunk_split<Fp8Rows, 64, false, false, false, true>      185   34304
+//   attn_chunk_split<Fp8Rows, 128, false, false, false, true>     255   67072
+//   attn_chunk_split<Bf16Rows, 64, true, false, false, true>      127   32768
+//   attn_chunk_split<Bf16Rows, 128, true, false, false, true>     235   65536
+//   attn_chunk_split<Fp8Rows, 64, true, false, false, true>       186   34304
+//   attn_chunk_split<Fp8Rows, 128, true, false, false, true>      256   67072
 // The grouped limit is no affine function of the row, and with both kept through the key loop
 // <Fp8Rows, 128, true> spilled (256 VGPRs, 8 B scratch): the masked tiles compute the limit again instead.
 #include <hip/hip_runtime.h>
@@ -119,6 +128,15 @@ struct ChunkArgs {
   int cap;     // RING kernels only: the ring's capacity C, a multiple of kSplitKeys
 };
 
+// PAGED kernels (the page rule: the docstring of ops/decode.py): the flat arguments, with the page stride of K, V and
+// the scales in kb, vb, ksb, vsb, plus the page table. A type of its own, so that the flat kernels' argument block (and
+// with it their code) stays as it was.
+struct PagedChunkArgs : ChunkArgs {
+  const int* pt;  // device int32 [B][pts]: the page of keys 256 c .. 256 c + 255 of row b, -1 for none
+  long long pts;
+  int n_pages;
+};
+
 template <class Vec>
 __device__ __forceinline__ Vec bload8(__amdgpu_buffer_rsrc_t r, int byte_off, int soff) {
   if constexpr (sizeof(Vec) == 16) return bload16(r, byte_off, soff);
@@ -144,9 +162,15 @@ __device__ __forceinline__ Vec bload8(__amdgpu_buffer_rsrc_t r, int byte_off, in
 // range ends at its row len - key0: the address unit returns zeros beyond it, as it does past row len of a flat cache,
 // at the cost of scalar registers only. (A select in stage_write, as for the first tile's rows below blo, spilled
 // <Fp8Rows, 128>: 256 VGPRs, 24 - 32 B scratch.)
-template <class Fmt, int D, bool GQ, bool WIN, bool RING>
-__global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
+// PAGED (a paged cache, the rule: ops/decode.py): key j lives in page pt[b][j >> 8] at row j & 255. A split spans
+// several pages, a 64-key tile lies in one: stage_load reads the tile's page id as a block-uniform scalar (clamped into
+// [0, n_pages - 1]; only tiles that begin below len are staged, so an absent entry is never read) and rebuilds the K, V
+// and scale descriptors on that page's (page, h) slice. Their range ends at row min(256, len - page's first key): the
+// rows at or beyond len read as zeros from the address unit, as on the flat cache and the ring's last tile.
+template <class Fmt, int D, bool GQ, bool WIN, bool RING, bool PAGED>
+__global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(std::conditional_t<PAGED, PagedChunkArgs, ChunkArgs> a) {
   static_assert(WIN || !RING, "a ring always has a window");
+  static_assert(!PAGED || !WIN, "a paged cache has neither a window nor a ring");
   typedef typename Fmt::Elem Elem;
   typedef typename Fmt::Vec Vec;
   constexpr int KS = D / 16;               // k-steps of the Q K^T product
@@ -216,8 +240,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
   }
 
   // the (b, h) slices end at row len: whatever lies at or beyond it reads as zero
-  const Elem* kbase = static_cast<const Elem*>(a.k) + b * a.kb + h * a.kh;
-  const Elem* vbase = static_cast<const Elem*>(a.v) + b * a.vb + h * a.vh;
+  const Elem* kbase = static_cast<const Elem*>(a.k) + (PAGED ? 0 : b * a.kb) + h * a.kh;  // PAGED: + page * kb per tile
+  const Elem* vbase = static_cast<const Elem*>(a.v) + (PAGED ? 0 : b * a.vb) + h * a.vh;
   const int kt = (int)a.kt, vt = (int)a.vt;
   const auto rk0 = slice_rsrc(kbase, (long long)len * kt * ES), rv0 = slice_rsrc(vbase, (long long)len * vt * ES);
   const auto rs0 = slice_rsrc(Fmt::kScaled ? (w == 0 ? a.ks + b * a.ksb + h * a.ksh : a.vs + b * a.vsb + h * a.vsh)
@@ -237,6 +261,15 @@ __global__ __launch_bounds__(kThreads, 2) void attn_chunk_split(ChunkArgs a) {
       key0 = slot;
       slot += FK;
       if (slot >= a.cap) slot -= a.cap;
+    }
+    if constexpr (PAGED) {  // the tile's page: its slice, in range up to the row that holds key len - 1
+      const long long page = min(max(a.pt[b * a.pts + (key0 >> 8)], 0), a.n_pages - 1);
+      const int rows = min(kSplitKeys, len - (key0 & ~(kSplitKeys - 1)));
+      rk = slice_rsrc(kbase + page * a.kb, (long long)rows * kt * ES);
+      rv = slice_rsrc(vbase + page * a.vb, (long long)rows * vt * ES);
+      if constexpr (Fmt::kScaled)
+        rs = slice_rsrc(w == 0 ? a.ks + page * a.ksb + h * a.ksh : a.vs + page * a.vsb + h * a.vsh, 4LL * rows);
+      key0 &= kSplitKeys - 1;
     }
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
@@ -481,13 +514,14 @@ bool chunk_gqa_ok(int B, int Hkv, int G, int D, int T, int t_bound) {
   return lg >= 0 && T >= 1 && T <= (kMaxRows >> lg) && chunk_shape_ok(B, Hkv, D, T << lg, t_bound);
 }
 
-template <class Fmt, bool WIN, bool RING>
-void launch_chunk(const ChunkArgs& a, int D, dim3 grid, hipStream_t s) {
+template <class Fmt, bool WIN, bool RING, bool PAGED = false, class Args = ChunkArgs>
+void launch_chunk(const Args& a, int D, dim3 grid, hipStream_t s) {
   const dim3 block(kThreads);
-  if (a.lg > 0 && D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true, WIN, RING>), grid, block, 0, s, a);
-  else if (a.lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true, WIN, RING>), grid, block, 0, s, a);
-  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false, WIN, RING>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false, WIN, RING>), grid, block, 0, s, a);
+  if (a.lg > 0 && D == 64)
+    hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, true, WIN, RING, PAGED>), grid, block, 0, s, a);
+  else if (a.lg > 0) hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, true, WIN, RING, PAGED>), grid, block, 0, s, a);
+  else if (D == 64) hipLaunchKernelGGL((attn_chunk_split<Fmt, 64, false, WIN, RING, PAGED>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_chunk_split<Fmt, 128, false, WIN, RING, PAGED>), grid, block, 0, s, a);
 }
 
 // keys a ring launch partitions: the ceil((W + T - 1) / 256) + 1 splits of 256 from base_b on (attn_kv.hip's count)
@@ -503,7 +537,12 @@ int ring_span(int window, int T) {
 template <class Fmt>
 int attn_chunk(const void* q, const void* k, const void* v, const float* ks, const float* vs, const int* lens,
                void* o, float* lse, void* ws, int B, int H, int D, int Tq, int t_bound, float scale,
-               const long long* st, void* stream, int G = 0, int window = 0, bool ring = false) {
+               const long long* st, void* stream, int G = 0, int window = 0, bool ring = false,
+               const int* pt = nullptr, long long pts = 0, int n_pages = 0) {
+  // paged (pt given): the b strides are page strides, the table holds a column for every 256 keys of t_bound
+  if (pt && (n_pages < 1 || window > 0 || ring || t_bound < 1 || pts < (t_bound + kSplitKeys - 1) / kSplitKeys ||
+             !kfkv::al4(pt)))
+    return KFAMD_EINVAL;
   // ring: t_bound is the capacity C (the limit checks below then bound the slice of C rows), and the split count and
   // the keys per split come from the span of W and T, never from a position
   if (ring && (window < 1 || t_bound < 1 || t_bound % kSplitKeys || Tq < 1 || (long long)window + Tq - 1 > t_bound))
@@ -543,7 +582,12 @@ int attn_chunk(const void* q, const void* k, const void* v, const float* ks, con
   a.scale_log2 = scale * kLog2e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)wgs, (unsigned)H, (unsigned)B);
-  if (ring) launch_chunk<Fmt, true, true>(a, D, grid, s);
+  if (pt) {
+    PagedChunkArgs pa = {};
+    static_cast<ChunkArgs&>(pa) = a;
+    pa.pt = pt, pa.pts = pts, pa.n_pages = n_pages;
+    launch_chunk<Fmt, false, false, true>(pa, D, grid, s);
+  } else if (ring) launch_chunk<Fmt, true, true>(a, D, grid, s);
   else if (a.window > 0) launch_chunk<Fmt, true, false>(a, D, grid, s);
   else launch_chunk<Fmt, false, false>(a, D, grid, s);
   hipError_t e = hipGetLastError();
@@ -651,4 +695,24 @@ extern "C" int kfamd_attn_chunk_ring_fp8(const void* q, const void* k_codes, con
   if (G <= 0) return KFAMD_EINVAL;
   return attn_chunk<kfkv::Fp8Rows>(q, k_codes, v_codes, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, cap, scale,
                                    st, stream, G, window, true);
+}
+
+// The paged forms (contract: kfamd_kernels.h): the grouped signatures with the page table before the stream; the b
+// entries of the stride array are the page strides. Split count and workspace: kfamd_attn_chunk_gqa_nsplit / _workspace.
+extern "C" int kfamd_attn_chunk_paged_bf16(const void* q, const void* k_pages, const void* v_pages, const int* lens,
+                                           void* o, float* lse, void* ws, int B, int Hkv, int G, int D, int T,
+                                           int t_bound, float scale, const long long* st, const int* page_table,
+                                           long long table_stride, int n_pages, void* stream) {
+  if (G <= 0 || !page_table) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Bf16Rows>(q, k_pages, v_pages, nullptr, nullptr, lens, o, lse, ws, B, Hkv, D, T, t_bound,
+                                    scale, st, stream, G, 0, false, page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_attn_chunk_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const float* k_scale,
+                                          const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B,
+                                          int Hkv, int G, int D, int T, int t_bound, float scale, const long long* st,
+                                          const int* page_table, long long table_stride, int n_pages, void* stream) {
+  if (G <= 0 || !page_table) return KFAMD_EINVAL;
+  return attn_chunk<kfkv::Fp8Rows>(q, k_pages, v_pages, k_scale, v_scale, lens, o, lse, ws, B, Hkv, D, T, t_bound,
+                                   scale, st, stream, G, 0, false, page_table, table_stride, n_pages);
 }

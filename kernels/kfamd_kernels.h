@@ -457,6 +457,61 @@ int kfamd_kv_append_rope_ring_fp8(void* qkv, void* k_codes, void* v_codes, float
                                   int D, int cap, long long qb, long long qt, const long long* cache_strides,
                                   void* stream);
 
+// ---- paged KV cache (attn_kv.hip, attn_kv_mfma.hip, rope_bf16.hip) -------------------------------------
+// THE PAGE RULE is stated once, in the docstring of kubeflow_rm_amd/ops/decode.py. K, V are page pools
+// [n_pages][H][256][D] (FP8: codes, plus scales [n_pages][H][256]); page_table is DEVICE int32 [B][table_stride >=
+// ceil(t_bound / 256)] (appends: >= cap / 256), -1 for "no page"; key j of row b lives in page page_table[b][j / 256] at
+// row j % 256. The attention entry points take kfamd_attn_decode_* (decode) and kfamd_attn_extend_gqa_* /
+// kfamd_attn_chunk_gqa_* (G = 1 for plain rows) with (page_table, table_stride, n_pages) before the stream; the appends
+// take kfamd_kv_append_gqa_* / kfamd_kv_append_rope_* the same way, cap (a multiple of 256) in Tcap's place. In every
+// stride array the b entries (kb, vb, ksb, vsb) are the PAGE strides. lens, t_bound, lse, the workspaces, split counts
+// and return codes are the flat forms'; the split partition, the tile order and the arithmetic are too, so the results
+// equal the flat launch's bit for bit on the same contents. Neither a window nor a ring goes with a page table.
+// A page id read on the device is used for a load only after clamping into [0, n_pages - 1] (and only for splits /
+// tiles that begin below lens[b]), and for a store only if it lies in [0, n_pages): an append drops a position at or
+// beyond cap or without a page (the rotary form then leaves the row unrotated). KFAMD_EINVAL also for a null table,
+// n_pages < 1, a table narrower than the keys it must cover, cap no multiple of 256.
+// VGPRs of the PAGED instantiations (scratch 0 for all): the tables in attn_kv.hip, attn_kv_mfma.hip, rope_bf16.hip.
+int kfamd_attn_decode_paged_bf16(const void* q, const void* k_pages, const void* v_pages, const int* lens, void* o,
+                                 float* lse, void* ws, int B, int H, int D, int t_bound, float scale,
+                                 const long long* strides, const int* page_table, long long table_stride, int n_pages,
+                                 void* stream);
+int kfamd_attn_decode_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const float* k_scale,
+                                const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int H,
+                                int D, int t_bound, float scale, const long long* strides, const int* page_table,
+                                long long table_stride, int n_pages, void* stream);
+int kfamd_attn_extend_paged_bf16(const void* q, const void* k_pages, const void* v_pages, const int* lens, void* o,
+                                 float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound, float scale,
+                                 const long long* strides, const int* page_table, long long table_stride, int n_pages,
+                                 void* stream);
+int kfamd_attn_extend_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const float* k_scale,
+                                const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                                int G, int D, int T, int t_bound, float scale, const long long* strides,
+                                const int* page_table, long long table_stride, int n_pages, void* stream);
+int kfamd_attn_chunk_paged_bf16(const void* q, const void* k_pages, const void* v_pages, const int* lens, void* o,
+                                float* lse, void* ws, int B, int Hkv, int G, int D, int T, int t_bound, float scale,
+                                const long long* strides, const int* page_table, long long table_stride, int n_pages,
+                                void* stream);
+int kfamd_attn_chunk_paged_fp8(const void* q, const void* k_pages, const void* v_pages, const float* k_scale,
+                               const float* v_scale, const int* lens, void* o, float* lse, void* ws, int B, int Hkv,
+                               int G, int D, int T, int t_bound, float scale, const long long* strides,
+                               const int* page_table, long long table_stride, int n_pages, void* stream);
+int kfamd_kv_append_paged_bf16(const void* qkv, void* k_pages, void* v_pages, const int* pos, int B, int T, int Hq,
+                               int Hkv, int D, int cap, long long qb, long long qt, const long long* cache_strides,
+                               const int* page_table, long long table_stride, int n_pages, void* stream);
+int kfamd_kv_append_paged_fp8(const void* qkv, void* k_pages, void* v_pages, float* k_scale, float* v_scale,
+                              const int* pos, int B, int T, int Hq, int Hkv, int D, int cap, long long qb, long long qt,
+                              const long long* cache_strides, const int* page_table, long long table_stride,
+                              int n_pages, void* stream);
+int kfamd_kv_append_rope_paged_bf16(void* qkv, void* k_pages, void* v_pages, const int* lens, const float* table,
+                                    int max_pos, int B, int T, int Hq, int Hkv, int D, int cap, long long qb,
+                                    long long qt, const long long* cache_strides, const int* page_table,
+                                    long long table_stride, int n_pages, void* stream);
+int kfamd_kv_append_rope_paged_fp8(void* qkv, void* k_pages, void* v_pages, float* k_scale, float* v_scale,
+                                   const int* lens, const float* table, int max_pos, int B, int T, int Hq, int Hkv,
+                                   int D, int cap, long long qb, long long qt, const long long* cache_strides,
+                                   const int* page_table, long long table_stride, int n_pages, void* stream);
+
 // ---- rotary position embeddings (rope_bf16.hip)-----------------------------------------------------
 // table: fp32 [max_pos][D] contiguous, row p = cos(p f_i) | sin(p f_i), i < D/2 (built on the host). The
 // rotation is rotate-half: y[i] = x[i] c - x[i + D/2] s, y[i + D/2] = x[i + D/2] c + x[i] s, in fp32 without

@@ -33,6 +33,7 @@
 // build time: _build.NO_SCRATCH_TUS). The rotation compiles to v_pk_mul_f32 / v_pk_add_f32 and v_cvt_pk_bf16_f32,
 // no v_fma / v_fmac outside the FP8 form's IEEE divisions.
 // kv_append_rope<D, F8, true> (a ring-buffer cache: absolute position, slot position % Tcap): 58 VGPRs, scratch 0.
+// kv_append_rope<D, F8, false, true> (a paged cache: page pt[b][p >> 8], row p & 255): 56 VGPRs, scratch 0.
 // Measured (profiles/rope; the gpt-1b layer, B = 8, 16 heads, D = 128): at T = 1 the fused append costs what
 // kv_append costs (11.3 against 10.8 us bf16, 12.6 against 12.8 FP8) and half of rope_qkv + kv_append; at T = 2048
 // 72.9 us (bf16) and 78.2 (FP8) against 49.1 / 61.8 for the append alone and 99.4 / 106.1 for two launches.
@@ -135,6 +136,14 @@ struct RingAppendArgs : AppendArgs {
   int max_pos;  // the table's rows
 };
 
+// The paged form's arguments (the page rule: ops/decode.py): kb, vb, ksb, vsb are the page strides.
+struct PagedAppendArgs : AppendArgs {
+  const int* pt;  // device int32 [B][pts]: the page of positions 256 c .. 256 c + 255 of row b, -1 for none
+  long long pts;
+  int n_pages;
+  int max_pos;  // the table's rows: a row's capacity may be rounded up past them
+};
+
 // 8 bf16-valued floats -> 8 e4m3 codes at the row's scale: kv_append_fp8's arithmetic (attn_kv.hip)
 __device__ __forceinline__ u32x2 fp8_codes(const float* x, float scale) {
   float y[8];
@@ -155,8 +164,13 @@ __device__ __forceinline__ u32x2 fp8_codes(const float* x, float scale) {
 // RING: the rotation takes the absolute position lens[b] + t, the store goes to slot (lens[b] + t) % Tcap and no row is
 // dropped. The host refuses a step without a table row for every position; a device-side lens beyond what the host
 // believed is still kept inside the table here: such a row is neither rotated nor stored.
-template <int D, bool F8, bool RING>
-__global__ __launch_bounds__(256) void kv_append_rope(std::conditional_t<RING, RingAppendArgs, AppendArgs> a) {
+// PAGED: position p = lens[b] + t goes to page pt[b][p >> 8], row p & 255; a position at or beyond Tcap, or whose
+// table entry lies outside [0, n_pages), or without a table row (p >= max_pos), is neither rotated nor stored (uniform
+// over a head row's lanes).
+template <int D, bool F8, bool RING, bool PAGED>
+__global__ __launch_bounds__(256) void kv_append_rope(
+    std::conditional_t<PAGED, PagedAppendArgs, std::conditional_t<RING, RingAppendArgs, AppendArgs>> a) {
+  static_assert(!PAGED || !RING, "a paged cache is no ring");
   constexpr int G = D / 16;
   const int NH = a.Hq + 2 * a.Hkv;
   const long long n = (long long)a.B * a.T * NH * G;
@@ -177,6 +191,13 @@ __global__ __launch_bounds__(256) void kv_append_rope(std::conditional_t<RING, R
   } else {
     if (row < 0 || row >= a.Tcap) return;  // past the capacity: neither appended nor rotated
   }
+  long long sl = b;  // the slice of the cache's first dimension
+  if constexpr (PAGED) {
+    if (row >= a.max_pos) return;
+    sl = a.pt[b * a.pts + (row >> 8)];
+    if (sl < 0 || sl >= a.n_pages) return;  // no page: dropped
+    slot = row & 255;
+  }
   __bf16* src = a.qkv + b * a.qb + t * a.qt + (long long)hh * D + j * 8;
   u32x4 lo = *reinterpret_cast<const u32x4*>(src);
   u32x4 hi = *reinterpret_cast<const u32x4*>(src + D / 2);
@@ -189,8 +210,8 @@ __global__ __launch_bounds__(256) void kv_append_rope(std::conditional_t<RING, R
   }
   const int h = is_v ? hh - a.Hq - a.Hkv : hh - a.Hq;
   if constexpr (!F8) {
-    __bf16* dst = is_v ? static_cast<__bf16*>(a.vc) + b * a.vb + h * a.vh + slot * a.vt
-                       : static_cast<__bf16*>(a.kc) + b * a.kb + h * a.kh + slot * a.kt;
+    __bf16* dst = is_v ? static_cast<__bf16*>(a.vc) + sl * a.vb + h * a.vh + slot * a.vt
+                       : static_cast<__bf16*>(a.kc) + sl * a.kb + h * a.kh + slot * a.kt;
     *reinterpret_cast<u32x4*>(dst + j * 8) = lo;
     *reinterpret_cast<u32x4*>(dst + D / 2 + j * 8) = hi;
   } else {
@@ -202,27 +223,29 @@ __global__ __launch_bounds__(256) void kv_append_rope(std::conditional_t<RING, R
     for (int i = 0; i < 16; ++i) am = fmaxf(am, fabsf(x[i]));
     am = kfw::group_max<G>(am);
     const float scale = am > 0.f ? am / kFp8Max : 1.f;  // IEEE division: the torch reference's scale
-    uint8_t* dst = is_v ? static_cast<uint8_t*>(a.vc) + b * a.vb + h * a.vh + slot * a.vt
-                        : static_cast<uint8_t*>(a.kc) + b * a.kb + h * a.kh + slot * a.kt;
+    uint8_t* dst = is_v ? static_cast<uint8_t*>(a.vc) + sl * a.vb + h * a.vh + slot * a.vt
+                        : static_cast<uint8_t*>(a.kc) + sl * a.kb + h * a.kh + slot * a.kt;
     *reinterpret_cast<u32x2*>(dst + j * 8) = fp8_codes(x, scale);
     *reinterpret_cast<u32x2*>(dst + D / 2 + j * 8) = fp8_codes(x + 8, scale);
     if (j == 0) {
-      float* sd = is_v ? a.vs + b * a.vsb + h * a.vsh : a.ks + b * a.ksb + h * a.ksh;
+      float* sd = is_v ? a.vs + sl * a.vsb + h * a.vsh : a.ks + sl * a.ksb + h * a.ksh;
       sd[slot] = scale;
     }
   }
 }
 
-template <bool F8, bool RING = false>
+template <bool F8, bool RING = false, bool PAGED = false>
 int append_rope(void* qkv, void* kc, void* vc, float* ks, float* vs, const int* lens, const float* table, int max_pos,
                 int B, int T, int Hq, int Hkv, int D, int Tcap, long long qb, long long qt, const long long* c,
-                void* stream) {
+                void* stream, const int* pt = nullptr, long long pts = 0, int n_pages = 0) {
+  if (PAGED && (!pt || n_pages < 1 || Tcap <= 0 || Tcap % kSplitKeys || pts < Tcap / kSplitKeys || !al4(pt)))
+    return KFAMD_EINVAL;
   if (!qkv || !kc || !vc || !lens || !table || !c || B <= 0 || T <= 0 || Hkv <= 0 || Tcap <= 0 || Hq < Hkv ||
       Hq % Hkv || group_log2(Hq / Hkv) < 0)
     return KFAMD_EINVAL;
   if (F8 && (!ks || !vs)) return KFAMD_EINVAL;
   if (D != 64 && D != 128) return KFAMD_EINVAL;
-  if (RING ? (max_pos < 1 || Tcap % kSplitKeys || T > Tcap) : max_pos < Tcap) return KFAMD_EINVAL;  // flat: every cache row has a table row
+  if (RING ? (max_pos < 1 || Tcap % kSplitKeys || T > Tcap) : PAGED ? max_pos < 1 : max_pos < Tcap) return KFAMD_EINVAL;  // flat: every cache row has a table row
   if (c[2] < D || c[5] < D) return KFAMD_EINVAL;
   if (!al16(qkv) || !al16(kc) || !al16(vc) || !al16(table)) return KFAMD_EALIGN;
   if (F8 && (!al4(ks) || !al4(vs))) return KFAMD_EALIGN;
@@ -230,8 +253,9 @@ int append_rope(void* qkv, void* kc, void* vc, float* ks, float* vs, const int* 
   if ((c[0] | c[1] | c[2] | c[3] | c[4] | c[5]) & (F8 ? 15 : 7)) return KFAMD_EALIGN;
   const long long n = (long long)B * T * (Hq + 2 * Hkv) * (D / 16);
   if ((n + 255) / 256 > 0x7fffffffll) return KFAMD_EINVAL;
-  std::conditional_t<RING, RingAppendArgs, AppendArgs> a = {};
+  std::conditional_t<PAGED, PagedAppendArgs, std::conditional_t<RING, RingAppendArgs, AppendArgs>> a = {};
   if constexpr (RING) a.max_pos = max_pos;
+  if constexpr (PAGED) a.pt = pt, a.pts = pts, a.n_pages = n_pages, a.max_pos = max_pos;
   a.qkv = static_cast<__bf16*>(qkv);
   a.kc = kc, a.vc = vc, a.ks = ks, a.vs = vs, a.lens = lens, a.table = table;
   a.B = B, a.T = T, a.Hq = Hq, a.Hkv = Hkv, a.Tcap = Tcap;
@@ -239,8 +263,8 @@ int append_rope(void* qkv, void* kc, void* vc, float* ks, float* vs, const int* 
   if (F8) a.ksb = c[6], a.ksh = c[7], a.vsb = c[8], a.vsh = c[9];
   const dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (D == 64) hipLaunchKernelGGL((kv_append_rope<64, F8, RING>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((kv_append_rope<128, F8, RING>), grid, dim3(256), 0, s, a);
+  if (D == 64) hipLaunchKernelGGL((kv_append_rope<64, F8, RING, PAGED>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((kv_append_rope<128, F8, RING, PAGED>), grid, dim3(256), 0, s, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
 }
@@ -298,4 +322,25 @@ extern "C" int kfamd_kv_append_rope_ring_fp8(void* qkv, void* k_codes, void* v_c
                                              const long long* cache_strides, void* stream) {
   return append_rope<true, true>(qkv, k_codes, v_codes, k_scale, v_scale, lens, table, max_pos, B, T, Hq, Hkv, D, cap,
                                  qb, qt, cache_strides, stream);
+}
+
+// The paged forms (the page rule: ops/decode.py): kfamd_kv_append_rope_bf16 / _fp8 with the page table before the
+// stream; cap is the row capacity (a multiple of 256), the b entries of cache_strides are the page strides. The table
+// need not reach cap (max_pos >= 1): a position at or beyond max_pos is neither rotated nor stored, the caller checks.
+extern "C" int kfamd_kv_append_rope_paged_bf16(void* qkv, void* k_pages, void* v_pages, const int* lens,
+                                               const float* table, int max_pos, int B, int T, int Hq, int Hkv, int D,
+                                               int cap, long long qb, long long qt, const long long* cache_strides,
+                                               const int* page_table, long long table_stride, int n_pages,
+                                               void* stream) {
+  return append_rope<false, false, true>(qkv, k_pages, v_pages, nullptr, nullptr, lens, table, max_pos, B, T, Hq, Hkv,
+                                         D, cap, qb, qt, cache_strides, stream, page_table, table_stride, n_pages);
+}
+
+extern "C" int kfamd_kv_append_rope_paged_fp8(void* qkv, void* k_pages, void* v_pages, float* k_scale, float* v_scale,
+                                              const int* lens, const float* table, int max_pos, int B, int T, int Hq,
+                                              int Hkv, int D, int cap, long long qb, long long qt,
+                                              const long long* cache_strides, const int* page_table,
+                                              long long table_stride, int n_pages, void* stream) {
+  return append_rope<true, false, true>(qkv, k_pages, v_pages, k_scale, v_scale, lens, table, max_pos, B, T, Hq, Hkv, D,
+                                        cap, qb, qt, cache_strides, stream, page_table, table_stride, n_pages);
 }

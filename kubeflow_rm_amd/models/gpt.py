@@ -72,6 +72,12 @@ Ring-buffer cache: ``new_cache(..., ring=True)`` / ``generate(..., ring=True)`` 
 depends on the window and the step's token count alone (no ``pin_bound``). A step of T tokens needs ``window + T - 1 <=
 capacity``. Not built: a ring without a window, a capacity that is no multiple of 256, tensor-parallel sharding of a
 ring.
+
+Paged cache: ``new_cache(..., paged=True)`` / ``generate(..., paged=True)`` keep the K / V rows in pages of an
+``ops.PagePool`` (``ops/decode.py``'s page rule): memory follows the tokens held, caches on one pool share it, and
+``generate(num_samples=S)`` prefills a prompt once and forks it S ways, the samples sharing the prompt's full pages.
+The steps call ``cache.reserve`` themselves; the logits equal a flat cache's bit for bit. Not built: paged with a
+window or a ring, with ``draft=``, or with a tensor-parallel group that issues collectives.
 """
 from __future__ import annotations
 
@@ -422,8 +428,12 @@ class _GraphedDecodeStep:
         c = self.cache
         if c._bound + 1 > self.limit:
             raise ValueError(f"max_seq {self.limit} exceeded" if c.ring else f"cache capacity {c.capacity} exceeded")
+        if c.pool is not None:  # the replay reads the device table: a page taken here is seen by it
+            c.reserve(1)
         out = self.graphed(tok)
         c._bound += 1
+        if c.pool is not None:
+            c._hlen = [n + 1 for n in c._hlen]  # the replay advanced lens on the device
         return out
 
 
@@ -440,8 +450,12 @@ class _GraphedGenerateStep:
         c = self.cache
         if c._bound + 1 > self.limit:
             raise ValueError(f"max_seq {self.limit} exceeded" if c.ring else f"cache capacity {c.capacity} exceeded")
+        if c.pool is not None:  # the replay reads the device table: a page taken here is seen by it
+            c.reserve(1)
         self.graphed.graph.replay()
         c._bound += 1
+        if c.pool is not None:
+            c._hlen = [n + 1 for n in c._hlen]  # the replay advanced lens on the device
 
 
 class GPT(torch.nn.Module):
@@ -486,14 +500,32 @@ class GPT(torch.nn.Module):
     # the layer itself is _cache_layer() and the LM head _lm_head(), each written once per path.
 
     def new_cache(self, B: int, capacity: int, device=None, kv_dtype: torch.dtype | None = None,
-                  ring: bool = False) -> "ops.KVCache":
+                  ring: bool = False, paged: bool = False, pool: "ops.PagePool | None" = None,
+                  n_pages: int | None = None) -> "ops.KVCache":
         """A cache for B sequences of up to ``capacity`` tokens. ``kv_dtype``: what the cache stores;
         ``None`` is the model's dtype, ``torch.float8_e4m3fn`` the 8-bit cache (codes plus one fp32 scale
         per row: about half the bytes, see ``KVCache.nbytes``). ``ring=True`` (a windowed model only): a ring buffer of
         the last ``capacity`` positions (``ops/decode.py``'s ring rule): ``capacity`` is a multiple of 256 and need
         neither exceed the window nor reach ``max_seq``; a step of T tokens needs ``window + T - 1 <= capacity``, and
-        the positions stay bounded by ``max_seq`` (the position or rotary table)."""
+        the positions stay bounded by ``max_seq`` (the position or rotary table). ``paged=True`` (or a ``pool``): a paged
+        cache (``ops/decode.py``'s page rule) on ``pool``, or on a new ``ops.PagePool`` of ``n_pages`` pages (default
+        ``B * capacity / 256``, which can never run short); ``capacity`` (at most ``max_seq``) is rounded up to a
+        multiple of 256 and bounds a row's length, the memory is the pool's. A windowed model raises."""
         c = self.cfg
+        if paged or pool is not None:
+            if c.window is not None or ring:
+                raise ValueError("new_cache(paged=True): a paged cache with a window or a ring is not built")
+            if capacity > c.max_seq:
+                raise ValueError(f"cache capacity {capacity} exceeds max_seq {c.max_seq}")
+            cap = -(-capacity // ops.decode.PAGE) * ops.decode.PAGE
+            hkv = self.blocks[0].local_kv_heads
+            if pool is None:
+                pool = ops.PagePool(c.n_layers, hkv, c.head_dim, B * cap // ops.decode.PAGE if n_pages is None
+                                    else n_pages, device=device if device is not None else self.tok.device,
+                                    dtype=kv_dtype if kv_dtype is not None else c.dtype)
+            elif n_pages is not None:
+                raise ValueError("new_cache: n_pages sizes a new pool; it cannot be given with pool=")
+            return ops.KVCache(c.n_layers, B, hkv, c.head_dim, cap, dtype=kv_dtype, pool=pool)
         if ring and c.window is None:
             raise ValueError("new_cache(ring=True): a ring cache needs a windowed model (GPTConfig(window=W))")
         if not ring and capacity > c.max_seq:
@@ -529,6 +561,12 @@ class GPT(torch.nn.Module):
                                  f"{cache.capacity}")
         elif cache._bound + T > cache.capacity:
             raise ValueError(f"cache capacity {cache.capacity} exceeded")
+        elif cache.pool is not None:
+            if self.cfg.window is not None:
+                raise ValueError("a paged cache with a windowed model is not built")
+            if cache._bound + T > self.cfg.max_seq:  # the capacity is rounded up to whole pages
+                raise ValueError(f"max_seq {self.cfg.max_seq} exceeded")
+            cache.reserve(T)  # the step's pages: present and private before the first append
 
     @staticmethod
     def _att(cache, T: int, window) -> dict:
@@ -879,7 +917,8 @@ class GPT(torch.nn.Module):
                  generator: torch.Generator | None = None, graph: bool = False, draft: "GPT | None" = None,
                  lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None,
                  weight_dtype: torch.dtype | None = None, top_p: float | None = None, stop_token: int | None = None,
-                 sampler: str = "torch", prefill_chunk: int | None = None, ring: bool = False):
+                 sampler: str = "torch", prefill_chunk: int | None = None, ring: bool = False, paged: bool = False,
+                 num_samples: int | None = None, pool: "ops.PagePool | None" = None, return_cache: bool = False):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -921,7 +960,36 @@ class GPT(torch.nn.Module):
         ``prefill_chunk=N`` (default 256) on every device, and the capacity is ``W + max(N, 16, lookahead + 1) - 1``
         rounded up to a multiple of 256. With ``draft=`` the target's cache is a ring, and the draft's is one iff the
         draft has a window. It composes with ``kv_dtype``, ``weight_dtype``, ``sampler="fused"``, ``graph=True``, grouped
-        K / V heads and ``pos="rope"`` by shapes only."""
+        K / V heads and ``pos="rope"`` by shapes only.
+
+        ``paged=True``: the same generation on a paged cache (``new_cache(paged=True)``; ``ops/decode.py``'s page rule),
+        token for token and logit for logit. It composes with ``kv_dtype``, ``weight_dtype``, ``sampler="fused"``,
+        ``graph=True`` (the whole length is reserved before the capture), ``prefill_chunk``, grouped K / V heads and
+        ``pos="rope"``. ``num_samples=S`` (implies ``paged``): S samples per prompt. The prompt is prefilled once on B
+        rows, the cache is forked S ways (the samples share the prompt's full pages; the parent's pages pass to its
+        last child), the last position's logits are repeated S-fold and decoding continues on ``B * S`` rows. Returns
+        ``[B * S, T0 + max_new_tokens]``, prompt-major: row ``b * S + s``; the samplers draw for ``B * S`` rows, so a
+        seeded run equals a flat run on the prompts repeated S-fold. ``S = 1`` is ``paged=True``. The pool holds
+        ``B * (T0 // 256) + B * S * (pages of the prompt's tail and the new tokens)`` pages. ``pool=``: generate on
+        that ``ops.PagePool`` instead (it must have that many pages free); the pages return to it at the end.
+        ``return_cache=True`` (paged only): returns ``(tokens, cache)`` and leaves the pages held, for a follow-up turn
+        or a look at ``cache.pool``; call ``cache.release()`` when done. Not built (raises): ``paged`` / ``num_samples``
+        with ``draft=``, with ``ring`` or a windowed model, or with a tensor-parallel group that issues collectives."""
+        if num_samples is not None:
+            if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+                raise ValueError(f"generate(num_samples=...): an int >= 1 expected, got {num_samples!r}")
+            paged = True
+        paged = bool(paged) or pool is not None
+        if return_cache and not paged:
+            raise ValueError("generate(return_cache=True) needs a paged cache (paged=True or num_samples=)")
+        if paged:
+            if draft is not None:
+                raise NotImplementedError("generate: paged / num_samples with draft= is not built")
+            if ring or self.cfg.window is not None:
+                raise ValueError("generate: a paged cache with a window or a ring is not built")
+            if tpl._collective(self.blocks[0].tp_group):
+                raise NotImplementedError("generate: a paged cache with a tensor-parallel group that issues collectives "
+                                          "is not built")
         if ring:
             if self.cfg.window is None:
                 raise ValueError("generate(ring=True) needs a windowed model (GPTConfig(window=W))")
@@ -961,29 +1029,49 @@ class GPT(torch.nn.Module):
             return idx.clone()
         if graph and not idx.is_cuda:
             raise ValueError("generate(graph=True) needs GPU tensors")
+        S = num_samples or 1
         if ring:
             cache = self.new_cache(B, self._ring_capacity(max(prefill_chunk, 16, lookahead + 1)), device=idx.device,
                                    kv_dtype=kv_dtype, ring=True)
+        elif paged:  # the prompt's full pages once per prompt, its tail and the new tokens once per sample
+            P = ops.decode.PAGE
+            n_pages = B * (T0 // P) + B * S * (-(-total // P) - T0 // P)
+            if pool is not None and pool.pages_free < n_pages:
+                raise RuntimeError(f"generate: {n_pages} pages needed, {pool.pages_free} free in the pool")
+            cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype, paged=True, pool=pool,
+                                   n_pages=None if pool is not None else n_pages)
         else:
             cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
         if prefill_chunk is None:
             logits = self.prefill(idx, cache)
         else:  # the bf16 weights, as prefill: a prompt is not a decode step
             logits = self.extend(idx, cache, last_only=True, chunk=prefill_chunk)
+        if S > 1:  # one prefill, S continuations: row b * S + s
+            cache = cache.fork(S, release=True)  # the parent's pages pass on: the pool is sized without them
+            logits, idx, B = logits.repeat_interleave(S, 0), idx.repeat_interleave(S, 0), B * S
+        if paged and graph:
+            cache.reserve(max_new_tokens - 1)  # a capture cannot take pages: every position the replays append
         weights = self.decode_weights() if weight_dtype is not None else None
         if sampler == "fused":
-            return self._generate_fused(idx, logits, cache, weights, max_new_tokens, temperature, top_k, top_p,
-                                        stop_token, generator, graph)
-        step = lambda t: self.decode_step(t, cache, weights=weights)  # noqa: E731
-        if graph and max_new_tokens > 1:
-            step = self.graphed_decode_step(cache, weights=weights)
-        out = [idx]
-        for i in range(max_new_tokens):
-            nxt = _sample(logits, temperature, top_k, generator)
-            out.append(nxt.view(B, 1))
-            if i + 1 < max_new_tokens:
-                logits = step(nxt)
-        return torch.cat(out, 1)
+            out = self._generate_fused(idx, logits, cache, weights, max_new_tokens, temperature, top_k, top_p,
+                                       stop_token, generator, graph)
+        else:
+            step = lambda t: self.decode_step(t, cache, weights=weights)  # noqa: E731
+            if graph and max_new_tokens > 1:
+                step = self.graphed_decode_step(cache, weights=weights)
+            out = [idx]
+            for i in range(max_new_tokens):
+                nxt = _sample(logits, temperature, top_k, generator)
+                out.append(nxt.view(B, 1))
+                if i + 1 < max_new_tokens:
+                    logits = step(nxt)
+            out = torch.cat(out, 1)
+        if return_cache:
+            return out, cache
+        if paged and pool is not None:  # a caller's pool gets its pages back
+            cache.release()
+        return out
+
 
     def _generate_fused(self, idx, logits, cache, weights, S: int, temperature, top_k, top_p, stop_token, generator,
                         graph: bool):
@@ -1031,11 +1119,14 @@ class GPT(torch.nn.Module):
         if not cache.ring:  # a ring's grid does not come from the bound
             cache.pin_bound()
         bound = cache._bound
+        hlen = list(cache._hlen) if cache.pool is not None else None  # a paged cache's host mirror of lens
         state = [t for t in (cache.lens, step, tok, seq, done) if t is not None]
         saved = [t.clone() for t in state]
 
         def body(t):  # warm-up and capture both start from the same host bound
             cache._bound = bound
+            if hlen is not None:  # the warm-up took the step's page; the capture finds it and changes nothing
+                cache._hlen = list(hlen)
             ops.sample(self.decode_step(t, cache, weights=weights), u, temperature=temperature, top_k=top_k,
                        top_p=top_p, step=step, out=t, seq=seq, done=done, stop_token=stop_token)
             step.add_(1)
@@ -1045,6 +1136,8 @@ class GPT(torch.nn.Module):
         for t, s0 in zip(state, saved):
             t.copy_(s0)
         cache._bound = bound
+        if hlen is not None:
+            cache._hlen = list(hlen)
         return _GraphedGenerateStep(g, cache, (weights, u, step, tok, seq, done), limit)
 
     def graphed_decode_step(self, cache, weights: "DecodeWeights | None" = None) -> "_GraphedDecodeStep":
@@ -1060,15 +1153,20 @@ class GPT(torch.nn.Module):
         if not cache.ring:  # a ring's grid does not come from the bound
             cache.pin_bound()
         saved, bound = cache.lens.clone(), cache._bound
+        hlen = list(cache._hlen) if cache.pool is not None else None  # a paged cache's host mirror of lens
 
         def step(t):  # warm-up and capture both start from the same host bound
             cache._bound = bound
+            if hlen is not None:  # the warm-up took the step's page; the capture finds it and changes nothing
+                cache._hlen = list(hlen)
             return self.decode_step(t, cache, weights=weights)
 
         g = ops.GraphedCallable(step, torch.zeros(cache.B, dtype=torch.long, device=cache.lens.device), warmup=1)
         torch.cuda.current_stream().synchronize()
         cache.lens.copy_(saved)
         cache._bound = bound
+        if hlen is not None:
+            cache._hlen = list(hlen)
         gs = _GraphedDecodeStep(g, cache, limit)
         gs.weights = weights  # the captured kernels read these tensors: they live as long as the step
         return gs

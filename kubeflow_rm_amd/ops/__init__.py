@@ -8,7 +8,7 @@ from .attention import attention_qkv, attn_block, flash_attention, split_heads  
 from .attention import supported as attention_supported  # noqa: F401
 from .allreduce import OneShotAllReduce  # noqa: F401
 from .graph import GraphedCallable  # noqa: F401
-from .decode import KVCache, attention_chunk, attention_decode, attention_extend, kv_append  # noqa: F401
+from .decode import KVCache, PagePool, attention_chunk, attention_decode, attention_extend, kv_append  # noqa: F401
 from . import decode  # noqa: F401
 from .rope import rope_qkv, rope_table  # noqa: F401
 from .swiglu import swiglu, swiglu_deinterleave, swiglu_interleave  # noqa: F401

@@ -170,6 +170,27 @@ _SIGNATURES = {
                                                c_int, c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_rope_ring_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                               c_int, c_int, c_int, c_ll, c_ll, ctypes.POINTER(c_ll), c_vp]),
+    # the paged forms: decode's / the grouped signatures with (page_table, table_stride, n_pages) before the stream
+    "kfamd_attn_decode_paged_bf16": (c_int, [c_vp] * 7 + [c_int] * 4 + [c_float, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                      c_vp]),
+    "kfamd_attn_decode_paged_fp8": (c_int, [c_vp] * 9 + [c_int] * 4 + [c_float, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                     c_vp]),
+    "kfamd_attn_extend_paged_bf16": (c_int, [c_vp] * 7 + [c_int] * 6 + [c_float, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                      c_vp]),
+    "kfamd_attn_extend_paged_fp8": (c_int, [c_vp] * 9 + [c_int] * 6 + [c_float, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                     c_vp]),
+    "kfamd_attn_chunk_paged_bf16": (c_int, [c_vp] * 7 + [c_int] * 6 + [c_float, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                     c_vp]),
+    "kfamd_attn_chunk_paged_fp8": (c_int, [c_vp] * 9 + [c_int] * 6 + [c_float, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                    c_vp]),
+    "kfamd_kv_append_paged_bf16": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_ll, c_ll, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                    c_vp]),
+    "kfamd_kv_append_paged_fp8": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_ll, c_ll, ctypes.POINTER(c_ll), c_vp, c_ll, c_int,
+                                                                   c_vp]),
+    "kfamd_kv_append_rope_paged_bf16": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_ll, c_ll, ctypes.POINTER(c_ll), c_vp, c_ll,
+                                                                         c_int, c_vp]),
+    "kfamd_kv_append_rope_paged_fp8": (c_int, [c_vp] * 7 + [c_int] * 7 + [c_ll, c_ll, ctypes.POINTER(c_ll), c_vp, c_ll,
+                                                                        c_int, c_vp]),
     "kfamd_kv_append_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll,
                                          ctypes.POINTER(c_ll), c_vp]),
     "kfamd_kv_append_gqa_fp8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -91,6 +91,32 @@ and is valid for ``n <= T`` of the step before it (draft-and-verify). ``t_bound`
 them; nothing on the ring path depends on them. The torch path gathers the live slots into absolute order and applies
 the masked softmax above. Positions up to 2^24 are covered. ``ring=False`` is the cache as it was: same launches, same
 bits. Not built: a ring without a window, a capacity that is no multiple of 256.
+
+Paged cache: ``KVCache(..., pool=PagePool(...))`` keeps its rows in pages of a pool that several caches share, so memory
+follows the use, not the capacity, and sequences can share a prefix. THE PAGE RULE (the kernels, ``kfamd_kernels.h`` and
+the documents point here): a page holds ``PAGE = 256`` consecutive positions of one sequence, for all K / V heads of one
+layer (``PAGE`` is the kernels' ``SPLIT_KEYS``). ``PagePool(n_layers, H, D, n_pages, device, dtype)`` owns per layer
+``k`` / ``v`` ``[n_pages, H, 256, D]`` (an FP8 pool also ``k_scale`` / ``v_scale`` ``[n_pages, H, 256]``), a host free
+list and a host reference count per page. ``capacity`` of a paged cache is a positive multiple of 256 (anything else
+raises ``ValueError``): the longest a row may grow, not memory. ``cache.page_table`` is a device ``int32 [B, capacity //
+256]`` with ``-1`` for "no page"; the host keeps an exact mirror of it and of every row's length, which ``advance``,
+``rewind``, ``set_lens`` and ``reset`` keep exact (so: no device-side change of ``lens`` behind the cache's back, except
+a captured step's, whose replay wrapper tells the mirror). Key ``j`` of row ``b`` lives in page ``page_table[b, j //
+256]`` at row ``j % 256``, for K, V and the FP8 scales alike. ``lens``, ``t_bound``, ``lens_after``, ``bound_after``,
+``pin_bound`` and the split workspaces mean exactly what they mean on a flat cache. ``cache.reserve(T)`` makes positions
+``0 .. len + T - 1`` present and the last T of them writable (a page shared with another cache is copied first);
+``GPT.prefill`` / ``decode_step`` / ``extend`` and the graphed steps call it, a direct user of ``kv_append`` calls it
+themselves: ``kv_append`` drops a position at or beyond the capacity or without a page, without a store (the rotary
+form then leaves that row unrotated). ``cache.fork(S)`` gives ``B * S`` rows that share the full pages; ``release()``
+gives the pages back. The kernels keep the flat launch's absolute 256-aligned split partition, tile order and
+arithmetic: a VALU workgroup reads its one page id as a block-uniform scalar after the empty-split return, the MFMA
+form the page of each 64-key tile, whose buffer descriptors end at the row that holds key ``len - 1`` (rows beyond read
+as zeros). So a paged launch equals the flat launch bit for bit on the same logical contents. A page id read on the
+device is clamped into ``[0, n_pages - 1]`` before a load and checked before a store. Pages no row owns, and rows at or
+beyond ``len`` in an owned page, may hold NaN (bf16) or ``0x7F`` codes and NaN scales (FP8). ``window=`` on a paged cache
+raises ``ValueError``, and so does ``ring=True`` with ``pool=``. The torch path gathers each row's pages into a ``[B, H,
+capacity, D]`` view (absent pages as zeros) and runs the flat references. ``pool=None`` is the cache as it was: same
+launches, same bits. Not built: paged with a window or a ring, page sizes other than 256.
 """
 from __future__ import annotations
 
@@ -114,6 +140,7 @@ GROUP_SIZES = (1, 2, 4, 8, 16)  # query heads per K / V head the kernels take
 # bf16 and FP8): at 8 rows the MFMA form is 1.5 - 2.0x faster, at 16 rows 2.5 - 3.7x, every case beyond the
 # blocks' spread; below 8 rows the forms were not compared and the VALU form stays.
 GQA_MFMA_MIN_ROWS: int | None = 8
+PAGE = 256  # positions per page of a paged cache: the kernels' SPLIT_KEYS
 RING_ALIGN = 256  # a ring's capacity is a multiple of the kernels' SPLIT_KEYS (a constant: importing needs no library)
 
 
@@ -192,6 +219,67 @@ def dequantize_rows(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return codes.float() * scale.float().unsqueeze(-1)
 
 
+class PagePool:
+    """The memory of paged caches (the module docstring's page rule): per layer ``k`` / ``v`` ``[n_pages, H, 256, D]``
+    (``dtype=torch.float8_e4m3fn``: codes, and ``k_scale`` / ``v_scale`` ``[n_pages, H, 256]`` fp32), a host free list
+    and a host reference count per page. Pages are handed out lowest id first. Every ``KVCache(..., pool=pool)`` on it
+    must match ``n_layers``, ``H``, ``D``, the dtype and the device."""
+
+    def __init__(self, n_layers: int, H: int, D: int, n_pages: int, device=None, dtype: torch.dtype = torch.bfloat16):
+        if min(n_layers, H, D, n_pages) < 1:
+            raise ValueError("PagePool: positive sizes expected")
+        self.n_layers, self.H, self.D, self.n_pages = n_layers, H, D, n_pages
+        self.device, self.dtype = torch.device(device if device is not None else "cpu"), dtype
+        self.k = [torch.zeros(n_pages, H, PAGE, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+        self.v = [torch.zeros(n_pages, H, PAGE, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+        self.k_scale = self.v_scale = None
+        if dtype == FP8:
+            self.k_scale = [torch.zeros(n_pages, H, PAGE, device=self.device) for _ in range(n_layers)]
+            self.v_scale = [torch.zeros(n_pages, H, PAGE, device=self.device) for _ in range(n_layers)]
+        self._free = list(range(n_pages))  # taken from the front
+        self._ref = [0] * n_pages
+
+    @property
+    def pages_total(self) -> int:
+        return self.n_pages
+
+    @property
+    def pages_free(self) -> int:
+        return len(self._free)
+
+    @property
+    def page_bytes(self) -> int:
+        """Bytes of one page over all layers: K and V, and the scales of an FP8 pool."""
+        per = self.H * PAGE * (self.D * self.k[0].element_size() + (4 if self.dtype == FP8 else 0))
+        return 2 * self.n_layers * per
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of device memory the pool holds, whatever is in use."""
+        return self.n_pages * self.page_bytes
+
+    def _take(self, n: int) -> list[int]:
+        """n pages from the free list, each with one reference; the caller has checked ``pages_free``."""
+        pages, self._free = self._free[:n], self._free[n:]
+        for p in pages:
+            self._ref[p] = 1
+        return pages
+
+    def _drop(self, page: int) -> None:
+        self._ref[page] -= 1
+        if self._ref[page] == 0:
+            self._free.append(page)
+
+    def _copy(self, src: int, dst: int) -> None:
+        """The device copy of page ``src`` into page ``dst`` in every layer, scales included."""
+        for ts in (self.k, self.v, self.k_scale or [], self.v_scale or []):
+            for t in ts:
+                if t.dtype == FP8:
+                    t.view(torch.uint8)[dst].copy_(t.view(torch.uint8)[src])
+                else:
+                    t[dst].copy_(t[src])
+
+
 class KVCache:
     """Per-layer K / V ``[B, H, capacity, D]``, device ``lens`` (int32 [B]), host ``t_bound``. ``H`` is the
     number of K / V heads: a grouped-query model's cache holds ``n_kv_heads`` and the attention functions take a
@@ -201,24 +289,49 @@ class KVCache:
     ``ring=True``: a ring buffer of the last ``capacity`` positions (the module docstring's ring rule): ``capacity`` a
     multiple of 256, ``lens`` absolute and unbounded, key ``j`` in slot ``j % capacity``. ``window``: optional, the
     window the cache will be attended with: only ``rewind`` reads it, for its limit ``capacity - window + 1`` (without
-    it the limit is ``capacity``, what a window of 1 allows). No call changes it."""
+    it the limit is ``capacity``, what a window of 1 allows). No call changes it.
+    ``pool=PagePool(...)``: a paged cache on that pool (the module docstring's page rule): ``capacity`` is a multiple of
+    256 and bounds a row's length, not memory; ``k`` / ``v`` (and the scales) ARE the pool's tensors ``[n_pages, H, 256,
+    D]``, ``page_table`` the device ``int32 [B, capacity // 256]``; the device and the dtype are the pool's. ``reserve``,
+    ``fork`` and ``release`` exist on a paged cache only."""
 
     def __init__(self, n_layers: int, B: int, H: int, D: int, capacity: int, device=None,
-                 dtype: torch.dtype = torch.bfloat16, ring: bool = False, window: int | None = None):
+                 dtype: torch.dtype | None = None, ring: bool = False, window: int | None = None,
+                 pool: "PagePool | None" = None):
         if min(n_layers, B, H, D, capacity) < 1:
             raise ValueError("KVCache: positive sizes expected")
         if ring and capacity % RING_ALIGN:
             raise ValueError(f"KVCache(ring=True): the capacity must be a multiple of {RING_ALIGN}, got {capacity}")
-        self.ring = bool(ring)
+        if pool is not None:
+            if ring:
+                raise ValueError("KVCache: ring=True cannot be combined with pool= (a paged ring is not built)")
+            if capacity % PAGE:
+                raise ValueError(f"KVCache(pool=...): the capacity must be a multiple of {PAGE}, got {capacity}")
+            if (pool.n_layers, pool.H, pool.D) != (n_layers, H, D):
+                raise ValueError(f"KVCache(pool=...): the pool holds {pool.n_layers} layers of {pool.H} heads x {pool.D}, "
+                                 f"got {n_layers} layers of {H} x {D}")
+            if dtype is not None and dtype != pool.dtype:
+                raise ValueError(f"KVCache(pool=...): the pool's dtype is {pool.dtype}, got {dtype}")
+            if device is not None and torch.device(device).type != pool.device.type:
+                raise ValueError(f"KVCache(pool=...): the pool lives on {pool.device}, got {device}")
+            device, dtype = pool.device, pool.dtype
+        dtype = torch.bfloat16 if dtype is None else dtype
+        self.ring, self.pool = bool(ring), pool
         self.window = _check_window("KVCache", window) if ring else None
         self.n_layers, self.B, self.H, self.D, self.capacity = n_layers, B, H, D, capacity
         self.device, self.dtype = torch.device(device if device is not None else "cpu"), dtype
-        self.k = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
-        self.v = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
         self.k_scale = self.v_scale = None
-        if dtype == FP8:
-            self.k_scale = [torch.zeros(B, H, capacity, device=self.device) for _ in range(n_layers)]
-            self.v_scale = [torch.zeros(B, H, capacity, device=self.device) for _ in range(n_layers)]
+        if pool is not None:  # the pool's tensors: the page stride stands where the batch stride stands
+            self.k, self.v, self.k_scale, self.v_scale = pool.k, pool.v, pool.k_scale, pool.v_scale
+            self.page_table = torch.full((B, capacity // PAGE), -1, device=self.device, dtype=torch.int32)
+            self._table = [[-1] * (capacity // PAGE) for _ in range(B)]  # the host mirror of page_table
+            self._hlen = [0] * B  # and of lens
+        else:
+            self.k = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+            self.v = [torch.zeros(B, H, capacity, D, device=self.device, dtype=dtype) for _ in range(n_layers)]
+            if dtype == FP8:
+                self.k_scale = [torch.zeros(B, H, capacity, device=self.device) for _ in range(n_layers)]
+                self.v_scale = [torch.zeros(B, H, capacity, device=self.device) for _ in range(n_layers)]
         self.lens = torch.zeros(B, device=self.device, dtype=torch.int32)
         self._lens_after = torch.zeros(B, device=self.device, dtype=torch.int32)  # lens_after()'s buffer
         self._bound, self._pinned = 0, False
@@ -238,7 +351,13 @@ class KVCache:
     @property
     def nbytes(self) -> int:
         """Bytes this cache holds: K / V (codes), the scales of an FP8 cache, and the attention workspaces
-        allocated so far. ``lens`` and its step buffer (8 bytes per batch row) are not counted."""
+        allocated so far. ``lens`` and its step buffer (8 bytes per batch row) are not counted. A paged cache: the page
+        table, the workspaces and ``pages_held * pool.page_bytes``; a page shared between caches (or between rows of
+        one) is counted once in each cache that holds it, so the sum over caches can exceed ``pool.nbytes``."""
+        if self.pool is not None:
+            ts = [self.page_table, self.workspace, self.extend_workspace, self.chunk_workspace]
+            return (sum(t.numel() * t.element_size() for t in ts if t is not None)
+                    + self.pages_held * self.pool.page_bytes)
         ts = [*self.k, *self.v, *(self.k_scale or []), *(self.v_scale or []), self.workspace, self.extend_workspace,
               self.chunk_workspace]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
@@ -261,6 +380,8 @@ class KVCache:
         """``lens += T`` on the device (capturable); the host bound follows."""
         self.lens.add_(T)
         self._bound = self._bound + T if self.ring else min(self._bound + T, self.capacity)
+        if self.pool is not None:
+            self._hlen = [n + T for n in self._hlen]
 
     def set_lens(self, lens) -> None:
         """Set per-row lengths from the host (a sync: not for a captured step)."""
@@ -272,6 +393,8 @@ class KVCache:
             raise ValueError(f"set_lens: {self.B} lengths in 0..{self.capacity} expected")
         self.lens.copy_(torch.tensor(vals, dtype=torch.int32))
         self._bound = max(vals)
+        if self.pool is not None:  # pages are not touched: reserve(0) makes the new lengths present
+            self._hlen = vals
 
     def pin_bound(self) -> None:
         """Size the attention grid for the whole capacity: what a step captured once must use."""
@@ -289,10 +412,130 @@ class KVCache:
                              f"overwritten), got {n}")
         self.lens.sub_(n).clamp_(min=0)
         self._bound = max(self._bound - n, 0)
+        if self.pool is not None:  # the pages stay held; a shared one is copied by the reserve before the next append
+            self._hlen = [max(m - n, 0) for m in self._hlen]
 
     def reset(self) -> None:
+        """Lengths to 0. A paged cache also gives its pages back (``release``)."""
+        if self.pool is not None:
+            self.release()
+            return
         self.lens.zero_()
         self._bound = 0
+
+    # ---- a paged cache's pages (the module docstring's page rule): plain host code, no kernel ----------------------
+    def _paged(self, what: str) -> "PagePool":
+        if self.pool is None:
+            raise ValueError(f"{what}: a paged cache expected (KVCache(..., pool=PagePool(...)))")
+        return self.pool
+
+    @property
+    def pages_held(self) -> int:
+        """Table entries that name a page (a page two rows share counts twice)."""
+        self._paged("pages_held")
+        return sum(p >= 0 for row in self._table for p in row)
+
+    def _push_table(self) -> None:
+        """The host mirror to the device: one host-to-device copy."""
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("KVCache: the page table cannot change inside a stream capture: reserve the whole "
+                               "length before capturing")
+        self.page_table.copy_(torch.tensor(self._table, dtype=torch.int32))
+
+    def reserve(self, T: int = 1) -> None:
+        """Make positions ``0 .. len[b] + T - 1`` of every row present (clamped to the capacity) and the T positions
+        from ``len[b]`` on writable: missing pages come from the pool's free list, and a page about to be written that
+        another holder shares (reference count above 1) is replaced by a private copy first (copy-on-write: a device
+        copy of that page in every layer, scales included). Raises ``RuntimeError`` naming the pages needed and the
+        pages free when the pool is short, and changes nothing then. Inside a stream capture it raises if it would
+        have to change the table: a captured generation reserves its whole length before the capture. The lengths are
+        the host mirror's (``advance`` / ``rewind`` / ``set_lens`` / ``reset`` keep it exact)."""
+        pool = self._paged("reserve")
+        if T < 0:
+            raise ValueError("reserve: T >= 0 expected")
+        missing, shared = [], []  # (row, column) without a page; with a shared page about to be written
+        for b, n in enumerate(self._hlen):
+            end = min(n + T, self.capacity)
+            first_w = min(n, self.capacity) // PAGE  # the first column the step writes
+            for c in range(-(-end // PAGE)):
+                p = self._table[b][c]
+                if p < 0:
+                    missing.append((b, c))
+                elif T > 0 and c >= first_w and n < end and pool._ref[p] > 1:
+                    shared.append((b, c))
+        need = len(missing) + len(shared)
+        if need == 0:
+            return
+        if need > pool.pages_free:
+            raise RuntimeError(f"KVCache.reserve: {need} pages needed, {pool.pages_free} free (pool of "
+                               f"{pool.pages_total})")
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("KVCache.reserve: the page table would change inside a stream capture: reserve the "
+                               "whole length before capturing")
+        pages = pool._take(need)
+        for (b, c), p in zip(missing, pages):
+            self._table[b][c] = p
+        for (b, c), p in zip(shared, pages[len(missing):]):
+            old = self._table[b][c]
+            pool._copy(old, p)
+            pool._drop(old)
+            self._table[b][c] = p
+        self._push_table()
+
+    def fork(self, S: int, release: bool = False) -> "KVCache":
+        """A new cache of ``B * S`` rows on the same pool, row ``b * S + s`` holding the contents of row ``b``: the full
+        pages are shared (reference count + 1 per child), the last partial page, if any, is copied into a fresh page per
+        child; ``lens`` is copied. The parent stays valid; whoever appends to a shared page next gets a private copy from
+        ``reserve``. Raises ``RuntimeError`` (nothing changed) when the pool lacks the pages for the partial copies.
+        ``release=True``: fork and release the parent in one move: each row's last child takes over the parent's own
+        references (its partial page included, no copy), so ``S - 1`` partial copies per row suffice and no page is
+        held twice meanwhile; the parent ends empty, as after ``release()``."""
+        pool = self._paged("fork")
+        if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+            raise ValueError(f"fork: S >= 1 expected, got {S!r}")
+        partial = [b for b, n in enumerate(self._hlen) if n % PAGE and n < self.capacity]
+        for b, n in enumerate(self._hlen):
+            if any(p < 0 for p in self._table[b][:-(-min(n, self.capacity) // PAGE)]):
+                raise RuntimeError(f"fork: row {b} has positions without a page (reserve(0) after set_lens)")
+        copies = len(partial) * (S - 1 if release else S)
+        if copies > pool.pages_free:
+            raise RuntimeError(f"KVCache.fork: {copies} pages needed, {pool.pages_free} free (pool of "
+                               f"{pool.pages_total})")
+        child = KVCache(self.n_layers, self.B * S, self.H, self.D, self.capacity, pool=pool)
+        fresh = iter(pool._take(copies))
+        for b, n in enumerate(self._hlen):
+            n = min(n, self.capacity)
+            for s in range(S - 1 if release else S):
+                row = child._table[b * S + s]
+                for c in range(n // PAGE):
+                    row[c] = self._table[b][c]
+                    pool._ref[row[c]] += 1
+                if n % PAGE:
+                    row[n // PAGE] = next(fresh)
+                    pool._copy(self._table[b][n // PAGE], row[n // PAGE])
+            if release:  # the parent's row, pages reserved ahead included, passes to the last child as it is
+                child._table[b * S + S - 1], self._table[b] = self._table[b], [-1] * len(self._table[b])
+        child._hlen = [n for n in self._hlen for _ in range(S)]
+        child.lens.copy_(self.lens.repeat_interleave(S))
+        child._bound, child._pinned = self._bound, self._pinned
+        child._push_table()
+        if release:
+            self.release()  # nothing left to drop: lengths to 0, the empty table to the device
+        return child
+
+    def release(self) -> None:
+        """Drop the cache's references (a page whose count reaches 0 returns to the pool's free list) and set the
+        lengths to 0. The cache can be filled again."""
+        pool = self._paged("release")
+        for row in self._table:
+            for c, p in enumerate(row):
+                if p >= 0:
+                    pool._drop(p)
+                    row[c] = -1
+        self._hlen = [0] * self.B
+        self.lens.zero_()
+        self._bound = 0
+        self._push_table()
 
     def _ring_ws(self, attr: str, nbytes: int, what: str) -> torch.Tensor:
         """A ring's workspace ``attr`` of at least ``nbytes`` (the size follows the window and the row count, never the
@@ -360,7 +603,9 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None
         raise ValueError(f"kv_append: T = {qkv.shape[1]} rows exceed the ring's capacity {cache.capacity}")
     if rope is not None:
         # a ring rotates by the absolute position: a table row for every position of the step, whatever the capacity
-        need = cache._bound + qkv.shape[1] if cache.ring else cache.capacity
+        # (a paged cache's capacity is rounded up to whole pages: the table covers the positions of the step)
+        need = (cache._bound + qkv.shape[1] if cache.ring else
+                min(cache._bound + qkv.shape[1], cache.capacity) if cache.pool is not None else cache.capacity)
         if rope.dim() != 2 or rope.shape[1] != D or rope.shape[0] < need or rope.dtype != torch.float32:
             raise ValueError(f"kv_append: rope must be an fp32 [max_pos >= {need}, {D}] table, got "
                              f"{tuple(rope.shape)} {rope.dtype}")
@@ -369,6 +614,7 @@ def kv_append(qkv: torch.Tensor, cache: KVCache, layer: int, q_heads: int | None
             return
         from .rope import rotate_torch  # rows at or beyond the capacity have no table row here: left as they are
         qkv.copy_(rotate_torch(qkv, rope if cache.ring else rope[:cache.capacity], Hq, H, positions=cache.lens))
+        # (a paged row without a page is left unrotated by the kernel and rotated here: reserve() first, either way)
     if native:
         _kv_append_native(qkv, cache, layer, Hq, G)
     else:
@@ -381,6 +627,9 @@ def _kv_append_torch(qkv, cache: KVCache, layer: int, Hq: int) -> None:
     k, v = cache.k[layer], cache.v[layer]
     # [B, T, 3, H, D]: slot 0 the last H query heads (unused), slots 1 and 2 k and v
     x = qkv[:, :, (Hq - H) * D:].reshape(B, T, 3, H, D)
+    if cache.pool is not None:
+        _kv_append_paged_torch(x, cache, layer)
+        return
     if cache.fp8:
         _kv_append_fp8_torch(x, cache, layer)
         return
@@ -398,6 +647,29 @@ def _kv_append_torch(qkv, cache: KVCache, layer: int, Hq: int) -> None:
         v[b].index_copy_(1, rows[b][keep], x[b, keep, 2].transpose(0, 1).to(v.dtype))
 
 
+def _page_args(cache: KVCache) -> tuple:
+    """What a paged entry point takes before the stream: the device table, its row stride, the pool's page count."""
+    return cache.page_table.data_ptr(), cache.page_table.stride(0), cache.pool.n_pages
+
+
+def _kv_append_paged_torch(x, cache: KVCache, layer: int) -> None:
+    """The torch form of the paged append (the page rule): position ``lens[b] + t`` to page ``page_table[b, p // 256]``,
+    row ``p % 256``; a position at or beyond the capacity or without a page is dropped. ``x [B, T, 3, H, D]``."""
+    B, T = x.shape[:2]
+    pos = cache.lens.long().unsqueeze(1) + torch.arange(T, device=x.device).unsqueeze(0)  # [B, T]
+    page = cache.page_table.long().gather(1, (pos // PAGE).clamp(0, cache.page_table.shape[1] - 1))
+    keep = (pos >= 0) & (pos < cache.capacity) & (page >= 0)
+    pg, row = page[keep], (pos % PAGE)[keep]  # [N]
+    for s, t, sc in ((1, cache.k[layer], cache.k_scale), (2, cache.v[layer], cache.v_scale)):
+        rows = x[:, :, s][keep]  # [N, H, D]
+        if cache.fp8:
+            codes, scale = quantize_rows(rows)
+            t.view(torch.uint8)[pg, :, row] = codes.view(torch.uint8)
+            sc[layer][pg, :, row] = scale
+        else:
+            t[pg, :, row] = rows.to(t.dtype)
+
+
 def _kv_append_native(qkv, cache: KVCache, layer: int, Hq: int, G: int) -> None:
     """The append launch without rotation (``kernels/attn_kv.hip``)."""
     B, H, D, T = cache.B, cache.H, cache.D, qkv.shape[1]
@@ -406,11 +678,14 @@ def _kv_append_native(qkv, cache: KVCache, layer: int, Hq: int, G: int) -> None:
         raise ValueError("kv_append: bf16 qkv with a contiguous last dim expected")
     if cache.fp8 and D not in HEAD_DIMS:
         raise ValueError(f"kv_append: head dim in {HEAD_DIMS} expected for an FP8 cache on a GPU, got {D}")
-    fn, scales, tag = _entry("kfamd_kv_append_ring" if cache.ring else "kfamd_kv_append" if G == 1 else
-                             "kfamd_kv_append_gqa", cache, layer)  # the ring form takes the grouped signature
+    paged = cache.pool is not None
+    fn, scales, tag = _entry("kfamd_kv_append_paged" if paged else "kfamd_kv_append_ring" if cache.ring else
+                             "kfamd_kv_append" if G == 1 else "kfamd_kv_append_gqa", cache, layer)
+    # the ring and paged forms take the grouped signature; a paged cache's first stride is the page stride
     rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(), B, T,
-            *((H,) if G == 1 and not cache.ring else (Hq, H)), D, cache.capacity, qkv.stride(0), qkv.stride(1),
-            _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
+            *((H,) if G == 1 and not cache.ring and not paged else (Hq, H)), D, cache.capacity, qkv.stride(0),
+            qkv.stride(1), _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])),
+            *(_page_args(cache) if paged else ()), _stream_ptr(qkv))
     _lib.check(rc, f"kv_append[{tag}B={B} T={T} Hq={Hq} H={H} D={D}]")
 
 
@@ -425,10 +700,13 @@ def _kv_append_rope_native(qkv, cache: KVCache, layer: int, Hq: int, rope: torch
                          f"a GPU, got {D}, {k.dtype}")
     if not rope.is_cuda or rope.device != qkv.device or not rope.is_contiguous():
         raise ValueError("kv_append: rope must be a contiguous table on the activation's device")
-    fn, scales, tag = _entry("kfamd_kv_append_rope_ring" if cache.ring else "kfamd_kv_append_rope", cache, layer)
+    paged = cache.pool is not None
+    fn, scales, tag = _entry("kfamd_kv_append_rope_paged" if paged else "kfamd_kv_append_rope_ring" if cache.ring else
+                             "kfamd_kv_append_rope", cache, layer)
     rc = fn(qkv.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), cache.lens.data_ptr(),
             rope.data_ptr(), rope.shape[0], B, T, Hq, H, D, cache.capacity, qkv.stride(0), qkv.stride(1),
-            _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])), _stream_ptr(qkv))
+            _ll(*k.stride()[:3], *v.stride()[:3], *(n for s in scales for n in s.stride()[:2])),
+            *(_page_args(cache) if paged else ()), _stream_ptr(qkv))
     _lib.check(rc, f"kv_append[rope {tag}B={B} T={T} Hq={Hq} H={H} D={D}]")
 
 
@@ -448,14 +726,38 @@ def _kv_append_fp8_torch(x, cache: KVCache, layer: int) -> None:
             scales[b].index_copy_(1, rows[b][keep], sc[b, keep].transpose(0, 1))
 
 
-def _dequantized_prefix(cache: KVCache, layer: int, lens, n: int, dtype):
+def _dequantized_prefix(cache: KVCache, layer: int, lens, n: int, dtype, kv=None):
     """K, V of an FP8 cache's first n rows as ``dtype`` tensors, the rows at or beyond ``lens[b]`` zeroed
-    (dead codes and scales may be NaN): what the torch reference attends."""
+    (dead codes and scales may be NaN): what the torch reference attends. ``kv``: ``(k, v, k_scale, v_scale)`` in flat
+    ``[B, H, capacity, ...]`` order instead of the cache's own tensors (a paged cache's gathered view)."""
+    ck, cv, cks, cvs = kv if kv is not None else (cache.k[layer], cache.v[layer], cache.k_scale[layer],
+                                                  cache.v_scale[layer])
     live = (torch.arange(n, device=lens.device).view(1, 1, n) < lens.view(-1, 1, 1)).unsqueeze(-1)
     zero = torch.zeros((), device=lens.device)
-    k = torch.where(live, dequantize_rows(cache.k[layer][:, :, :n], cache.k_scale[layer][:, :, :n]), zero)
-    v = torch.where(live, dequantize_rows(cache.v[layer][:, :, :n], cache.v_scale[layer][:, :, :n]), zero)
+    k = torch.where(live, dequantize_rows(ck[:, :, :n], cks[:, :, :n]), zero)
+    v = torch.where(live, dequantize_rows(cv[:, :, :n], cvs[:, :, :n]), zero)
     return k.to(dtype), v.to(dtype)
+
+
+def _paged_view(cache: KVCache, layer: int):
+    """The torch path's view of a paged cache (the page rule): ``(k, v, k_scale, v_scale)`` with every row's pages
+    gathered into flat ``[B, H, capacity, D]`` / ``[B, H, capacity]`` order (the scales ``None`` for a bf16 cache).
+    Positions without a page read as zeros (codes 0, scale 0). Also what a test compares a flat cache with."""
+    B, H, C, D = cache.B, cache.H, cache.capacity, cache.D
+    table = cache.page_table.long()  # [B, C // 256]
+    absent = (table < 0).repeat_interleave(PAGE, dim=1).view(B, 1, C)
+    idx = table.clamp(min=0)
+
+    def gather(t):
+        if t is None:
+            return None
+        u = t.view(torch.uint8) if t.dtype == FP8 else t
+        g = u[idx]  # [B, C // 256, H, 256, (D)]
+        g = g.transpose(1, 2).reshape(B, H, C, *g.shape[4:])
+        g = g.masked_fill(absent.unsqueeze(-1) if g.dim() == 4 else absent, 0)
+        return g.view(FP8) if t.dtype == FP8 else g
+    sc = (cache.k_scale[layer], cache.v_scale[layer]) if cache.fp8 else (None, None)
+    return gather(cache.k[layer]), gather(cache.v[layer]), gather(sc[0]), gather(sc[1])
 
 
 def _ring_view(cache: KVCache, layer: int, lens, dtype):
@@ -499,8 +801,11 @@ def _ring_check(what: str, cache: KVCache, window, T: int, t_bound) -> int:
     return window
 
 
-def _check_window(what: str, window) -> int | None:
-    """``window`` as the ops take it: ``None`` or an ``int >= 1`` (``bool`` rejected)."""
+def _check_window(what: str, window, cache: "KVCache | None" = None) -> int | None:
+    """``window`` as the ops take it: ``None`` or an ``int >= 1`` (``bool`` rejected); none on a paged ``cache``."""
+    if window is not None and cache is not None and cache.pool is not None:
+        raise ValueError(f"{what}: window= cannot be given on a paged cache (paged with a window is not built), got "
+                         f"{window!r}")
     if window is None:
         return None
     if isinstance(window, bool) or not isinstance(window, int) or window < 1:
@@ -568,6 +873,10 @@ def _attend_torch(reference, q, cache: KVCache, layer: int, G: int, scale, out, 
     k, v = cache.k[layer], cache.v[layer]
     if cache.ring:  # the live slots in absolute order, then the same masked softmax
         k, v, lens = _ring_view(cache, layer, lens, dtype)
+    elif cache.pool is not None:  # every row's pages in flat order, then the flat references
+        k, v, ks, vs = _paged_view(cache, layer)
+        if cache.fp8:
+            k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), dtype, (k, v, ks, vs))
     elif cache.fp8:
         k, v = _dequantized_prefix(cache, layer, lens, max(min(t_bound, cache.capacity), 1), dtype)
     o, lse = reference(q, *_expand_kv(k, v, G), lens, scale, window)
@@ -608,14 +917,15 @@ def _attend_launch(what: str, name: str, q, cache: KVCache, layer: int, out, len
     else:
         T, qs, os, dims = 1, (q.stride(0), 0, q.stride(1)), (out.stride(0), 0, out.stride(1)), f"H={q.shape[1]} G={G}"
     lse = torch.empty(q.shape[:-1], device=q.device, dtype=torch.float32) if return_lse else None
-    grouped = G > 1 or window is not None
-    fn, scales, tag = _entry(name + ("_ring" if cache.ring else "_win" if window is not None else "_gqa" if grouped
-                                     else ""), cache, layer)  # a ring: t_bound is the capacity
+    paged = cache.pool is not None  # the grouped signature with the page table before the stream
+    grouped = G > 1 or window is not None or paged
+    fn, scales, tag = _entry(name + ("_paged" if paged else "_ring" if cache.ring else "_win" if window is not None
+                                     else "_gqa" if grouped else ""), cache, layer)  # a ring: t_bound is the capacity
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
             lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, *((cache.H, G) if grouped else (cache.H,)),
             D, T, t_bound, *(() if window is None else (min(window, cache.capacity),)), scale,
             _ll(*qs, *k.stride()[:3], *v.stride()[:3], *os, *(n for s in scales for n in s.stride()[:2])),
-            _stream_ptr(q))
+            *(_page_args(cache) if paged else ()), _stream_ptr(q))
     _lib.check(rc, f"{what}[{tag}B={B} {dims} D={D} t_bound={t_bound}{'' if window is None else f' window={window}'}]")
     return (out, lse) if return_lse else out
 
@@ -632,7 +942,7 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     extend / chunk workspace, allocated on first use and never inside a capture). ``window=W``: the last W of those
     keys only (the module docstring's rule), on the windowed kernels of the same routing."""
     what = "attention_decode"
-    window = _check_window(what, window)
+    window = _check_window(what, window, cache)
     if cache.ring:
         window, t_bound = _ring_check(what, cache, window, 1, t_bound), cache.capacity
     _, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound, rank=3)
@@ -660,15 +970,16 @@ def attention_decode(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     B, H, D = q.shape
     k, v = cache.k[layer], cache.v[layer]
     lse = torch.empty(B, H, device=q.device, dtype=torch.float32) if return_lse else None
-    fn, scales, tag = _entry("kfamd_attn_decode_ring" if cache.ring else "kfamd_attn_decode" if window is None else
-                             "kfamd_attn_decode_win", cache, layer)
+    paged = cache.pool is not None
+    fn, scales, tag = _entry("kfamd_attn_decode_paged" if paged else "kfamd_attn_decode_ring" if cache.ring else
+                             "kfamd_attn_decode" if window is None else "kfamd_attn_decode_win", cache, layer)
     ws = cache.workspace if not cache.ring else cache._ring_ws(
         "workspace", _lib.lib().kfamd_attn_decode_ring_workspace(B, H, D, window), what)
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), *(s.data_ptr() for s in scales), lens.data_ptr(), out.data_ptr(),
             lse.data_ptr() if lse is not None else None, ws.data_ptr(), B, H, D, t_bound,
             *(() if window is None else (min(window, cache.capacity),)), scale,
             _ll(q.stride(0), q.stride(1), *k.stride()[:3], *v.stride()[:3], out.stride(0), out.stride(1),
-                *(n for s in scales for n in s.stride()[:2])), _stream_ptr(q))
+                *(n for s in scales for n in s.stride()[:2])), *(_page_args(cache) if paged else ()), _stream_ptr(q))
     _lib.check(rc, f"attention_decode[{tag}B={B} H={H} D={D} t_bound={t_bound}]")
     return (out, lse) if return_lse else out
 
@@ -686,7 +997,7 @@ def attention_extend(q: torch.Tensor, cache: KVCache, layer: int, scale: float |
     ``T * G <= MAX_EXTEND_ROWS``; with G > 1, ``GQA_MFMA_MIN_ROWS`` rows or more run ``attention_chunk``'s kernel.
     ``window=W``: each row sees the last W keys up to its own only (the module docstring's rule)."""
     what = "attention_extend"
-    window = _check_window(what, window)
+    window = _check_window(what, window, cache)
     if cache.ring:
         window, t_bound = _ring_check(what, cache, window, q.shape[1] if q.dim() == 4 else 1, t_bound), cache.capacity
     T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
@@ -719,7 +1030,7 @@ def attention_chunk(q: torch.Tensor, cache: KVCache, layer: int, scale: float | 
     (``T * G <= 65535``). ``window=W``: each row sees the last W keys up to its own only (the module docstring's
     rule); the key tiles below the lowest lower bound of a query tile's rows are not read."""
     what = "attention_chunk"
-    window = _check_window(what, window)
+    window = _check_window(what, window, cache)
     if cache.ring:
         window, t_bound = _ring_check(what, cache, window, q.shape[1] if q.dim() == 4 else 1, t_bound), cache.capacity
     T, G, scale, lens, t_bound = _attend_args(what, q, cache, scale, lens, t_bound)
