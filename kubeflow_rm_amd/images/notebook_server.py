@@ -206,6 +206,13 @@ def _warmup_torch() -> dict:
     # stream and caching allocator, the result copied back and spot-checked on the host: proves torch's
     # GPU runtime and the pod's GPU work without launching (and so code-object loading) any of torch's
     # own kernels before Ready — the first of those costs ~100 ms and lands in the user's first cell
+    # The host side (two 1M-element operands, the spot check) runs on the calling thread alone. Left to
+    # torch's intra-op pool, its first parallel op starts the pool here, before Ready, and on a node with
+    # no more CPUs than the pool has threads (16 and 16) the workers spin at every barrier while one of
+    # them waits behind the node's own processes for a CPU: ~100 ms and ~1.5 s of CPU time for a few ms
+    # of arithmetic. The pool keeps the container's size and starts with the user's first parallel op.
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
     g = torch.Generator().manual_seed(0)
     ha = (torch.rand(1024, 1024, generator=g) * 2 - 1).to(torch.bfloat16)
     hb = (torch.rand(1024, 1024, generator=g) * 2 - 1).to(torch.bfloat16)
@@ -222,6 +229,7 @@ def _warmup_torch() -> dict:
     err = (got - ref).abs().max().item()
     ok = bool(torch.isfinite(got).all().item()) and err <= 1e-2 * ref.abs().max().item() + 1e-2
     t4 = time.perf_counter()
+    torch.set_num_threads(threads)
     return {"ok": ok, "check_ms": round((t4 - t3) * 1e3, 1), "import_torch_ms": round((t1 - t0) * 1e3, 1), "import_ops_ms": round((t2 - t1) * 1e3, 1),
             "first_gemm_ms": round((t3 - t2) * 1e3, 1), "total_ms": round((t3 - t0) * 1e3, 1), "hip_preinit": (pre or {}).get("mode"), "preinit_join_ms": round((t_join - t1) * 1e3, 1),
             "preinit_ms": dict(PREINIT),
