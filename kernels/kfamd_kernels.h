@@ -587,6 +587,31 @@ int kfamd_gemm_nt_skinny_w8_glu_path(int path, const void* A, const void* codes,
 int kfamd_gemm_nt_skinny_w8_glu_tiles(int path, int tiles, const void* A, const void* codes, const float* wscale,
                                       void* C, const void* bias, int M, int N, int K, long long lda, long long ldw,
                                       long long ldc, float alpha, void* stream);
+// The same on OCP MXFP4 weights (gemm_skinny_mx4.hip; ops.MXFP4Weight states the format): codes [N][K / 2] bytes, two
+// e2m1 codes per byte (element 2i in the low nibble), row stride ldw_bytes; scales [N][K / 32] e8m0 bytes, row stride
+// lds, one per group of 32 elements, 1 .. 254 (2^(e - 127)). C[M][N] = act(alpha * (A . W^T) + bias[n]) (+ R), W the
+// dequantised weight; no row scale. K >= 32, K % 32 == 0, codes 16-B aligned, ldw_bytes % 16 == 0, ldw_bytes >= K / 2,
+// lds >= K / 32, A as above; the scales need no alignment. Return codes, path, tiles and the gated form as the W8 set.
+int kfamd_gemm_nt_skinny_mx4(const void* A, const void* codes, const void* scales, void* C, const void* bias,
+                             const void* R, int M, int N, int K, long long lda, long long ldw_bytes, long long lds,
+                             long long ldc, long long ldr, float alpha, int act, void* stream);
+int kfamd_gemm_nt_skinny_mx4_path(int path, const void* A, const void* codes, const void* scales, void* C,
+                                  const void* bias, const void* R, int M, int N, int K, long long lda,
+                                  long long ldw_bytes, long long lds, long long ldc, long long ldr, float alpha, int act,
+                                  void* stream);
+int kfamd_gemm_nt_skinny_mx4_tiles(int path, int tiles, const void* A, const void* codes, const void* scales, void* C,
+                                   const void* bias, const void* R, int M, int N, int K, long long lda,
+                                   long long ldw_bytes, long long lds, long long ldc, long long ldr, float alpha,
+                                   int act, void* stream);
+int kfamd_gemm_nt_skinny_mx4_glu(const void* A, const void* codes, const void* scales, void* C, const void* bias, int M,
+                                 int N, int K, long long lda, long long ldw_bytes, long long lds, long long ldc,
+                                 float alpha, void* stream);
+int kfamd_gemm_nt_skinny_mx4_glu_path(int path, const void* A, const void* codes, const void* scales, void* C,
+                                      const void* bias, int M, int N, int K, long long lda, long long ldw_bytes,
+                                      long long lds, long long ldc, float alpha, void* stream);
+int kfamd_gemm_nt_skinny_mx4_glu_tiles(int path, int tiles, const void* A, const void* codes, const void* scales,
+                                       void* C, const void* bias, int M, int N, int K, long long lda,
+                                       long long ldw_bytes, long long lds, long long ldc, float alpha, void* stream);
 // The gate as its own pass (swiglu_bf16.hip), any row count: z [rows][2F] (row stride ldz >= 2F) -> h [rows][F]
 // (ldh >= F); backward dh [rows][F] (lddh), z -> dz [rows][2F] (lddz): dz[2j] = dh u s (1 + g (1 - s)),
 // dz[2j + 1] = dh silu(g), s = 1 / (1 + exp(-g)). 16-B loads and stores when F % 8 == 0, every stride % 8 == 0

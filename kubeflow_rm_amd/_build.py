@@ -76,12 +76,14 @@ def build_diag_kernels() -> Path:
 # forces AGPRs — the default AGPR form shuttled S / dP through 972 v_accvgpr moves per backward
 # iteration at D = 128 (329 with this); gpt-1b backward 665 -> 636 us, the forward ~1 % faster, the
 # D = 64 backward level (profiles/r5n_attn_ab, tools/attn_ab.py)
-TU_FLAGS = {"attention_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+TU_FLAGS = {"attention_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+            # no packed fp32 VALU ops in the MXFP4 weight-streaming kernel's FMA chains
+            "gemm_skinny_mx4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 # translation units whose kernels must not spill: several KV-cache attention instantiations sit at the VGPR
 # budget (attn_chunk_split<Fp8Rows, 128, true>: 255 of 256), and a spill there costs time without failing any
 # test. The compiler's resource remarks are read at build time; a kernel with scratch fails the build.
-NO_SCRATCH_TUS = ("attn_kv.hip", "attn_kv_mfma.hip", "rope_bf16.hip")
+NO_SCRATCH_TUS = ("attn_kv.hip", "attn_kv_mfma.hip", "rope_bf16.hip", "gemm_skinny_mx4.hip")
 
 
 def check_no_scratch(src: Path, remarks: str) -> None:

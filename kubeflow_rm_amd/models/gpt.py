@@ -383,11 +383,13 @@ def _sample(logits, temperature, top_k, generator):
 
 
 _LINEARS = ("qkv", "proj", "fc1", "fc2")
+_QUANTIZED = (ops.QuantizedWeight, ops.MXFP4Weight)
 
 class DecodeWeights:
-    """8-bit copies of a ``GPT``'s projection weights for the KV-cache steps (``GPT.decode_weights``):
-    ``blocks[i]`` maps "qkv" / "proj" / "fc1" / "fc2" to an ``ops.QuantizedWeight`` (to the model's own bf16 weight
-    for a matrix whose inner dimension is no multiple of 16, which the 8-bit kernel does not take), ``head`` is the
+    """8-bit (or MXFP4) copies of a ``GPT``'s projection weights for the KV-cache steps (``GPT.decode_weights``):
+    ``blocks[i]`` maps "qkv" / "proj" / "fc1" / "fc2" to an ``ops.QuantizedWeight`` or ``ops.MXFP4Weight`` (to the
+    model's own bf16 weight for a matrix whose inner dimension is no multiple of 16, for MXFP4 of 32, which the
+    quantised kernel does not take), ``head`` is the
     quantised LM head (the tied embedding; the embedding gather itself keeps the model's ``tok``). The
     biases are the model's own. ``unquantized`` names the matrices left in bf16 ("blocks.0.fc2", ...; empty when all
     were quantised). Plain tensors: neither parameters nor buffers."""
@@ -395,8 +397,8 @@ class DecodeWeights:
     def __init__(self, blocks: list, head, key: tuple):
         self.blocks, self.head, self._key = blocks, head, key
         self.unquantized = [f"blocks.{i}.{n}" for i, b in enumerate(blocks) for n in _LINEARS
-                            if not isinstance(b[n], ops.QuantizedWeight)]
-        if not isinstance(head, ops.QuantizedWeight):
+                            if not isinstance(b[n], _QUANTIZED)]
+        if not isinstance(head, _QUANTIZED):
             self.unquantized.append("head")
 
     def matrices(self) -> list:
@@ -404,13 +406,13 @@ class DecodeWeights:
 
     @property
     def nbytes(self) -> int:
-        """The sum of the quantised matrices' ``nbytes`` (codes + fp32 row scales)."""
+        """The sum of the matrices' ``nbytes`` (codes + scales; a matrix left in bf16 counts its bf16 bytes)."""
         return sum(q.nbytes for q in self.matrices())
 
 
 def _flinear(x, w, bias=None):
-    """``F.linear`` of the torch path; a ``QuantizedWeight`` enters as its dequantised value in x's dtype."""
-    if isinstance(w, ops.QuantizedWeight):
+    """``F.linear`` of the torch path; a quantised weight enters as its dequantised value in x's dtype."""
+    if isinstance(w, _QUANTIZED):
         w = w.dequantize().to(x.dtype)
     return F.linear(x, w, bias)
 
@@ -699,12 +701,19 @@ class GPT(torch.nn.Module):
         in-place update (a training step) requantises what changed and returns a new object. An object kept
         across an update is stale and out of contract: ask the model again after training.
 
+        ``dtype="mxfp4"`` (``torch.float4_e2m1fn_x2`` is the same request): ``ops.MXFP4Weight`` copies instead, 4.25
+        bits per weight (``ops.quantize_weight(w, dtype="mxfp4")``); here a matrix stays bf16 when its inner dimension
+        is no multiple of 32. Each format has its own memo: asking for one neither returns nor evicts the other's.
+
         Which steps read them: those of up to 16 rows, see ``extend``; ``prefill`` never does."""
-        if dtype != torch.float8_e4m3fn:
-            raise ValueError(f"decode_weights: torch.float8_e4m3fn expected, got {dtype}")
+        mx4 = ops.gemm.is_mxfp4(dtype)
+        if not mx4 and dtype != torch.float8_e4m3fn:
+            raise ValueError(f'decode_weights: torch.float8_e4m3fn or "mxfp4" expected, got {dtype}')
+        kq, fmt = (32, "mxfp4") if mx4 else (16, None)
+        slot = "_decode_weights_mxfp4" if mx4 else "_decode_weights"
         srcs = [getattr(blk, n).weight for blk in self.blocks for n in _LINEARS] + [self.tok]
         key = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in srcs)
-        memo = self.__dict__.get("_decode_weights")
+        memo = self.__dict__.get(slot)
         if memo is not None and memo._key == key:
             return memo
         old = memo.matrices() if memo is not None and len(memo._key) == len(key) else [None] * len(srcs)
@@ -712,16 +721,16 @@ class GPT(torch.nn.Module):
             # the W8A16 kernel takes K % 16 == 0: a matrix off that grid (fc2 of a Llama-style d_ff such as 344 or
             # 11008 / tp) stays the model's bf16 parameter, and its steps run the bf16 weight-streaming kernel
             qs = [q if q is not None and memo._key[i] == key[i]
-                  else (ops.quantize_weight(p.detach()) if p.shape[1] % 16 == 0 else p.detach())
+                  else (ops.quantize_weight(p.detach(), dtype=fmt) if p.shape[1] % kq == 0 else p.detach())
                   for i, (p, q) in enumerate(zip(srcs, old))]
         n = len(_LINEARS)
         blocks = [dict(zip(_LINEARS, qs[i * n:(i + 1) * n])) for i in range(len(self.blocks))]
         memo = DecodeWeights(blocks, qs[-1], key)
         if memo.unquantized:  # once per (memoised) object: the caller asked for 8-bit weights and gets a mixed set
             warnings.warn(f"decode_weights: {len(memo.unquantized)} matrices keep bf16 weights (inner dimension no "
-                          f"multiple of 16): {', '.join(memo.unquantized[:4])}"
+                          f"multiple of {kq}): {', '.join(memo.unquantized[:4])}"
                           f"{', ...' if len(memo.unquantized) > 4 else ''}", stacklevel=2)
-        self.__dict__["_decode_weights"] = memo  # not a parameter, buffer or submodule
+        self.__dict__[slot] = memo  # not a parameter, buffer or submodule
         return memo
 
     def _weight_selector(self, weights, rows: int):
@@ -931,7 +940,7 @@ class GPT(torch.nn.Module):
         ``kv_dtype``: what the KV cache stores (``new_cache``); ``torch.float8_e4m3fn`` halves its bytes.
         With a draft, both the target's and the draft's caches use it.
 
-        ``weight_dtype``: ``torch.float8_e4m3fn`` decodes on ``self.decode_weights()`` (and the draft on its
+        ``weight_dtype``: ``torch.float8_e4m3fn`` or ``"mxfp4"`` decodes on ``self.decode_weights(weight_dtype)`` (and the draft on its
         own): every step of up to 16 rows reads 8-bit projection weights and LM head, half the bytes of a
         small-batch step; the prompt's ``prefill`` and steps of more rows read the bf16 weights. It combines
         freely with ``kv_dtype`` and ``graph``. Any other dtype raises.
@@ -1003,8 +1012,10 @@ class GPT(torch.nn.Module):
             raise ValueError('generate(top_p=..., stop_token=...) need sampler="fused"')
         if sampler == "fused" and draft is not None:
             raise ValueError('generate(draft=...) keeps its greedy sampler: sampler="fused" cannot be combined with it')
-        if weight_dtype is not None and weight_dtype != torch.float8_e4m3fn:
-            raise ValueError(f"generate(weight_dtype=...): None or torch.float8_e4m3fn expected, got {weight_dtype}")
+        if (weight_dtype is not None and weight_dtype != torch.float8_e4m3fn
+                and not ops.gemm.is_mxfp4(weight_dtype)):
+            raise ValueError(f'generate(weight_dtype=...): None, torch.float8_e4m3fn or "mxfp4" expected, got '
+                             f"{weight_dtype}")
         B, T0 = idx.shape
         total = T0 + max_new_tokens
         if max_new_tokens < 0 or T0 < 1 or total > self.cfg.max_seq:
@@ -1019,8 +1030,10 @@ class GPT(torch.nn.Module):
                 raise ValueError(f"prompt + max_new_tokens must fit the draft's max_seq {draft.cfg.max_seq}")
             out, stats = ((idx.clone(), {"target_steps": 0, "proposed": 0, "accepted": 0}) if max_new_tokens == 0
                           else self._generate_draft(idx, max_new_tokens, draft, int(lookahead), kv_dtype,
-                                                    self.decode_weights() if weight_dtype is not None else None,
-                                                    draft.decode_weights() if weight_dtype is not None else None,
+                                                    self.decode_weights(weight_dtype) if weight_dtype is not None
+                                                    else None,
+                                                    draft.decode_weights(weight_dtype) if weight_dtype is not None
+                                                    else None,
                                                     prefill_chunk if ring else None))
             return (out, stats) if return_stats else out
         if return_stats:
@@ -1051,7 +1064,7 @@ class GPT(torch.nn.Module):
             logits, idx, B = logits.repeat_interleave(S, 0), idx.repeat_interleave(S, 0), B * S
         if paged and graph:
             cache.reserve(max_new_tokens - 1)  # a capture cannot take pages: every position the replays append
-        weights = self.decode_weights() if weight_dtype is not None else None
+        weights = self.decode_weights(weight_dtype) if weight_dtype is not None else None
         if sampler == "fused":
             out = self._generate_fused(idx, logits, cache, weights, max_new_tokens, temperature, top_k, top_p,
                                        stop_token, generator, graph)

@@ -222,6 +222,18 @@ _SIGNATURES = {
                                                  c_ll, c_float, c_vp]),
     "kfamd_gemm_nt_skinny_w8_glu_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll,
                                                   c_ll, c_ll, c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_mx4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
+                                         c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_mx4_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,
+                                              c_ll, c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_mx4_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                               c_ll, c_ll, c_ll, c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_skinny_mx4_glu": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll,
+                                             c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_mx4_glu_path": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll,
+                                                  c_ll, c_ll, c_float, c_vp]),
+    "kfamd_gemm_nt_skinny_mx4_glu_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                                   c_ll, c_ll, c_ll, c_ll, c_float, c_vp]),
     "kfamd_swiglu_fwd_bf16": (c_int, [c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_vp]),
     "kfamd_swiglu_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_ll, c_vp]),
     "kfamd_rmsnorm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp]),

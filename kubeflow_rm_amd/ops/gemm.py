@@ -55,14 +55,152 @@ class QuantizedWeight:
         return dequantize_rows(self.codes, self.scale)
 
 
-def quantize_weight(w: torch.Tensor) -> QuantizedWeight:
-    """A bf16 or fp32 weight ``[N, K]`` (CPU or GPU) as a ``QuantizedWeight``: exactly
-    ``ops.decode.quantize_rows(w)``, i.e. scale = row amax / 448 (1 for a zero row), codes =
-    RNE_e4m3(clamp(w / scale, -448, 448))."""
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_FP4X2 = getattr(torch, "float4_e2m1fn_x2", None)
+_E8M0 = getattr(torch, "float8_e8m0fnu", None)
+MXFP4 = "mxfp4"
+
+
+def is_mxfp4(dtype) -> bool:
+    """``"mxfp4"`` or ``torch.float4_e2m1fn_x2``: the two spellings of the MXFP4 request."""
+    return dtype == MXFP4 or (_FP4X2 is not None and dtype is _FP4X2)
+
+
+class MXFP4Weight:
+    """An OCP microscaling FP4 (MXFP4, 4.25 bits per weight) weight ``[N, K]``, ``K % 32 == 0``, for ``gemm_nt``'s
+    weight-streaming kernel (``kernels/gemm_skinny_mx4.hip``). This docstring is the format rule; the kernel refers to
+    it.
+
+    ``codes [N, K / 2]`` ``uint8`` (for the kernel: unit inner stride, row stride a multiple of 16 bytes). Element ``k``
+    of a row is a 4-bit e2m1 code: bit 3 the sign, bits 2..0 an index into the magnitudes ``{0, 0.5, 1, 1.5, 2, 3, 4,
+    6}``. Byte ``i`` holds element ``2i`` in its low nibble and element ``2i + 1`` in its high nibble (the OCP /
+    ``torch.float4_e2m1fn_x2`` packing; a tensor of that dtype is taken as a view of the same bytes).
+
+    ``scales [N, K / 32]`` ``uint8``, contiguous, one per group of 32 elements: byte ``e`` is e8m0 and means
+    ``2^(e - 127)`` (``torch.float8_e8m0fnu`` is taken as a view). ``e`` in ``[1, 254]`` is in contract; 255 is the
+    format's NaN and 0 would be an fp32 zero as ``e << 23``: both out of contract.
+
+    The weight it stands for is ``dequantize()``: ``value(code) * 2^(e - 127)`` in fp32. Every in-contract entry whose
+    magnitude is zero or lies in ``[2^-126, 2^128)`` is exactly a bf16 value, so the kernel's widened operand is the
+    dequantised weight itself. Other magnitudes are out of contract for the kernel (the hardware convert's denormal
+    handling is not established)."""
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
+        if _FP4X2 is not None and codes.dtype is _FP4X2:
+            codes = codes.view(torch.uint8)
+        if _E8M0 is not None and scales.dtype is _E8M0:
+            scales = scales.view(torch.uint8)
+        if codes.dim() != 2 or codes.dtype != torch.uint8 or codes.shape[1] == 0 or codes.shape[1] % 16:
+            raise ValueError(f"MXFP4Weight: codes [N, K / 2] uint8 with K % 32 == 0 expected, got {tuple(codes.shape)} "
+                             f"{codes.dtype}")
+        want = (codes.shape[0], codes.shape[1] // 16)
+        if scales.dtype != torch.uint8 or tuple(scales.shape) != want or scales.device != codes.device:
+            raise ValueError(f"MXFP4Weight: scales uint8 {list(want)} on {codes.device} expected, got "
+                             f"{tuple(scales.shape)} {scales.dtype} on {scales.device}")
+        self.codes, self.scales = codes, scales
+        self._shape = torch.Size((codes.shape[0], 2 * codes.shape[1]))
+
+    @property
+    def shape(self) -> torch.Size:
+        return self._shape
+
+    @property
+    def device(self) -> torch.device:
+        return self.codes.device
+
+    @property
+    def nbytes(self) -> int:
+        """N * K / 2 code bytes + N * K / 32 scale bytes."""
+        return self.codes.numel() + self.scales.numel()
+
+    def dequantize(self) -> torch.Tensor:
+        """The fp32 weight ``value(code) * 2^(e - 127)`` the kernel multiplies by."""
+        N, K = self.shape
+        c = self.codes
+        nib = torch.stack((c & 0xF, c >> 4), -1).reshape(N, K).long()
+        mag = torch.tensor(_E2M1, dtype=torch.float32, device=c.device)[nib & 7]
+        val = torch.where((nib & 8) != 0, -mag, mag)
+        scale = (self.scales.to(torch.int32) << 23).view(torch.float32)
+        return (val.view(N, K // 32, 32) * scale.unsqueeze(-1)).view(N, K)
+
+
+def _quantize_mxfp4(w: torch.Tensor) -> MXFP4Weight:
+    """The OCP MX v1.0 rule. Per group of 32: e = clamp(floor(log2(amax)) - 2 + 127, 1, 254) (127 for a zero group),
+    floor(log2) taken from frexp; codes = w / 2^(e - 127) rounded to the nearest e2m1 magnitude, ties to the even code
+    index, saturating at 6; the sign bit is the input's (-0 stays -0)."""
+    N, K = w.shape
+    if K == 0 or K % 32:
+        raise ValueError(f"quantize_weight(dtype='mxfp4'): K % 32 == 0 expected, got K={K}")
+    g = w.detach().float().reshape(N, K // 32, 32)
+    amax = g.abs().amax(-1)
+    _, ex = torch.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax == 0, torch.full_like(ex, 127), (ex - 1 - 2 + 127).clamp(1, 254)).to(torch.int32)
+    a = (g / (e << 23).view(torch.float32).unsqueeze(-1)).abs()
+    # the midpoints between neighbouring magnitudes; a tie goes to the even index
+    idx = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (idx | (torch.signbit(g).to(torch.uint8) << 3)).reshape(N, K // 2, 2)
+    return MXFP4Weight((code[..., 0] | (code[..., 1] << 4)).contiguous(), e.to(torch.uint8).contiguous())
+
+
+def quantize_weight(w: torch.Tensor, dtype=None) -> "QuantizedWeight | MXFP4Weight":
+    """A bf16 or fp32 weight ``[N, K]`` (CPU or GPU) as a ``QuantizedWeight`` (``dtype`` ``None`` or
+    ``torch.float8_e4m3fn``): exactly ``ops.decode.quantize_rows(w)``, i.e. scale = row amax / 448 (1 for a zero row),
+    codes = RNE_e4m3(clamp(w / scale, -448, 448)); or, with ``dtype="mxfp4"`` (``torch.float4_e2m1fn_x2`` is the same
+    request), as an ``MXFP4Weight`` by the OCP MX v1.0 rule (``_quantize_mxfp4``; ``K % 32 == 0``)."""
     if w.dim() != 2 or w.dtype not in (torch.bfloat16, torch.float32):
         raise ValueError(f"quantize_weight: a 2-D bf16 or fp32 tensor expected, got {tuple(w.shape)} {w.dtype}")
+    if is_mxfp4(dtype):
+        return _quantize_mxfp4(w)
+    if dtype is not None and dtype != FP8:
+        raise ValueError(f'quantize_weight: dtype None, torch.float8_e4m3fn or "mxfp4" expected, got {dtype!r}')
     codes, scale = quantize_rows(w.detach())
     return QuantizedWeight(codes.contiguous(), scale.contiguous())
+
+
+def _gemm_nt_mx4(a, qw: MXFP4Weight, bias, residual, alpha, act, out, variant, tiles: int = 0):
+    """gemm_nt on an MXFP4Weight: the MXFP4 weight-streaming kernel or an error, never a dequantised copy."""
+    if variant not in SKINNY_PATHS:
+        raise ValueError(f"gemm_nt with an MXFP4Weight runs the weight-streaming kernel only: variant in "
+                         f"{sorted(SKINNY_PATHS)} expected, got {variant!r}")
+    _check_operand(a, "a")
+    codes, scales = qw.codes, qw.scales
+    if not codes.is_cuda or codes.device != a.device:
+        raise ValueError("gemm_nt: the MXFP4Weight must live on a's GPU")
+    N, K = qw.shape
+    if a.shape[-1] != K:
+        raise ValueError(f"inner dims differ: a has K={a.shape[-1]}, the weight has K={K}")
+    a2 = a.reshape(-1, K) if a.dim() != 2 else a
+    if a2.stride(-1) != 1:
+        a2 = a2.contiguous()
+    M = a2.shape[0]
+    if not 1 <= M <= SKINNY_MAX_M:
+        raise ValueError(f"gemm_nt[mx4] variant={variant!r}: 1 <= M <= {SKINNY_MAX_M} expected, got M={M}")
+    if codes.stride(1) != 1 or not scales.is_contiguous():
+        raise ValueError("gemm_nt[mx4]: codes with a unit inner stride and contiguous scales expected")
+    out_shape = (*a.shape[:-1], N)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.bfloat16, device=a.device)
+    else:
+        _check_operand(out, "out")
+        if out.device != a.device or tuple(out.shape) != tuple(out_shape):
+            raise ValueError(f"out must be a bf16 {tuple(out_shape)} tensor on {a.device}, got {tuple(out.shape)} on "
+                             f"{out.device}")
+    c2 = out.view(M, N)
+    if bias is not None:
+        _check_operand(bias, "bias")
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError("bias must be a contiguous [N] tensor")
+    r_ptr, ldr = None, 0
+    if residual is not None:
+        _check_operand(residual, "residual")
+        r2 = residual.reshape(M, N)
+        r_ptr, ldr = r2.data_ptr(), r2.stride(0)
+    rc = _lib.lib().kfamd_gemm_nt_skinny_mx4_tiles(
+        SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), codes.data_ptr(), scales.data_ptr(), c2.data_ptr(),
+        bias.data_ptr() if bias is not None else None, r_ptr, M, N, K, a2.stride(0), codes.stride(0), scales.stride(0),
+        c2.stride(0), ldr, float(alpha), ACTS[act], _stream_ptr(a))
+    _lib.check(rc, f"gemm_nt[skinny mx4 {M}x{N}x{K}]")
+    return out
 
 
 def _gemm_nt_w8(a, qw: QuantizedWeight, bias, residual, alpha, act, out, variant, tiles: int = 0):
@@ -114,11 +252,12 @@ def _gemm_nt_w8(a, qw: QuantizedWeight, bias, residual, alpha, act, out, variant
 
 def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
     """gemm_nt(act="swiglu"): the gated weight-streaming GEMM (ops/swiglu.py states the rule; w's rows are
-    interleaved gate / up, the output is [..., N / 2]) on a bf16 weight or a QuantizedWeight. Only the three skinny
+    interleaved gate / up, the output is [..., N / 2]) on a bf16 weight, a QuantizedWeight or an MXFP4Weight. Only the three skinny
     variants: "swiglu" is not an activation code of any other GEMM and never reaches one. CPU tensors and
     ops.torch_reference() compute the rule in torch, under the same argument checks."""
     from .swiglu import swiglu_reference
-    quant = isinstance(w, QuantizedWeight)
+    mx4 = isinstance(w, MXFP4Weight)
+    quant = mx4 or isinstance(w, QuantizedWeight)
     if variant not in SKINNY_PATHS:
         raise ValueError(f'gemm_nt(act="swiglu") runs the weight-streaming kernel only: variant in '
                          f"{sorted(SKINNY_PATHS)} expected, got {variant!r}")
@@ -138,7 +277,7 @@ def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
     if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
         raise ValueError("bias must be a contiguous [N] tensor")
     M = a.numel() // K if K else 0
-    kq = 16 if quant else 8
+    kq = 32 if mx4 else (16 if quant else 8)
     if not 1 <= M <= SKINNY_MAX_M or K < kq or K % kq:
         raise ValueError(f'gemm_nt(act="swiglu") variant={variant!r}: 1 <= M <= {SKINNY_MAX_M} and K % {kq} == 0 '
                          f"expected, got M={M} K={K}")
@@ -159,7 +298,7 @@ def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
     a2 = a.reshape(-1, K) if a.dim() != 2 else a
     if a2.stride(-1) != 1:
         a2 = a2.contiguous()
-    if wt.stride(1) != 1 or (quant and not w.scale.is_contiguous()):
+    if wt.stride(1) != 1 or (quant and not (w.scales if mx4 else w.scale).is_contiguous()):
         raise ValueError("gemm_nt: a weight with a unit inner stride (and a contiguous scale) expected")
     if out is None:
         out = torch.empty(out_shape, dtype=torch.bfloat16, device=a.device)
@@ -170,7 +309,12 @@ def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
         _check_operand(bias, "bias")
     bp = bias.data_ptr() if bias is not None else None
     L = _lib.lib()
-    if quant:
+    if mx4:
+        rc = L.kfamd_gemm_nt_skinny_mx4_glu_tiles(SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), wt.data_ptr(),
+                                                  w.scales.data_ptr(), c2.data_ptr(), bp, M, N, K, a2.stride(0),
+                                                  wt.stride(0), w.scales.stride(0), c2.stride(0), float(alpha),
+                                                  _stream_ptr(a))
+    elif quant:
         rc = L.kfamd_gemm_nt_skinny_w8_glu_tiles(SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), wt.data_ptr(),
                                                  w.scale.data_ptr(), c2.data_ptr(), bp, M, N, K, a2.stride(0),
                                                  wt.stride(0), c2.stride(0), float(alpha), _stream_ptr(a))
@@ -178,7 +322,7 @@ def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
         rc = L.kfamd_gemm_nt_skinny_bf16_glu_tiles(SKINNY_PATHS[variant], int(tiles), a2.data_ptr(), wt.data_ptr(),
                                                    c2.data_ptr(), bp, M, N, K, a2.stride(0), wt.stride(0), c2.stride(0),
                                                    float(alpha), _stream_ptr(a))
-    _lib.check(rc, f"gemm_nt[skinny {'w8 ' if quant else ''}swiglu {M}x{N}x{K}]")
+    _lib.check(rc, f"gemm_nt[skinny {'mx4 ' if mx4 else 'w8 ' if quant else ''}swiglu {M}x{N}x{K}]")
     return out
 
 
@@ -266,12 +410,13 @@ def _gemm_nt_padded(a3, b, bias, residual, alpha, act, out, batched, batch, M, N
     return out
 
 
-def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight", *, bias: torch.Tensor | None = None,
+def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight | MXFP4Weight", *, bias: torch.Tensor | None = None,
             residual: torch.Tensor | None = None, alpha: float = 1.0, act: str = "none",
             out: torch.Tensor | None = None, variant: str = "auto") -> torch.Tensor:
     """C = act(alpha * a @ b^T + bias) (+ residual). a: [..., M, K] or [B, M, K]; b: [N, K] or [B, N, K].
     ``b`` may be a ``QuantizedWeight`` with ``variant`` "skinny" / "skinny_valu" / "skinny_mfma" (M <= 16, K % 16 == 0):
-    the W8A16 weight-streaming kernel; every other variant or shape raises ``ValueError``.
+    the W8A16 weight-streaming kernel; every other variant or shape raises ``ValueError``. An ``MXFP4Weight`` likewise
+    (K % 32 == 0): the MXFP4 weight-streaming kernel (``kernels/gemm_skinny_mx4.hip``).
     ``act="swiglu"`` (the three skinny variants only; ``b``'s rows interleaved gate / up, ``ops/swiglu.py``): C =
     silu(z[..., 2j]) * z[..., 2j + 1] of z = alpha * a @ b^T + bias, shape ``[..., N / 2]``, in the GEMM's one launch;
     a residual, an odd N or any other variant raises ``ValueError``."""
@@ -279,6 +424,8 @@ def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight", *, bias: torch
         return _gemm_nt_swiglu(a, b, bias, residual, alpha, out, variant)
     if isinstance(b, QuantizedWeight):
         return _gemm_nt_w8(a, b, bias, residual, alpha, act, out, variant)
+    if isinstance(b, MXFP4Weight):
+        return _gemm_nt_mx4(a, b, bias, residual, alpha, act, out, variant)
     _check_operand(a, "a")
     _check_operand(b, "b")
     batched = b.dim() == 3

@@ -32,6 +32,13 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         weights x bf16 / FP8 KV cache x eager / graphed; one extend of T in {4, 16} tokens at B = 1;
         DecodeWeights.nbytes against the bf16 bytes of the same matrices; the max-abs logit difference of
         one step on FP8 against bf16 weights (gpt-tiny and gpt-1b; reported, not judged).
+  mx4   (not in the default list) MXFP4 decode weights against FP8 and bf16 ones, the w8 step's protocol. Kernel:
+        gemm_nt on an MXFP4Weight ("skinny", and every tile / row count of each form forced) against the FP8 and bf16
+        weight-streaming kernels on the gpt-1b projection shapes, and the gated form at N = 2F for F in {8192, 5504},
+        at M in {1, 2, 4, 8, 16}: us. Model: gpt-1b (gpt-small with --quick) ms/token near position 2048, B in
+        {1, 16}, bf16 / FP8 / MXFP4 weights x eager / graphed; one graphed extend of T in {4, 16} tokens at B = 1;
+        DecodeWeights.nbytes of each format; the max-abs logit difference of one step against bf16 weights (gpt-tiny
+        and gpt-1b; reported, not judged).
   sample  (not in the default list) the fused sampler. Kernel: ops.sample against the model's torch _sample
         at V = 32000, B in {1, 16}, interleaved blocks: greedy, top_k = 50, top_p = 0.9 and both (_sample has
         no top_p: those two rows time it at the nearest setting it has, named in the row). Model: gpt-small
@@ -95,7 +102,7 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 ROOF = 6.29e12
-STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "sample": 420,
+STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "mx4": 900, "sample": 420,
                 "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600, "ring": 900}
 WINDOW_WS = (256, 1024, 4095, 4096)
 GQA_GS = (1, 2, 4, 8, 16)
@@ -719,6 +726,169 @@ def step_w8(quick: bool):
         if batches:
             result["extend"] += _w8_extend_rows(model, name, quick)
         del model, W
+        torch.cuda.empty_cache()
+    return result
+
+
+def _mx4_kernel_rows(quick: bool):
+    """us per call on the gpt-1b shapes: bf16, FP8 and MXFP4 weights ("skinny"), then both MXFP4 forms and every tile /
+    row count forced; gated rows (N = 2F) time the MXFP4 forms and the FP8 gated launch."""
+    import torch
+    from kubeflow_rm_amd import ops
+    from kubeflow_rm_amd.ops.gemm import _gemm_nt_mx4, _gemm_nt_swiglu
+    rows = []
+    shapes = [(N, K, False) for N, K in GEMM_SHAPES] + [(16384, 2048, True), (11008, 2048, True)]
+    for N, K, glu in shapes[:2] + shapes[-1:] if quick else shapes:
+        ncopy = 2 if quick else max(2, -(-(1024 << 20) // (N * K)))  # the 4-bit copies alone exceed the cache
+        ws = [torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16) for _ in range(ncopy)]
+        q8 = [ops.quantize_weight(w) for w in ws]
+        q4 = [ops.quantize_weight(w, dtype="mxfp4") for w in ws]
+        if glu:
+            ws = ws[:2]  # not timed
+        bias = torch.randn(N, device="cuda").to(torch.bfloat16)
+        for M in GEMM_MS:
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            out = torch.empty(M, N // 2 if glu else N, device="cuda", dtype=torch.bfloat16)
+
+            def mx4(variant, tiles=0):
+                if glu:
+                    return lambda i: _gemm_nt_swiglu(a, q4[i % ncopy], bias, None, 1.0, out, variant, tiles)
+                return lambda i: _gemm_nt_mx4(a, q4[i % ncopy], bias, None, 1.0, "none", out, variant, tiles)
+
+            act = "swiglu" if glu else "none"
+            fns = {"w8": lambda i: ops.gemm_nt(a, q8[i % ncopy], bias=bias, act=act, out=out, variant="skinny"),
+                   "mx4": mx4("skinny"), **{f"mx4_mfma_t{t}": mx4("skinny_mfma", t) for t in (1, 2, 4)}}
+            if not glu:
+                fns["bf16"] = lambda i: ops.gemm_nt(a, ws[i % ncopy], bias=bias, out=out, variant="skinny")
+            if M <= 8:
+                fns.update({"mx4_valu_r2": mx4("skinny_valu", 2), "mx4_valu_r4": mx4("skinny_valu", 4)})
+            r = _time_blocks(fns, blocks=5 if quick else 7, iters=ncopy)
+            row = {"M": M, "N": N, "K": K, "gated": glu, "weight_copies": ncopy, **r}
+            row["w8_over_mx4"] = r["w8"]["median_us"] / r["mx4"]["median_us"]
+            row["separated"] = _sep({"min": r["mx4"]["min_us"], "max": r["mx4"]["max_us"]},
+                                    {"min": r["w8"]["min_us"], "max": r["w8"]["max_us"]})
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del ws, q8, q4
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _mx4_model_rows(model, name: str, B: int, quick: bool):
+    """ms/token around position 2048: bf16 / FP8 / MXFP4 weights x eager / graphed (bf16 KV cache), interleaved."""
+    import torch
+    cfg = model.cfg
+    prompt, new = 2048 - 128, 64 if quick else 128
+    weights = {"wbf16": None, "wfp8": model.decode_weights(), "wmx4": model.decode_weights("mxfp4")}
+    idx = torch.randint(0, cfg.vocab_size, (B, prompt), device="cuda")
+    toks = torch.randint(0, cfg.vocab_size, (new, B), device="cuda")
+
+    def run(w, mode):
+        cache = model.new_cache(B, prompt + new)
+        model.prefill(idx, cache)
+        W = weights[w]
+        step = ((lambda t: model.decode_step(t, cache, weights=W)) if mode != "graph"
+                else model.graphed_decode_step(cache, weights=W))
+        step(toks[0])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(1, new):
+            step(toks[i])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / (new - 1)
+
+    res = {f"{w}_{m}": [] for w in weights for m in ("eager", "graph")}
+    for _ in range(3 if quick else 7):  # interleaved
+        for key in res:
+            res[key].append(run(*key.split("_")))
+    row = {"model": name, "B": B, "prompt": prompt, "new": new}
+    for k, v in res.items():
+        row[k] = {"ms_per_token": statistics.median(v), "min": min(v), "max": max(v)}
+    for m in ("eager", "graph"):
+        row[f"fp8_over_mx4_{m}"] = row[f"wfp8_{m}"]["ms_per_token"] / row[f"wmx4_{m}"]["ms_per_token"]
+        row[f"separated_{m}"] = _sep(row[f"wfp8_{m}"], row[f"wmx4_{m}"])
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def _mx4_extend_rows(model, name: str, quick: bool):
+    """One graphed extend of T tokens at B = 1, position 1920: bf16, FP8 and MXFP4 weights."""
+    import torch
+    from kubeflow_rm_amd import ops
+    pos, cap, iters = 1920, 2048, 4
+    pinned = model.new_cache(1, cap)
+    for t in (*pinned.k, *pinned.v):
+        t.normal_()
+    pinned.set_lens([pos])
+    pinned.pin_bound()
+    rows = []
+    for T in (4, 16):
+        toks = torch.randint(0, model.cfg.vocab_size, (1, T), device="cuda")
+        graphs = {}
+        for k, w in (("wbf16", None), ("wfp8", model.decode_weights()), ("wmx4", model.decode_weights("mxfp4"))):
+            pinned.set_lens([pos])
+            graphs[k] = ops.GraphedCallable(lambda t, w=w: model.extend(t, pinned, weights=w), toks.clone(), warmup=1)
+        torch.cuda.synchronize()
+        times = {k: [] for k in graphs}
+        for b in range(-1, 5 if quick else 7):  # block -1: warm-up, not recorded
+            for k, f in graphs.items():
+                pinned.set_lens([pos])  # a sync, outside the timed region: every block starts at the same position
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    f(toks)
+                e1.record()
+                e1.synchronize()
+                if b >= 0:
+                    times[k].append(e0.elapsed_time(e1) / iters)  # ms per extend of T tokens
+        row = {"model": name, "B": 1, "T": T, "position": pos, "capacity": cap}
+        for k, v in times.items():
+            row[k] = {"median_ms": statistics.median(v), "min": min(v), "max": max(v)}
+        row["separated_fp8_mx4"] = _sep(row["wfp8"], row["wmx4"])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del graphs
+    return rows
+
+
+def _mx4_logit_row(model, name: str):
+    """max-abs logit difference of one decode step on MXFP4 (and FP8) against bf16 weights (one prompt; reported only)."""
+    import torch
+    cfg = model.cfg
+    T0 = min(128, cfg.max_seq - 2)
+    idx = torch.randint(0, cfg.vocab_size, (1, T0), device="cuda", generator=torch.Generator("cuda").manual_seed(0))
+    outs = []
+    for W in (None, model.decode_weights(), model.decode_weights("mxfp4")):
+        cache = model.new_cache(1, T0 + 1)
+        tok = model.prefill(idx, cache).argmax(-1)
+        outs.append(model.decode_step(tok, cache, weights=W).float())
+    row = {"model": name, "prompt": T0, "max_abs_logit": outs[0].abs().max().item()}
+    for k, o in (("fp8", outs[1]), ("mxfp4", outs[2])):
+        row[f"max_abs_logit_diff_{k}"] = (outs[0] - o).abs().max().item()
+        row[f"argmax_equal_{k}"] = bool((outs[0].argmax(-1) == o.argmax(-1)).all())
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def step_mx4(quick: bool):
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    result = {"kernel": _mx4_kernel_rows(quick), "model": [], "extend": [], "nbytes": [], "logits": []}
+    plan = [("gpt-tiny", ())] + ([("gpt-small", (1,))] if quick else [("gpt-1b", (1, 16))])
+    for name, batches in plan:
+        model = GPT(CONFIGS[name], device="cuda").eval()
+        W8, W4 = model.decode_weights(), model.decode_weights("mxfp4")
+        bf16 = sum(q.shape[0] * q.shape[1] * 2 for q in W4.matrices())
+        row = {"model": name, "mxfp4_nbytes": W4.nbytes, "fp8_nbytes": W8.nbytes, "bf16_nbytes": bf16,
+               "unquantized": W4.unquantized}
+        print(json.dumps(row), flush=True)
+        result["nbytes"].append(row)
+        result["logits"].append(_mx4_logit_row(model, name))
+        for B in batches:
+            result["model"].append(_mx4_model_rows(model, name, B, quick))
+        if batches:
+            result["extend"] += _mx4_extend_rows(model, name, quick)
+        del model, W8, W4
         torch.cuda.empty_cache()
     return result
 
@@ -1372,7 +1542,7 @@ def step_window(quick: bool):
     return {"kernel": _window_kernel_rows(quick), "model": _window_model_rows(quick)}
 
 
-STEPS = {"ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8}
+STEPS = {"ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8, "mx4": step_mx4}
 
 
 def main() -> int:
