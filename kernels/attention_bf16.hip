@@ -44,6 +44,11 @@
 // group's K / V tiles meet in one L2 whenever G divides the heads per XCD (B H / 8). dK / dV sums a
 // group in fp32 inside attn_bwd_dkdv8 (GRP), see there and gqa_group_split.
 //
+// Packed documents (the DOC template flag; ops/attention.py's rule): a row of the batch holds several documents and
+// a query sees the keys of its own document only, doc_start[b][q] <= key <= q. The causal kernels then sweep, per
+// workgroup and per wave, only the tiles between a row's document start and its diagonal (the dK / dV kernel: between
+// a key and its document's end); see "DOC" ahead of the forward.
+//
 // Counterpart in the reference: none (its notebook images ship the framework's own attention);
 // SURVEY §7.1C rules out Triton on the hot path.
 #include <hip/hip_runtime.h>
@@ -168,6 +173,54 @@ __device__ __forceinline__ void store_rows16(__bf16* row, const f32x16 (&acc)[ND
 }
 
 // ------------------------------------------------------------------------------------------------
+// DOC: attention over packed documents (the rule: ops/attention.py). `doc_start` / `doc_end` are int32 [B][T],
+// both non-decreasing along a row; query i sees key j iff doc_start[i] <= j <= i, that is iff j <= i < doc_end[j].
+// The flag is a design of the tile sweep, not one more term of the mask:
+//   forward and dQ (query on the lane): a lane holds lo = doc_start of its row. The workgroup's K / V staging starts
+//   at tile doc_start[q0] / 64, its first row's bound and so its smallest; a wave skips the tiles below its first
+//   row's lo; the per-element test key < lo runs only on tiles with k0 < lo of the wave's last row (its largest);
+//   the tiles between those and the diagonal run the unmasked body. A packed row of n equal documents costs ~1 / n.
+//   A wave's later rows can meet tiles that lie wholly below their lo while their running maximum is still -inf:
+//   doc_ref gives the exponentials a finite reference there, so such a tile leaves m, l and O as they were, with no
+//   per-row branch (the softmax of attn_fwd and attn_fwd_pp; the dQ kernel has the LSE and replaces P by 0).
+//   dK / dV (key on the lane): a lane holds hi = doc_end of its key; a 128-key block sweeps the query tiles from its
+//   first key to doc_end of its last key instead of to T, a wave skips the halves at or past its last key's hi, and
+//   the test q >= hi runs only on the halves that reach its first key's hi.
+// Work order: block_order's rank and the forward's PAIR are kept as they are. Both assume causal work that grows
+// with the block index, which packed documents break (a block's work is then its distance from its document's
+// start), so with DOC they balance less well; nothing depends on the order for correctness, every workgroup
+// derives its own bounds, and keeping it makes a single document (doc_start = 0) the very sweep of the plain causal
+// kernels: the same tiles in the same order with the same arithmetic per row.
+// The DOC = false instantiations are the kernels they were, instruction for instruction (tools/kernel_isa_diff.py).
+// ------------------------------------------------------------------------------------------------
+struct DocRows {
+  int own;          // the lane's row: doc_start of its query (forward, dQ) / doc_end of its key (dK / dV)
+  int first, last;  // the same of the wave's first and last row (rows ascend with lane & 31): its smallest, largest
+  int blk;          // of the workgroup's row `brow` (uniform)
+};
+template <bool DOC>
+__device__ __forceinline__ DocRows doc_rows(const int* __restrict__ doc, int b, int T, int brow, int row) {
+  if constexpr (!DOC) return {0, 0, 0, 0};
+  const int* d = doc + (long long)b * T;
+  const int own = d[min(row, T - 1)];  // rows past T: the last row's, so the bounds stay monotone
+  return {own, __builtin_amdgcn_readfirstlane(own), __builtin_amdgcn_readlane(own, 31),
+          __builtin_amdgcn_readfirstlane(d[brow])};
+}
+// keys below the row's document: lim = lo - k0 - 4 * hh in the accumulator's row index
+__device__ __forceinline__ void doc_mask_tile(f32x16 (&s)[2], int lim) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      if (32 * t + (e & 3) + 8 * (e >> 2) < lim) s[t][e] = -INFINITY;
+}
+// the reference maximum of a tile's exponentials: mn, or 0 while the row has seen no key yet (mn = -inf)
+template <bool DOC>
+__device__ __forceinline__ float doc_ref(float mn) {
+  return DOC && mn == -INFINITY ? 0.f : mn;
+}
+
+// ------------------------------------------------------------------------------------------------
 // forward: one workgroup = 4 waves = 128 query rows of one (b, h); 64-key K/V tiles through a
 // double-buffered LDS image, register-staged (issued before the tile's products, written after)
 // ------------------------------------------------------------------------------------------------
@@ -236,10 +289,11 @@ __device__ __forceinline__ void pv_ra(const char* vimg, const int (&voff0)[D / 3
 // attn_fwd (D = 64 and small grids): LDS reads pinned this many MFMAs ahead of their use (profiles/r6v_ra)
 constexpr int kFwd4ReadAhead = 2;
 
-template <int D, bool CAUSAL, bool PAIR = false>
+template <int D, bool CAUSAL, bool PAIR = false, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                    const __bf16* __restrict__ v, __bf16* __restrict__ o,
-                                                   float* __restrict__ lse, AttnShape a) {
+                                                   float* __restrict__ lse, AttnShape a, const int* __restrict__ doc) {
+  static_assert(CAUSAL || !DOC, "a document mask is causal");
   constexpr int KS = D / 16;           // k-steps of the QK^T product
   constexpr int ND = D / 32;           // 32-wide d tiles of O
   constexpr int CH = D / 8;            // 16-B chunks per row
@@ -274,6 +328,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q,
   }
 
   const int ntiles = CAUSAL ? min((T + FK - 1) / FK, (q0 + FQW) / FK) : (T + FK - 1) / FK;
+  const DocRows dr = doc_rows<DOC>(doc, b, T, q0, qrow);
+  const int lo = dr.own, jt0 = dr.blk / FK;  // DOC: the row's first key, the workgroup's first tile
 
   u32x4 kreg[NCH], vreg[NCH];
   const auto rk = slice_rsrc(kb, 2LL * T * kt), rv = slice_rsrc(vb, 2LL * T * vt);
@@ -318,7 +374,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q,
 #pragma unroll
   for (int n = 0; n < ND; ++n) oacc[n] = (f32x16){};
 
-  stage_load(0);
+  stage_load(jt0);
   stage_write(0);
   __syncthreads();
 
@@ -346,8 +402,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q,
     if (more) stage_load(j + 1);
     const char* kimg = smem + BUF * 2 * TILE;
     const char* vimg = kimg + TILE;
-    // a wave whose 32 rows all precede the tile's first key has nothing to do (causal)
-    if (!(CAUSAL && k0 > qw + 31)) {
+    // a wave whose 32 rows all precede the tile's first key has nothing to do (causal), nor has one whose first
+    // row's document (and so every row's) begins after the tile's last key (DOC)
+    if (!(CAUSAL && k0 > qw + 31) && !(DOC && k0 + FK - 1 < dr.first)) {
       f32x16 sacc[2] = {(f32x16){}, (f32x16){}};
       qk_ra<D, kFwd4ReadAhead>(kimg, koff, qf, sacc);
       // masks: causal (key > query) on tiles that reach the wave's diagonal, key >= T on the tail
@@ -362,19 +419,23 @@ __global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q,
           }
         }
       }
+      if (DOC && k0 < dr.last) doc_mask_tile(sacc, lo - k0 - 4 * hh);  // some row's document begins inside or after
       float mx = -INFINITY;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sacc[t][e]);
       mx = kfw::max_halves(mx);  // the row's other 32 keys (v_permlane32_swap; no LDS round trip)
-      const float mn = fmaxf(m, mx);  // finite: the first tile holds key 0 <= every query
+      // finite without DOC: the first tile holds key 0 <= every query. DOC: -inf while the row's document has not
+      // begun; the exponentials then take 0 as their reference (doc_ref): alpha = 0 on O = l = 0, every p = 0
+      const float mn = fmaxf(m, mx);
+      const float mr = doc_ref<DOC>(mn);
       // O and l are rescaled only when some row's max grew (exact: alpha == 1 otherwise); late in a
       // row's sweep that is the rare case, and the 64-register multiply is skipped
       const bool grew = __builtin_amdgcn_ballot_w64(mx > m) != 0;
-      const float alpha = grew ? fast_exp2((m - mn) * c) : 1.f;
+      const float alpha = grew ? fast_exp2((m - mr) * c) : 1.f;
       m = mn;
-      const float mc = mn * c;
+      const float mc = mr * c;
       float rs = 0.f;
       uint32_t pf[2][2][4];  // [t][s][pair]: P^T as the B operand of PV
 #pragma unroll
@@ -399,7 +460,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd(const __bf16* __restrict__ q,
     if (more) stage_write(1 - BUF);
     __syncthreads();
   };
-  for (int j = 0; j < ntiles; j += 2) {
+  for (int j = jt0; j < ntiles; j += 2) {
     tile_body(j, std::integral_constant<int, 0>{});
     if (j + 1 < ntiles) tile_body(j + 1, std::integral_constant<int, 1>{});
   }
@@ -436,10 +497,11 @@ constexpr int kFwdReadAhead = 2;
 // scheduling fence between the QK^T / softmax / PV phases of attn_fwd_pp
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
 
-template <int D, bool CAUSAL, bool PAIR>
+template <int D, bool CAUSAL, bool PAIR, bool DOC = false>
 __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                       const __bf16* __restrict__ v, __bf16* __restrict__ o,
-                                                      float* __restrict__ lse, AttnShape a) {
+                                                      float* __restrict__ lse, AttnShape a, const int* __restrict__ doc) {
+  static_assert(CAUSAL || !DOC, "a document mask is causal");
   constexpr int KS = D / 16, ND = D / 32, CH = D / 8;
   constexpr int NT = 512, FQW = 256;
   constexpr int NCH = FK * CH / NT;  // 16-B chunks per thread per K (and per V) tile
@@ -487,8 +549,10 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
   auto pv = [&](const char* vimg, const uint32_t (&pf)[2][2][4], f32x16 (&oa)[ND]) __attribute__((always_inline)) {
     pv_ra<D, kFwdReadAhead>(vimg, voff0, voff1, pf, oa);
   };
+  DocRows dr = {};  // DOC: set per pass
   // causal / tail mask of the wave's S^T tile (keys from k0, rows from qw); a uniform branch
   auto mask = [&](f32x16 (&s)[2], int k0, int qw) __attribute__((always_inline)) {
+    if (DOC && k0 < dr.last) doc_mask_tile(s, dr.own - k0 - 4 * hh);
     if ((CAUSAL && k0 + FK - 1 > qw) || k0 + FK > T) {
       const int lim = (CAUSAL ? min(qw + r, T - 1) : T - 1) - k0 - 4 * hh;
 #pragma unroll
@@ -508,11 +572,13 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
 #pragma unroll
       for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[t][e]);
     mx = kfw::max_halves(mx);
-    const bool move = (mx - m) * c > THR;  // m = -inf on the first tile: moves
+    // m = -inf on the first tile: moves. DOC: a row whose document has not begun has mx = m = -inf; the difference
+    // is NaN, which does not move, and p = 0 against doc_ref's reference 0: m, l and O pass untouched
+    const bool move = (mx - m) * c > THR;
     const float mn = move ? mx : m;
     const float alpha = move ? fast_exp2((m - mn) * c) : 1.f;
     m = mn;
-    const float mc = mn * c;
+    const float mc = doc_ref<DOC>(mn) * c;
     float rs = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -571,6 +637,8 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     const int ntiles = CAUSAL ? min(nta, (q0 + FQW) / FK) : nta;
     const int jl = CAUSAL ? min(ntiles - 1, (qw + 31) / FK) : ntiles - 1;  // this wave's last tile
     const bool pre = PXP && pass == 1;  // Q and tiles 0 / 1 already in flight
+    dr = doc_rows<DOC>(doc, b, T, q0, qrow);
+    const int jt0 = dr.blk / FK, jf = dr.first / FK;  // DOC: the workgroup's and this wave's first tile
 
     if (!pre) load_q(qrow);
     f32x16 oacc[ND], S[2][2];
@@ -583,18 +651,18 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     // K / V two tiles ahead: tile j + 2's loads are issued at tile j into the register set tile j
     // used (written at tile j - 1), and tile j + 1's set is written at the end of tile j into the
     // slot of tile j - 3 (a four-tile ring: slot and set compile-time in the 4x unrolled loop)
-    if (!pre) ld(0, kreg, vreg);
+    if (!pre) ld(jt0, kreg, vreg);
     st(0, kreg, vreg);
-    if (!pre && 1 < ntiles) ld(1, kr2, vr2);
+    if (!pre && jt0 + 1 < ntiles) ld(jt0 + 1, kr2, vr2);
     __syncthreads();
     auto tile = [&](int j, auto SLC) __attribute__((always_inline)) {
-      constexpr int SL = decltype(SLC)::value;  // j % 4; register set j & 1
+      constexpr int SL = decltype(SLC)::value;  // (j - jt0) % 4; register set SL & 1
       auto& kc = (SL & 1) ? kr2 : kreg;
       auto& vc = (SL & 1) ? vr2 : vreg;
       auto& kn = (SL & 1) ? kreg : kr2;
       auto& vn = (SL & 1) ? vreg : vr2;
       if (j + 2 < ntiles) ld(j + 2, kc, vc);
-      if (j <= jl) {
+      if (j <= jl && !(DOC && j < jf)) {
         qk(smem + SL * TILE, qf, S[0]);
         mask(S[0], j * FK, qw);
         FENCE();
@@ -609,7 +677,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
-    int j = 0;
+    int j = jt0;
 #pragma unroll 1
     for (; j + 3 < ntiles; j += 4) {
       tile(j, I0{});
@@ -624,8 +692,9 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
     if (PXP && pass == 0) {  // the light block's Q and first K / V tiles, under this epilogue
       const int q0n = bo.rank * FQW;
       load_q(q0n + 32 * wu + r);
-      ld(0, kreg, vreg);
-      if (1 < (CAUSAL ? min(nta, (q0n + FQW) / FK) : nta)) ld(1, kr2, vr2);
+      const int jn = doc_rows<DOC>(doc, b, T, q0n, q0n).blk / FK;  // its first tile
+      ld(jn, kreg, vreg);
+      if (jn + 1 < (CAUSAL ? min(nta, (q0n + FQW) / FK) : nta)) ld(jn + 1, kr2, vr2);
     }
 
     // epilogue: lane (r, hh) holds row qrow, d = 32 n + (e & 3) + 8 (e >> 2) + 4 hh
@@ -658,13 +727,14 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pp(const __bf16* __restrict__
 // because the compiler orders the kernel's prologue differently without it.
 // Measured and not taken as well: LDS reads pinned ahead of their MFMAs as qk_ra / pv_ra (profiles/r6v_ra).
 // ------------------------------------------------------------------------------------------------
-template <int D, bool CAUSAL, bool PAIR = false>
+template <int D, bool CAUSAL, bool PAIR = false, bool DOC = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                             const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
                                                             const float* __restrict__ lse, const float* __restrict__ unused_slot,
                                                             __bf16* __restrict__ dq, AttnShape a,
                                                             const __bf16* __restrict__ o, float* __restrict__ nl_out,
-                                                            float* __restrict__ nd_out) {
+                                                            float* __restrict__ nd_out, const int* __restrict__ doc) {
+  static_assert(CAUSAL || !DOC, "a document mask is causal");
   constexpr int KS = D / 16;
   constexpr int ND = D / 32;
   constexpr int CH = D / 8;
@@ -716,6 +786,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
   }
 
   const int ntiles = CAUSAL ? min((T + FK - 1) / FK, (q0 + FQ) / FK) : (T + FK - 1) / FK;
+  const DocRows dr = doc_rows<DOC>(doc, b, T, q0, qrow);
+  const int lo = dr.own, jt0 = dr.blk / FK;  // DOC: the row's first key, the workgroup's first tile
   // K / V tile `tile` -> image buffer `buf`, each lane fetching the chunk the swizzle puts at its slot
   // LDS-DMA pieces: the wave index as a uniform value, each piece's per-lane source offset computed
   // once (image chunk sc of row `row` holds source chunk sc ^ swz(row, 0))
@@ -744,7 +816,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
 #pragma unroll
   for (int n = 0; n < ND; ++n) dqacc[n] = (f32x16){};
 
-  if (ntiles > 0) stage_dma(0, 0);
+  if (ntiles > 0) stage_dma(jt0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -767,7 +839,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
     if (j + 1 < ntiles) stage_dma(j + 1, 1 - BUF);  // buffer 1 - BUF was last read before the barrier
     const char* kimg = smem + BUF * 2 * TILE;
     const char* vimg = kimg + TILE;
-    if (!(CAUSAL && k0 > qw + 31)) {
+    if (!(CAUSAL && k0 > qw + 31) && !(DOC && k0 + FK - 1 < dr.first)) {  // DOC: as attn_fwd
       f32x16 sacc[2] = {(f32x16){}, (f32x16){}}, dpacc[2] = {(f32x16){}, (f32x16){}};
 #pragma unroll
       for (int kk = 0; kk < KS; ++kk) {
@@ -777,7 +849,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
           dpacc[t] = mfma32(lds_row(vimg + 32 * t * D * 2, koff[kk]), dof[kk], dpacc[t]);
         }
       }
-      const bool need_mask = (CAUSAL && k0 + FK - 1 > qw) || k0 + FK > T;
+      // DOC: a key below the row's document has P = 0 like one above the diagonal; exp2 of its score minus the
+      // row's LSE may be +inf, and is replaced, not multiplied
+      const bool need_mask = (CAUSAL && k0 + FK - 1 > qw) || k0 + FK > T || (DOC && k0 < dr.last);
       uint32_t sf[2][2][4];  // [t][s][pair]: dS^T as the B operand of K^T dS^T
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -786,8 +860,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
           float p0 = fast_exp2(fmaf(sacc[t][e], c, nlc)), p1 = fast_exp2(fmaf(sacc[t][e + 1], c, nlc));
           if (need_mask) {
             const int key = k0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-            if ((CAUSAL && key > qrow) || key >= T) p0 = 0.f;
-            if ((CAUSAL && key + 1 > qrow) || key + 1 >= T) p1 = 0.f;
+            if ((CAUSAL && key > qrow) || key >= T || (DOC && key < lo)) p0 = 0.f;
+            if ((CAUSAL && key + 1 > qrow) || key + 1 >= T || (DOC && key + 1 < lo)) p1 = 0.f;
           }
           sf[t][e >> 3][(e & 7) >> 1] = pack2(p0 * (dpacc[t][e] + nd_q), p1 * (dpacc[t][e + 1] + nd_q));
         }
@@ -810,7 +884,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
-  for (int j = 0; j < ntiles; j += 2) {
+  for (int j = jt0; j < ntiles; j += 2) {
     tile_body(j, std::integral_constant<int, 0>{});
     if (j + 1 < ntiles) tile_body(j + 1, std::integral_constant<int, 1>{});
   }
@@ -844,15 +918,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split(const __bf16* __rest
 // Registers (hipcc 7.2 remarks; no scratch anywhere): D = 128 causal / full 226 / 222 VGPRs ungrouped,
 // 227 / 228 GRP; D = 64 126 / 128 ungrouped, 124 / 128 GRP. GRP at D = 64 asks for 4 waves per SIMD
 // in its launch bounds: unforced, the non-causal kernel took 142 VGPRs and lost the second workgroup per CU.
+// DOC (causal only; the lane's doc_end and three wave bounds more): D = 128 228 ungrouped, 229 GRP; D = 64 128, 125 GRP.
 // ------------------------------------------------------------------------------------------------
 constexpr int BK = 128, BQ = 64;
 
-template <int D, bool CAUSAL, bool GRP = false>
+template <int D, bool CAUSAL, bool GRP = false, bool DOC = false>
 __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkdv8(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                          const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
                                                          const float* __restrict__ nl, const float* __restrict__ nd,
                                                          __bf16* __restrict__ dk, __bf16* __restrict__ dv, AttnShape a,
-                                                         float* __restrict__ gpart) {
+                                                         float* __restrict__ gpart, const int* __restrict__ doc) {
+  static_assert(CAUSAL || !DOC, "a document mask is causal");
   constexpr int KS = D / 16;
   constexpr int ND = D / 32;
   constexpr int CH = D / 8;
@@ -901,7 +977,10 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
   }
 
   const int qstart = CAUSAL ? k0 : 0;
-  const int ntiles = (T - qstart + BQ - 1) / BQ;
+  // DOC: `doc` is doc_end and dr.own the end of the lane's key's document; the sweep stops at the end of the block's last
+  // key's document (doc_end is non-decreasing: the block's largest), GRP's heads under the same bounds
+  const DocRows dr = doc_rows<DOC>(doc, b, T, min(k0 + BK, T) - 1, key);
+  const int ntiles = ((DOC ? dr.blk : T) - qstart + BQ - 1) / BQ;
 
   const i32x4 dq_desc = slice_desc(qb, 2LL * T * qt), ddo_desc = slice_desc(dob, 2LL * T * dot);
   const i32x4 drow_desc = slice_desc(wv == 0 ? nlb : ndb, 4LL * T);
@@ -983,8 +1062,10 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
     const float* nd_s = nl_s + BQ;
     const int qw = q0 + 32 * jh;
     // causal: every query of the half precedes every key of the wave -> P = dS = 0
-    if (!(CAUSAL && qw + 31 < kw)) {
-      const bool need_mask = (CAUSAL && qw < kw + 31) || qw + 32 > T || key >= T;
+    // DOC: nor has a half whose queries all lie past the end of the wave's last key's document
+    if (!(CAUSAL && qw + 31 < kw) && !(DOC && qw >= dr.last)) {
+      // DOC: the q >= hi test only where the half reaches the end of the wave's first key's document
+      const bool need_mask = (CAUSAL && qw < kw + 31) || qw + 32 > T || key >= T || (DOC && qw + 31 >= dr.first);
       f32x16 sacc, dpacc;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -1008,8 +1089,8 @@ __global__ __launch_bounds__(512, D == 64 ? (GRP ? 4 : 2) : 1) void attn_bwd_dkd
         float p0 = fast_exp2(sacc[e] * c), p1 = fast_exp2(sacc[e + 1] * c);
         if (need_mask) {
           const int qa0 = qw + (e & 3) + 8 * (e >> 2) + 4 * hh;
-          if ((CAUSAL && qa0 < key) || qa0 >= T || key >= T) p0 = 0.f;
-          if ((CAUSAL && qa0 + 1 < key) || qa0 + 1 >= T || key >= T) p1 = 0.f;
+          if ((CAUSAL && qa0 < key) || qa0 >= T || key >= T || (DOC && qa0 >= dr.own)) p0 = 0.f;
+          if ((CAUSAL && qa0 + 1 < key) || qa0 + 1 >= T || key >= T || (DOC && qa0 + 1 >= dr.own)) p1 = 0.f;
         }
         pf[e >> 3][(e & 7) >> 1] = pack2(p0, p1);
         sf[e >> 3][(e & 7) >> 1] = pack2(p0 * dpacc[e], p1 * dpacc[e + 1]);
@@ -1204,10 +1285,11 @@ int gqa_group_split(int B, int H, int Hkv, int T, int D) {
 
 long long align16(long long n) { return (n + 15) & ~15ll; }
 
+// doc (or null): doc_start, int32 [B][T]: the DOC instantiations of the same kernel choice, grid and pairing; causal only
 int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* lse, int B, int H, int Hkv, int T,
-                    int D, float scale, int causal, const long long* strides, void* stream) {
+                    int D, float scale, int causal, const long long* strides, void* stream, const int* doc = nullptr) {
   AttnShape s;
-  if (!q || !k || !v || !o || !lse) return KFAMD_EINVAL;
+  if (!q || !k || !v || !o || !lse || (doc && !causal)) return KFAMD_EINVAL;
   if (!fill_shape(s, B, H, T, D, scale, strides, 4) || !set_kv_heads(s, Hkv)) return KFAMD_EINVAL;
   if (!al16(q) || !al16(k) || !al16(v) || !al16(o)) return KFAMD_EALIGN;
   const long long nwg = (long long)((T + FQ - 1) / FQ) * H * B;
@@ -1217,7 +1299,7 @@ int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* 
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), 0, st, static_cast<const __bf16*>(q),
                        static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<__bf16*>(o),
-                       static_cast<float*>(lse), s);
+                       static_cast<float*>(lse), s, doc);
   };
   const int nq = (T + FQ - 1) / FQ;
   const int nq4 = (T + 255) / 256;
@@ -1230,22 +1312,23 @@ int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* 
     auto go4 = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3((unsigned)g4), dim3(512), 0, st, static_cast<const __bf16*>(q),
                          static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<__bf16*>(o),
-                         static_cast<float*>(lse), s);
+                         static_cast<float*>(lse), s, doc);
     };
-    pair ? go4(attn_fwd_pp<128, true, true>) : causal ? go4(attn_fwd_pp<128, true, false>)
-                                                   : go4(attn_fwd_pp<128, false, false>);
+    if (doc) pair ? go4(attn_fwd_pp<128, true, true, true>) : go4(attn_fwd_pp<128, true, false, true>);
+    else pair ? go4(attn_fwd_pp<128, true, true>) : causal ? go4(attn_fwd_pp<128, true, false>)
+                                                        : go4(attn_fwd_pp<128, false, false>);
   } else if (causal && nq % 2 == 0) {
     auto go2 = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3((unsigned)(nwg / 2)), dim3(256), 0, st, static_cast<const __bf16*>(q),
                          static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<__bf16*>(o),
-                         static_cast<float*>(lse), s);
+                         static_cast<float*>(lse), s, doc);
     };
-    if (D == 128) go2(attn_fwd<128, true, true>);
-    else go2(attn_fwd<64, true, true>);
+    if (D == 128) doc ? go2(attn_fwd<128, true, true, true>) : go2(attn_fwd<128, true, true>);
+    else doc ? go2(attn_fwd<64, true, true, true>) : go2(attn_fwd<64, true, true>);
   } else if (D == 128) {
-    causal ? go(attn_fwd<128, true>) : go(attn_fwd<128, false>);
+    doc ? go(attn_fwd<128, true, false, true>) : causal ? go(attn_fwd<128, true>) : go(attn_fwd<128, false>);
   } else {
-    causal ? go(attn_fwd<64, true>) : go(attn_fwd<64, false>);
+    doc ? go(attn_fwd<64, true, false, true>) : causal ? go(attn_fwd<64, true>) : go(attn_fwd<64, false>);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KFAMD_OK : static_cast<int>(e);
@@ -1254,11 +1337,14 @@ int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, void* 
 // One schedule: attn_bwd_dq_split (dQ, and the row constants nl / nd into the workspace), then attn_bwd_dkdv8,
 // then (grouped K / V with GS < G) attn_bwd_gqa_reduce over the parts' fp32 sums behind nl / nd in the workspace.
 // group_split: 0 = gqa_group_split's rule, else the GS to use (a divisor of G). Hkv == H: the ungrouped kernels.
+// doc_start and doc_end (both or neither; int32 [B][T]): the DOC instantiations on the same grids; causal only.
 int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout, const void* lse,
                     void* dq, void* dk, void* dv, void* workspace, int B, int H, int Hkv, int T, int D, float scale,
-                    int causal, int group_split, const long long* strides, void* stream) {
+                    int causal, int group_split, const long long* strides, void* stream,
+                    const int* doc_start = nullptr, const int* doc_end = nullptr) {
   AttnShape s;
   if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !workspace) return KFAMD_EINVAL;
+  if (!doc_start != !doc_end || (doc_start && !causal)) return KFAMD_EINVAL;
   if (!fill_shape(s, B, H, T, D, scale, strides, 8) || !set_kv_heads(s, Hkv)) return KFAMD_EINVAL;
   if (group_split < 0 || (group_split > 0 && s.G % group_split != 0)) return KFAMD_EINVAL;
   const bool grouped = Hkv != H;
@@ -1282,11 +1368,11 @@ int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, 
     hipLaunchKernelGGL(dq_k, dim3((unsigned)nq), dim3(256), 0, st, static_cast<const __bf16*>(q),
                        static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<const __bf16*>(dout),
                        static_cast<const float*>(lse), static_cast<const float*>(nullptr), static_cast<__bf16*>(dq), s,
-                       static_cast<const __bf16*>(o), nl, nd);
+                       static_cast<const __bf16*>(o), nl, nd, doc_start);
     hipLaunchKernelGGL(dkdv_k, dim3((unsigned)nkg), dim3(512), 0, st, static_cast<const __bf16*>(q),
                        static_cast<const __bf16*>(k), static_cast<const __bf16*>(v), static_cast<const __bf16*>(dout),
                        static_cast<const float*>(nl), static_cast<const float*>(nd), static_cast<__bf16*>(dk),
-                       static_cast<__bf16*>(dv), s, gpart);
+                       static_cast<__bf16*>(dv), s, gpart, doc_end);
     if (gpart) {
       const long long krows = (long long)B * Hkv * T;
       const unsigned kblocks = (unsigned)((krows + 256 / (D / 8) - 1) / (256 / (D / 8)));
@@ -1294,7 +1380,12 @@ int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, 
                          static_cast<__bf16*>(dv), s);
     }
   };
-  if (D == 128) {
+  if (doc_start) {
+    if (D == 128) grouped ? run(attn_bwd_dq_split<128, true, false, true>, attn_bwd_dkdv8<128, true, true, true>, attn_bwd_gqa_reduce<128>)
+                          : run(attn_bwd_dq_split<128, true, false, true>, attn_bwd_dkdv8<128, true, false, true>, attn_bwd_gqa_reduce<128>);
+    else grouped ? run(attn_bwd_dq_split<64, true, false, true>, attn_bwd_dkdv8<64, true, true, true>, attn_bwd_gqa_reduce<64>)
+                 : run(attn_bwd_dq_split<64, true, false, true>, attn_bwd_dkdv8<64, true, false, true>, attn_bwd_gqa_reduce<64>);
+  } else if (D == 128) {
     if (grouped) causal ? run(attn_bwd_dq_split<128, true>, attn_bwd_dkdv8<128, true, true>, attn_bwd_gqa_reduce<128>)
                         : run(attn_bwd_dq_split<128, false>, attn_bwd_dkdv8<128, false, true>, attn_bwd_gqa_reduce<128>);
     else causal ? run(attn_bwd_dq_split<128, true>, attn_bwd_dkdv8<128, true>, attn_bwd_gqa_reduce<128>)
@@ -1358,4 +1449,21 @@ extern "C" int kfamd_attn_bwd_gqa_bf16(const void* q, const void* k, const void*
                                        const long long* strides, void* stream) {
   return attn_bwd_launch(q, k, v, o, dout, lse, dq, dk, dv, workspace, B, H, Hkv, T, D, scale, causal, group_split,
                          strides, stream);
+}
+
+// ---- packed documents (kfamd_kernels.h) ----
+extern "C" int kfamd_attn_fwd_doc_bf16(const void* q, const void* k, const void* v, void* o, void* lse,
+                                       const int* doc_start, int B, int H, int Hkv, int T, int D, float scale,
+                                       const long long* strides, void* stream) {
+  if (!doc_start) return KFAMD_EINVAL;
+  return attn_fwd_launch(q, k, v, o, lse, B, H, Hkv, T, D, scale, 1, strides, stream, doc_start);
+}
+
+extern "C" int kfamd_attn_bwd_doc_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                       const void* lse, void* dq, void* dk, void* dv, void* workspace,
+                                       const int* doc_start, const int* doc_end, int B, int H, int Hkv, int T, int D,
+                                       float scale, int group_split, const long long* strides, void* stream) {
+  if (!doc_start || !doc_end) return KFAMD_EINVAL;
+  return attn_bwd_launch(q, k, v, o, dout, lse, dq, dk, dv, workspace, B, H, Hkv, T, D, scale, 1, group_split, strides,
+                         stream, doc_start, doc_end);
 }

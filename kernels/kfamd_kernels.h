@@ -244,6 +244,19 @@ int kfamd_attn_bwd_gqa_bf16(const void* q, const void* k, const void* v, const v
                             const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int H, int Hkv,
                             int T, int D, float scale, int causal, int group_split, const long long* strides,
                             void* stream);
+// Causal attention over packed documents (the DOC instantiations; the rule: ops/attention.py). doc_start, doc_end:
+// int32 [B][T] device arrays, contiguous: the first position and the exclusive end of the document that holds
+// position t. Valid: doc_start[b][0] = 0 and doc_start[b][t] is doc_start[b][t - 1] or t; doc_end the matching
+// ends. Query i sees key j iff doc_start[i] <= j <= i, for every head alike. The kernels trust the arrays (as the
+// KV-cache kernels trust lens): values outside [0, T] or a decreasing row are the caller's fault. Everything else
+// is the _gqa_ entry points' with causal = 1: Hkv (== H: ungrouped), group_split and kfamd_attn_bwd_gqa_workspace.
+// All zeros / all T (one document) is the sweep of the plain causal kernels, tile for tile.
+int kfamd_attn_fwd_doc_bf16(const void* q, const void* k, const void* v, void* o, void* lse, const int* doc_start,
+                            int B, int H, int Hkv, int T, int D, float scale, const long long* strides, void* stream);
+int kfamd_attn_bwd_doc_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                            const void* lse, void* dq, void* dk, void* dv, void* workspace, const int* doc_start,
+                            const int* doc_end, int B, int H, int Hkv, int T, int D, float scale, int group_split,
+                            const long long* strides, void* stream);
 
 // ---- decode (KV-cache generation) ------------------------------------------------------------
 // Everything from here to the FP8 entry points is attn_kv.hip.

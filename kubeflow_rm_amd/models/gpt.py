@@ -63,8 +63,19 @@ on the GPU cannot use the flash kernel, which has no window: it runs the prompt 
 ``ops.attention_chunk`` in one step (its docstring). The training ``forward`` applies the mask on the torch path (CPU,
 ``ops.torch_reference()``) and raises ``NotImplementedError`` on the native GPU path. A flat ``KVCache`` still holds
 every position (the ring below does not). ``window=None`` (the default) is the model as it was: same launches, same
-bits. Not built: a window in the flash forward / backward kernels (native GPU training of a windowed model), per-layer
-windows, attention sinks.
+bits. Not built: a window in the flash forward / backward kernels (native GPU training of a windowed model; the
+kernels have a per-row lower bound on the keys since the packed-document mask below, and the window is not wired to
+it), per-layer windows, attention sinks.
+
+Packed documents: ``forward(idx, targets, doc_start=...)`` trains on rows that pack several documents, each token
+attending within its own document only (block-diagonal causal; the rule is the docstring of ``ops/attention.py``, and
+``ops.doc_bounds(doc_ids)`` makes ``doc_start`` from a loader's document ids on the device). On the GPU the flash
+kernels' ``DOC`` instantiations skip the tiles outside a row's document, forward and backward (``ops.attn_block`` /
+``ops.attention_qkv(doc_start=...)``); the torch path runs SDPA under the rule's mask. Learned positions restart per
+document (one ``F.embedding`` gather at ``t - doc_start``); rotary positions need no change. The caller gives the last
+token of each document the target ``-100``. ``doc_start=None`` is the model as it was. Not built: ``prefill`` /
+``generate`` on packed prompts (one prompt is one document), a window with ``doc_start``, rows of different lengths
+without padding.
 
 Ring-buffer cache: ``new_cache(..., ring=True)`` / ``generate(..., ring=True)`` of a windowed model keep the last
 ``capacity`` positions only (``ops/decode.py``'s ring rule): the cache's memory is O(window), the positions run to
@@ -314,11 +325,32 @@ class Block(torch.nn.Module):
         y = F.scaled_dot_product_attention(q, k, v, attn_mask=_window_mask(T, self.cfg.window, x.device))
         return self.proj(y.transpose(1, 2).reshape(B, T, h * hd), residual=residual)
 
-    def attention(self, x, residual=None, rope=None):
+    def _attention_docs(self, x, residual, rope, doc_start):
+        """Attention over packed documents (``ops/attention.py``'s rule): the routes of ``attention`` with
+        ``doc_start`` passed down: the fused ``ops.attn_block``, else ``ops.attention_qkv``, which runs the flash
+        kernels on the GPU and SDPA under the rule's mask on the torch path (CPU, ``ops.torch_reference()``, other
+        head dims). The flash kernels' per-row lower bound is not wired to a window: a windowed model raises."""
+        h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
+        if self.cfg.window is not None:
+            raise NotImplementedError("GPTConfig(window=...) with doc_start: a sliding window inside packed documents "
+                                      "is not built")
+        if x.is_cuda and ops.native_enabled() and ops.attention_supported(x, hd) and not tpl._collective(self.tp_group):
+            return ops.attn_block(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, h, hd,
+                                  residual=residual, rope=rope, kv_heads=hkv, doc_start=doc_start)
+        qkv = self.qkv(x)
+        if rope is not None:
+            qkv = ops.rope_qkv(qkv, rope, h, hkv)
+        y = ops.attention_qkv(qkv.contiguous(), h, hd, causal=True, kv_heads=hkv, doc_start=doc_start)
+        return self.proj(y, residual=residual)
+
+    def attention(self, x, residual=None, rope=None, doc_start=None):
         """``rope``: the model's rotary table (``GPTConfig(pos="rope")``): q and k are rotated right after the QKV
-        projection, inside ``ops.attn_block`` on the fused path, by ``ops.rope_qkv`` on the others."""
+        projection, inside ``ops.attn_block`` on the fused path, by ``ops.rope_qkv`` on the others. ``doc_start``:
+        packed documents (``_attention_docs``)."""
         B, T, _ = x.shape
         h, hkv, hd = self.local_heads, self.local_kv_heads, self.cfg.head_dim
+        if doc_start is not None:
+            return self._attention_docs(x, residual, rope, doc_start)
         if self.cfg.window is not None:
             return self._attention_window(x, residual, rope)
         # the fused single-rank path whenever the TP layers would issue no collective; a forced-distributed
@@ -353,11 +385,11 @@ class Block(torch.nn.Module):
                            residual=residual)
         return self.fc2(self.fc1(h), residual=residual)
 
-    def forward(self, x, rope=None):
+    def forward(self, x, rope=None, doc_start=None):
         # both residual adds ride in the output projections' GEMM epilogues (without TP); the
         # residual gradient joins the LayerNorm backward's dx store (LayerNorm.with_residual)
         h, r = self.ln1.with_residual(x)
-        x = self.attention(h, residual=r, rope=rope)
+        x = self.attention(h, residual=r, rope=rope, doc_start=doc_start)
         h, r = self.ln2.with_residual(x)
         return self.mlp(h, r)
 
@@ -478,13 +510,30 @@ class GPT(torch.nn.Module):
         self.blocks = torch.nn.ModuleList([Block(cfg, i, tp_group, device) for i in range(cfg.n_layers)])
         self.ln_f = Norm(cfg, device)
 
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, doc_start=None):
+        """``doc_start`` (``int32 [B, T]`` on ``idx``'s device, from ``ops.doc_bounds``): every row of ``idx`` packs
+        several documents, and a token attends within its own document only (``ops/attention.py``'s rule).
+        ``pos="learned"``: positions restart per document, the position embedding gathered at ``t - doc_start[b, t]``
+        on the device. ``pos="rope"``: nothing changes, since a rotated score depends on ``i - j`` alone and restarting
+        the rotation per document is the same function. Targets across a boundary are the caller's job: give the
+        last token of each document ``ignore_index`` (-100), which the cross-entropy kernel skips. A windowed
+        model raises ``NotImplementedError``. ``doc_start=None``: the forward as it was."""
         B, T = idx.shape
         x = F.embedding(idx, self.tok)
+        if doc_start is not None and self.cfg.window is not None:
+            raise NotImplementedError("GPTConfig(window=...) with doc_start: a sliding window inside packed documents "
+                                      "is not built")
         if self.pos is not None:
-            x = x + self.pos[:T]
-        for blk in self.blocks:
-            x = blk(x, self.rope_table)
+            if doc_start is None:
+                x = x + self.pos[:T]
+            else:  # positions restart per document
+                x = x + F.embedding(torch.arange(T, device=idx.device, dtype=torch.int32) - doc_start, self.pos)
+        if doc_start is None:
+            for blk in self.blocks:
+                x = blk(x, self.rope_table)
+        else:
+            for blk in self.blocks:
+                x = blk(x, self.rope_table, doc_start)
         x = self.ln_f(x)
         logits = tpl._linear(x, self.tok)  # tied output head [B, T, vocab]
         if targets is None:

@@ -98,6 +98,10 @@ _SIGNATURES = {
     "kfamd_attn_bwd_gqa_workspace": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "kfamd_attn_bwd_gqa_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                         c_int, c_int, c_float, c_int, c_int, ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_fwd_doc_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float,
+                                        ctypes.POINTER(c_ll), c_vp]),
+    "kfamd_attn_bwd_doc_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                                        c_int, c_int, c_int, c_int, c_float, c_int, ctypes.POINTER(c_ll), c_vp]),
     "kfamd_attn_decode_split_keys": (c_int, []),
     "kfamd_attn_decode_workspace": (c_ll, [c_int, c_int, c_int, c_int]),
     "kfamd_attn_decode_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_float,

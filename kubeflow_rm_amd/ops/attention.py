@@ -17,6 +17,20 @@ sum over a group's query heads taken in fp32 inside the kernel. ``attention_qkv`
 ``split_heads(qkv, h, hd)`` remains for torch's SDPA path (CPU, other head dims): its backward
 packs SDPA's dq / dk / dv into the QKV gradient layout in one HIP pass (``qkv_pack_bf16.hip``).
 
+Packed documents (the rule; everything else refers to it). ``doc_start`` is an ``int32 [B, T]`` tensor on the inputs'
+device: ``doc_start[b, t]`` is the position of the first token of the document that holds position ``t`` of row ``b``.
+Valid input: ``doc_start[b, 0] == 0`` and, for every ``t``, ``doc_start[b, t]`` is ``doc_start[b, t - 1]`` or ``t``
+(so it is non-decreasing and ``<= t``). The mask: query ``i`` sees key ``j`` iff ``doc_start[b, i] <= j <= i``, the
+same for every head, and the same K / V head for a grouped query head. Every row sees at least itself, so no row is
+empty. ``doc_start=None`` is the op as it was: same launches, same bits. ``doc_start`` requires ``causal=True``.
+``doc_bounds(doc_ids)`` makes ``doc_start`` (and ``doc_end``, each key's exclusive document end, which the backward
+kernels take and the ops derive themselves) from the document ids of a data loader, on the device, with no host sync.
+``flash_attention``, ``attention_qkv`` and ``attn_block`` take ``doc_start=``: on the GPU the ``DOC`` instantiations of
+the flash kernels, which skip the tiles outside a row's document (n equal documents per row: about 1 / n of the causal
+work); on the torch path (CPU tensors, ``ops.torch_reference()``, other head dims) SDPA under the boolean mask of the
+rule. A ``doc_start`` on the CPU is checked against the rule; on the GPU it is the caller's contract, as ``lens`` is
+for the KV-cache kernels.
+
 There is no silent fallback on a GPU: a kernel that rejects its arguments raises.
 """
 from __future__ import annotations
@@ -68,12 +82,76 @@ def _kv_heads_of(q, k, v, what: str) -> int:
     return Hkv
 
 
-def _fwd(q, k, v, o, causal: bool, scale: float) -> torch.Tensor:
-    """q, o: [B, H, T, D] views, k, v: [B, Hkv, T, D] views (Hkv divides H). Returns lse [B, H, T] (f32)."""
+def _doc_end(doc_start: torch.Tensor) -> torch.Tensor:
+    """``doc_end[b, j]``: the exclusive end of ``j``'s document = the next document's start after ``j``, or T."""
+    B, T = doc_start.shape
+    ar = torch.arange(T, device=doc_start.device, dtype=torch.int32)
+    nxt = torch.where(doc_start == ar, ar, T)  # a start's own position, T elsewhere
+    nxt = torch.cat([nxt[:, 1:], nxt.new_full((B, 1), T)], 1)  # ... seen from the position before
+    return nxt.flip(1).cummin(1).values.flip(1).contiguous()
+
+
+def doc_bounds(doc_ids: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(doc_start, doc_end)``, ``int32 [B, T]`` on ``doc_ids``' device, of an int ``[B, T]`` tensor of document ids
+    that change where a new document begins (the module docstring's rule). Torch ops only, no host sync."""
+    if doc_ids.dim() != 2 or doc_ids.dtype.is_floating_point or doc_ids.dtype == torch.bool:
+        raise ValueError(f"doc_bounds: an int [B, T] tensor of document ids expected, got {doc_ids.dtype} "
+                         f"{tuple(doc_ids.shape)}")
+    T = doc_ids.shape[1]
+    ar = torch.arange(T, device=doc_ids.device, dtype=torch.int32)
+    new = torch.ones(doc_ids.shape, dtype=torch.bool, device=doc_ids.device)
+    new[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+    doc_start = torch.where(new, ar, 0).cummax(1).values.to(torch.int32).contiguous()
+    return doc_start, _doc_end(doc_start)
+
+
+def doc_mask(doc_start: torch.Tensor) -> torch.Tensor:
+    """The rule as a boolean mask ``[B, 1, T, T]`` (True: seen) for SDPA: the torch path and the tests' reference."""
+    T = doc_start.shape[1]
+    ar = torch.arange(T, device=doc_start.device)
+    return ((ar >= doc_start[:, :, None]) & (ar <= ar[:, None])).unsqueeze(1)
+
+
+def _check_doc(doc_start, B: int, T: int, device, causal: bool, what: str) -> None:
+    if not causal:
+        raise ValueError(f"{what}: doc_start requires causal=True (a document mask is block-diagonal causal)")
+    if (not isinstance(doc_start, torch.Tensor) or doc_start.dtype != torch.int32 or doc_start.shape != (B, T)
+            or doc_start.device != device or not doc_start.is_contiguous()):
+        raise ValueError(f"{what}: doc_start: a contiguous int32 [{B}, {T}] tensor on {device} expected "
+                         "(ops.doc_bounds makes one)")
+    if not doc_start.is_cuda:  # the validity rule; on the GPU it is the caller's contract (no host sync)
+        ar = torch.arange(T, dtype=torch.int32)
+        if not ((doc_start[:, 0] == 0).all() and ((doc_start[:, 1:] == doc_start[:, :-1]) | (doc_start[:, 1:] == ar[1:])).all()):
+            raise ValueError(f"{what}: doc_start breaks the rule: doc_start[b, 0] == 0 and doc_start[b, t] in "
+                             "{doc_start[b, t - 1], t}")
+
+
+def _sdpa_doc(q, k, v, doc_start, scale):
+    """The torch path: SDPA under the rule's mask; grouped K / V heads expanded."""
+    import torch.nn.functional as F
+    G = q.shape[1] // k.shape[1]
+    if G > 1:
+        k, v = k.repeat_interleave(G, 1), v.repeat_interleave(G, 1)
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=doc_mask(doc_start), scale=scale)
+
+
+def _torch_path(x: torch.Tensor, head_dim: int) -> bool:
+    from . import native_enabled
+    return not (native_enabled() and supported(x, head_dim))
+
+
+def _fwd(q, k, v, o, causal: bool, scale: float, doc_start: torch.Tensor | None = None) -> torch.Tensor:
+    """q, o: [B, H, T, D] views, k, v: [B, Hkv, T, D] views (Hkv divides H). Returns lse [B, H, T] (f32).
+    ``doc_start``: the packed-document forward (the module docstring's rule)."""
     B, H, T, D = q.shape
     Hkv = _kv_heads_of(q, k, v, "attn_fwd")
     lse = torch.empty(B, H, T, device=q.device, dtype=torch.float32)
-    if Hkv == H:
+    if doc_start is not None:
+        _check_doc(doc_start, B, T, q.device, causal, "attn_fwd")
+        rc = _lib.lib().kfamd_attn_fwd_doc_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
+                                                doc_start.data_ptr(), B, H, Hkv, T, D, float(scale),
+                                                _strides(q, k, v, o), _stream_ptr(q))
+    elif Hkv == H:
         rc = _lib.lib().kfamd_attn_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
                                             B, H, T, D, float(scale), int(causal), _strides(q, k, v, o), _stream_ptr(q))
     else:
@@ -84,15 +162,29 @@ def _fwd(q, k, v, o, causal: bool, scale: float) -> torch.Tensor:
     return lse
 
 
-def _bwd(q, k, v, o, do, lse, dq, dk, dv, causal: bool, scale: float, group_split: int = 0) -> None:
+def _bwd(q, k, v, o, do, lse, dq, dk, dv, causal: bool, scale: float, group_split: int = 0,
+         doc: tuple[torch.Tensor, torch.Tensor] | None = None) -> None:
     """dq [B, H, T, D], dk / dv [B, Hkv, T, D] views. ``group_split`` (grouped K / V only): how many query heads
-    of a group one dK / dV workgroup sweeps, a divisor of H / Hkv; 0: the launcher's rule."""
+    of a group one dK / dV workgroup sweeps, a divisor of H / Hkv; 0: the launcher's rule. ``doc``: the forward's
+    ``(doc_start, _doc_end(doc_start))``."""
     B, H, T, D = q.shape
     Hkv = _kv_heads_of(q, k, v, "attn_bwd")
     if dk.shape != k.shape or dv.shape != v.shape:
         raise ValueError(f"attn_bwd: dk / dv {tuple(k.shape)} expected, got {tuple(dk.shape)}, {tuple(dv.shape)}")
     L = _lib.lib()
-    if Hkv == H and group_split in (0, 1):
+    if doc is not None:
+        _check_doc(doc[0], B, T, q.device, causal, "attn_bwd")
+        if Hkv == H:
+            group_split = 0
+        elif group_split < 0 or (group_split and (H // Hkv) % group_split):
+            raise ValueError(f"attn_bwd: group_split={group_split} must divide the group size {H // Hkv}")
+        ws = torch.empty(L.kfamd_attn_bwd_gqa_workspace(B, H, Hkv, T, D, int(group_split)), device=q.device,
+                         dtype=torch.uint8)
+        rc = L.kfamd_attn_bwd_doc_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
+                                       lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(),
+                                       doc[0].data_ptr(), doc[1].data_ptr(), B, H, Hkv, T, D, float(scale),
+                                       int(group_split), _strides(q, k, v, o, do, dq, dk, dv), _stream_ptr(q))
+    elif Hkv == H and group_split in (0, 1):
         ws = torch.empty(L.kfamd_attn_bwd_workspace(B, H, T, D), device=q.device, dtype=torch.uint8)
         rc = L.kfamd_attn_bwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
                                    lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), B, H, T,
@@ -126,49 +218,54 @@ def _bhtd(x: torch.Tensor) -> torch.Tensor:
     return x.permute(0, 2, 1, 3)
 
 
+def _saved_doc(doc_start) -> tuple:
+    """What a forward with ``doc_start`` saves for its backward besides: ``(doc_start, doc_end)``, else nothing."""
+    return () if doc_start is None else (doc_start, _doc_end(doc_start))
+
+
 class _FlashAttn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
+    def forward(ctx, q, k, v, causal, scale, doc_start=None):
         _check_views(q, k, v)
         B, H, T, D = q.shape
         _kv_heads_of(q, k, v, "flash_attention")
         o = _bhtd(torch.empty(B, T, H, D, device=q.device, dtype=q.dtype))
-        lse = _fwd(q, k, v, o, causal, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
+        lse = _fwd(q, k, v, o, causal, scale, doc_start)
+        ctx.save_for_backward(q, k, v, o, lse, *_saved_doc(doc_start))
         ctx.causal, ctx.scale = causal, scale
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, *doc = ctx.saved_tensors
         B, H, T, D = q.shape
         if do.stride(-1) != 1 or any(s % 8 for s in do.stride()[:3]):
             do = do.contiguous()
         grads = [_bhtd(torch.empty(B, T, n, D, device=q.device, dtype=q.dtype)) for n in (H, k.shape[1], v.shape[1])]
-        _bwd(q, k, v, o, do, lse, *grads, ctx.causal, ctx.scale)
-        return grads[0], grads[1], grads[2], None, None
+        _bwd(q, k, v, o, do, lse, *grads, ctx.causal, ctx.scale, doc=tuple(doc) or None)
+        return grads[0], grads[1], grads[2], None, None, None
 
 
 class _FlashAttnQKV(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, h, hd, causal, scale, hkv):
+    def forward(ctx, qkv, h, hd, causal, scale, hkv, doc_start=None):
         B, T, _ = qkv.shape
         o = torch.empty(B, T, h, hd, device=qkv.device, dtype=qkv.dtype)
-        lse = _fwd(*_qkv_views(qkv, h, hkv, hd), _bhtd(o), causal, scale)
-        ctx.save_for_backward(qkv, o, lse)
+        lse = _fwd(*_qkv_views(qkv, h, hkv, hd), _bhtd(o), causal, scale, doc_start)
+        ctx.save_for_backward(qkv, o, lse, *_saved_doc(doc_start))
         ctx.dims, ctx.causal, ctx.scale = (h, hkv, hd), causal, scale
         return o.view(B, T, h * hd)
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, *doc = ctx.saved_tensors
         h, hkv, hd = ctx.dims
         B, T, _ = qkv.shape
         do = do.contiguous().view(B, T, h, hd)
         dqkv = torch.empty_like(qkv)
         _bwd(*_qkv_views(qkv, h, hkv, hd), _bhtd(o), _bhtd(do), lse, *_qkv_views(dqkv, h, hkv, hd),
-             ctx.causal, ctx.scale)
-        return dqkv, None, None, None, None, None
+             ctx.causal, ctx.scale, doc=tuple(doc) or None)
+        return dqkv, None, None, None, None, None, None
 
 
 class _AttnBlock(torch.autograd.Function):
@@ -182,7 +279,7 @@ class _AttnBlock(torch.autograd.Function):
     weight-gradient pair read it. ``hkv`` K / V heads: qkv and dqkv are ``[B, T, (h + 2 hkv) hd]`` (q | k | v)."""
 
     @staticmethod
-    def forward(ctx, x, wqkv, bqkv, wproj, bproj, h, hd, causal, scale, residual, rope=None, hkv=None):
+    def forward(ctx, x, wqkv, bqkv, wproj, bproj, h, hd, causal, scale, residual, rope=None, hkv=None, doc_start=None):
         from .gemm import gemm_nt
         from .rope import rotate_native_
         B, T, D = x.shape
@@ -194,11 +291,11 @@ class _AttnBlock(torch.autograd.Function):
         if rope is not None:
             rotate_native_(qkv, rope, h, hkv)
         o = torch.empty(B, T, h, hd, device=x.device, dtype=x.dtype)
-        lse = _fwd(*_qkv_views(qkv, h, hkv, hd), _bhtd(o), causal, scale)
+        lse = _fwd(*_qkv_views(qkv, h, hkv, hd), _bhtd(o), causal, scale, doc_start)
         o2 = o.view(B * T, h * hd)
         res = residual.reshape(B * T, wproj.shape[0]).contiguous() if residual is not None else None
         out = gemm_nt(o2, wproj, bias=bproj, residual=res)
-        ctx.save_for_backward(x2, wqkv, bqkv, wproj, bproj, qkv, o, lse)
+        ctx.save_for_backward(x2, wqkv, bqkv, wproj, bproj, qkv, o, lse, *_saved_doc(doc_start))
         ctx.dims, ctx.causal, ctx.scale, ctx.rope = (B, T, D, h, hkv, hd), causal, scale, rope
         return out.view(B, T, wproj.shape[0])
 
@@ -206,7 +303,7 @@ class _AttnBlock(torch.autograd.Function):
     def backward(ctx, gy):
         from .gemm import act_grad, mm, wgrad_pair
         from .rope import rotate_native_
-        x2, wqkv, bqkv, wproj, bproj, qkv, o, lse = ctx.saved_tensors
+        x2, wqkv, bqkv, wproj, bproj, qkv, o, lse, *doc = ctx.saved_tensors
         B, T, D, h, hkv, hd = ctx.dims
         ni = ctx.needs_input_grad
         gy2 = gy.reshape(B * T, wproj.shape[0])
@@ -224,7 +321,7 @@ class _AttnBlock(torch.autograd.Function):
         do = mm(gy2, wproj).view(B, T, h, hd)  # the projection's dgrad
         dqkv = torch.empty_like(qkv)
         _bwd(*_qkv_views(qkv, h, hkv, hd), _bhtd(o), _bhtd(do), lse, *_qkv_views(dqkv, h, hkv, hd),
-             ctx.causal, ctx.scale)
+             ctx.causal, ctx.scale, doc=tuple(doc) or None)
         if ctx.rope is not None:  # the gradient of the rotated q, k -> of the projection's output
             rotate_native_(dqkv, ctx.rope, h, hkv, inverse=True)
         dqkv2 = dqkv.view(B * T, (h + 2 * hkv) * hd)
@@ -237,19 +334,21 @@ class _AttnBlock(torch.autograd.Function):
         else:
             gwq = mm(dqkv2, x2, trans_a=True) if ni[1] else None
             gwp = mm(gy2, o2, trans_a=True) if ni[3] else None
-        return dx, gwq, gbq, gwp, gbp, None, None, None, None, (gy if ni[9] else None), None, None
+        return dx, gwq, gbq, gwp, gbp, None, None, None, None, (gy if ni[9] else None), None, None, None
 
 
 def attn_block(x: torch.Tensor, wqkv: torch.Tensor, bqkv: torch.Tensor | None, wproj: torch.Tensor,
                bproj: torch.Tensor | None, h: int, hd: int, residual: torch.Tensor | None = None,
                causal: bool = True, scale: float | None = None, rope: torch.Tensor | None = None,
-               kv_heads: int | None = None) -> torch.Tensor:
+               kv_heads: int | None = None, doc_start: torch.Tensor | None = None) -> torch.Tensor:
     """A transformer block's attention half on the HIP kernels: ``proj(attn(qkv(x))) (+ residual)``,
     x ``[B, T, D]``, wqkv ``[3 h hd, D]`` (q | k | v rows, heads inside each), wproj ``[D_out, h hd]``.
     ``rope``: an ``ops.rope_table`` ``[max_pos >= T, hd]``; q and k are rotated (positions 0 .. T - 1) between the
     QKV projection and the attention, in place in both directions (``ops.rope_qkv``'s kernel).
     ``kv_heads``: grouped-query attention with that many K / V heads (a divisor of ``h``); wqkv is then
-    ``[(h + 2 kv_heads) hd, D]`` and the flash kernels read each K / V head in place for its whole group."""
+    ``[(h + 2 kv_heads) hd, D]`` and the flash kernels read each K / V head in place for its whole group.
+    ``doc_start``: packed documents (the module docstring's rule); ``rope`` positions do not restart, which computes
+    the same function (a rotated score depends on ``i - j`` alone)."""
     hkv = h if kv_heads is None else int(kv_heads)
     check_kv_heads(h, hkv, "attn_block")
     if x.dim() != 3 or wqkv.shape[0] != (h + 2 * hkv) * hd or wproj.shape[1] != h * hd:
@@ -259,35 +358,54 @@ def attn_block(x: torch.Tensor, wqkv: torch.Tensor, bqkv: torch.Tensor | None, w
         raise ValueError(f"attn_block: bf16 CUDA input with head dim in {HEAD_DIMS} expected")
     if rope is not None and (rope.dim() != 2 or rope.shape[1] != hd or rope.shape[0] < x.shape[1]):
         raise ValueError(f"attn_block: rope [max_pos >= {x.shape[1]}, {hd}] expected, got {tuple(rope.shape)}")
-    return _AttnBlock.apply(x, wqkv, bqkv, wproj, bproj, h, hd, causal,
-                            scale if scale is not None else 1.0 / math.sqrt(hd), residual, rope, hkv)
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if doc_start is None:
+        return _AttnBlock.apply(x, wqkv, bqkv, wproj, bproj, h, hd, causal, scale, residual, rope, hkv)
+    _check_doc(doc_start, x.shape[0], x.shape[1], x.device, causal, "attn_block")
+    return _AttnBlock.apply(x, wqkv, bqkv, wproj, bproj, h, hd, causal, scale, residual, rope, hkv, doc_start)
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
-                    scale: float | None = None) -> torch.Tensor:
+                    scale: float | None = None, doc_start: torch.Tensor | None = None) -> torch.Tensor:
     """softmax(scale * q k^T (+ causal mask)) v for [B, H, T, D] bf16 views (D = 64 / 128). ``k`` / ``v`` may have
     ``Hkv`` heads, ``Hkv`` dividing ``H`` (grouped-query attention: query head h reads K / V head h // (H // Hkv));
-    the output is ``[B, H, T, D]`` and the gradients of k / v have ``Hkv`` heads."""
+    the output is ``[B, H, T, D]`` and the gradients of k / v have ``Hkv`` heads. ``doc_start``: packed documents
+    (the module docstring's rule); with it, tensors off the flash kernels (CPU, ``ops.torch_reference()``, other
+    head dims or dtypes) run SDPA under the rule's mask."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("flash attention: [B, H, T, D] views expected")
     _kv_heads_of(q, k, v, "flash_attention")
     D = q.shape[-1]
-    return _FlashAttn.apply(q, k, v, causal, scale if scale is not None else 1.0 / math.sqrt(D))
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if doc_start is None:
+        return _FlashAttn.apply(q, k, v, causal, scale)
+    _check_doc(doc_start, q.shape[0], q.shape[2], q.device, causal, "flash_attention")
+    if _torch_path(q, D):
+        return _sdpa_doc(q, k, v, doc_start, scale)
+    return _FlashAttn.apply(q, k, v, causal, scale, doc_start)
 
 
 def attention_qkv(qkv: torch.Tensor, h: int, hd: int, causal: bool = True, scale: float | None = None,
-                  kv_heads: int | None = None) -> torch.Tensor:
+                  kv_heads: int | None = None, doc_start: torch.Tensor | None = None) -> torch.Tensor:
     """Attention of the fused QKV output ``[B, T, 3 * h * hd]`` (q | k | v, heads inside each) ->
     ``[B, T, h * hd]``, the output projection's input layout. ``kv_heads``: grouped-query attention, the activation
-    is ``[B, T, (h + 2 kv_heads) * hd]`` (read in place) and so is its gradient."""
+    is ``[B, T, (h + 2 kv_heads) * hd]`` (read in place) and so is its gradient. ``doc_start``: packed documents (the
+    module docstring's rule); with it, an activation off the flash kernels runs SDPA under the rule's mask."""
     hkv = h if kv_heads is None else int(kv_heads)
     check_kv_heads(h, hkv, "attention_qkv")
     if qkv.dim() != 3 or not qkv.is_contiguous() or qkv.shape[-1] != (h + 2 * hkv) * hd:
         raise ValueError("attention_qkv: contiguous [B, T, (h + 2 * kv_heads) * hd] expected "
                          "([B, T, 3 * h * hd] without kv_heads)")
+    scale = scale if scale is not None else 1.0 / math.sqrt(hd)
+    if doc_start is not None:
+        B, T, _ = qkv.shape
+        _check_doc(doc_start, B, T, qkv.device, causal, "attention_qkv")
+        if _torch_path(qkv, hd):
+            return _sdpa_doc(*_qkv_views(qkv, h, hkv, hd), doc_start, scale).transpose(1, 2).reshape(B, T, h * hd)
+        return _FlashAttnQKV.apply(qkv, h, hd, causal, scale, hkv, doc_start)
     if not supported(qkv, hd):
         raise ValueError(f"attention_qkv: bf16 CUDA input with head dim in {HEAD_DIMS} expected")
-    return _FlashAttnQKV.apply(qkv, h, hd, causal, scale if scale is not None else 1.0 / math.sqrt(hd), hkv)
+    return _FlashAttnQKV.apply(qkv, h, hd, causal, scale, hkv)
 
 
 class _SplitHeads(torch.autograd.Function):

@@ -6,7 +6,8 @@
     python tools/kernel_isa_diff.py old new [--vgprs SUBSTRING]
 
 Every kernel of ``old/*.s`` is looked up in ``new/*.s`` by its demangled name, also with one more trailing ``false``
-template argument (a kernel that gained a compile-time flag), and the two instruction streams are compared with labels
+template argument (a kernel that gained a compile-time flag, and maybe trailing parameters that only the flag reads),
+and the two instruction streams are compared with labels
 and symbol names normalised. Prints the kernels that differ or are missing and the count compared / identical; exits 1
 when any differs. ``--vgprs S``: also print ``.amdhsa_next_free_vgpr`` of the new build's kernels whose name holds S."""
 import re
@@ -70,8 +71,8 @@ def main():
             flagged = name[:-1] + ",false>" if name.endswith(">") else name + "<false>"
             hit = by_name.get(name) or by_name.get(flagged)
             if hit is None:  # a name c++filt does not know (a __bf16 parameter): the flag in the mangled name
-                alt = key.replace("EEEv", "ELb0EEEv", 1)
-                hit = alt if alt in new else None
+                alt = key.replace("EEEv", "ELb0EEEv", 1)  # ... which may come with more trailing parameters
+                hit = alt if alt in new else next((n for n in new if n.startswith(alt)), None)
             total += 1
             if hit is not None and new[hit] == old[key]:
                 same += 1
