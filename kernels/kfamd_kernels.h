@@ -625,6 +625,29 @@ int kfamd_gemm_nt_skinny_mx4_glu_path(int path, const void* A, const void* codes
 int kfamd_gemm_nt_skinny_mx4_glu_tiles(int path, int tiles, const void* A, const void* codes, const void* scales,
                                        void* C, const void* bias, int M, int N, int K, long long lda,
                                        long long ldw_bytes, long long lds, long long ldc, float alpha, void* stream);
+// Wide weight-streaming NT GEMM, 1 <= M <= 128 (gemm_stream_wide.hip; meant for 17 .. 128 rows): the M <= 16
+// kernels' formulas, operand rules and epilogues on a bf16 weight, on e4m3fn codes with a row scale, and on MXFP4, and
+// their gated form (N = 2F weight rows, C [M][F]). K % 8 / 16 / 32 == 0 (bf16 / w8 / mx4), A and the weight rows 16-B
+// aligned, unit inner strides, any N, lda, ldc, ldr. tiles: 0 = by (M, N), else 1 / 2 / 4 16-row weight tiles per
+// workgroup. KFAMD_EINVAL: M outside 1..128, K off its grid, a tiles value outside {0, 1, 2, 4}, the epilogue rules
+// above; KFAMD_EALIGN: alignment. Both before any launch. Deterministic (no atomics): a captured launch replays its bits.
+int kfamd_gemm_nt_stream_bf16(int tiles, const void* A, const void* W, void* C, const void* bias, const void* R, int M,
+                              int N, int K, long long lda, long long ldw, long long ldc, long long ldr, float alpha,
+                              int act, void* stream);
+int kfamd_gemm_nt_stream_w8(int tiles, const void* A, const void* codes, const float* wscale, void* C, const void* bias,
+                            const void* R, int M, int N, int K, long long lda, long long ldw, long long ldc,
+                            long long ldr, float alpha, int act, void* stream);
+int kfamd_gemm_nt_stream_mx4(int tiles, const void* A, const void* codes, const void* scales, void* C, const void* bias,
+                             const void* R, int M, int N, int K, long long lda, long long ldw_bytes, long long lds,
+                             long long ldc, long long ldr, float alpha, int act, void* stream);
+int kfamd_gemm_nt_stream_bf16_glu(int tiles, const void* A, const void* W, void* C, const void* bias, int M, int N,
+                                  int K, long long lda, long long ldw, long long ldc, float alpha, void* stream);
+int kfamd_gemm_nt_stream_w8_glu(int tiles, const void* A, const void* codes, const float* wscale, void* C,
+                                const void* bias, int M, int N, int K, long long lda, long long ldw, long long ldc,
+                                float alpha, void* stream);
+int kfamd_gemm_nt_stream_mx4_glu(int tiles, const void* A, const void* codes, const void* scales, void* C,
+                                 const void* bias, int M, int N, int K, long long lda, long long ldw_bytes,
+                                 long long lds, long long ldc, float alpha, void* stream);
 // The gate as its own pass (swiglu_bf16.hip), any row count: z [rows][2F] (row stride ldz >= 2F) -> h [rows][F]
 // (ldh >= F); backward dh [rows][F] (lddh), z -> dz [rows][2F] (lddz): dz[2j] = dh u s (1 + g (1 - s)),
 // dz[2j + 1] = dh silu(g), s = 1 / (1 + exp(-g)). 16-B loads and stores when F % 8 == 0, every stride % 8 == 0

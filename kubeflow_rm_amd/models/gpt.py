@@ -16,7 +16,9 @@ Sampling: ``GPT.generate`` (``prefill`` + ``decode_step`` over an ``ops.KVCache`
 on the decode kernels — the M <= 16 weight-streaming GEMM, the KV append and split-KV single-query
 attention — and can replay the step as one hipGraph (no tensor-parallel group; head dims 64 / 128).
 ``GPT.decode_weights()`` / ``generate(weight_dtype=torch.float8_e4m3fn)`` run the steps of up to 16 rows on
-8-bit copies of the projection weights (W8A16: bf16 activations, fp32 accumulation).
+8-bit copies of the projection weights (W8A16: bf16 activations, fp32 accumulation). ``stream_rows=R`` (16 .. 128, on
+``decode_step`` / ``extend`` / the graphed steps / ``generate``) takes steps of 17 .. R rows to the wide weight-streaming
+GEMM (``ops.gemm_nt(variant="stream")``), on the bf16 or the quantised weights; ``extend`` states the rule.
 ``generate(sampler="fused")`` samples on ``ops.sample`` (top-k, top-p, a stop token; seeded uniforms, so the
 result does not depend on the device) and with ``graph=True`` replays step + sampler + token feedback as
 one hipGraph per token.
@@ -717,15 +719,33 @@ class GPT(torch.nn.Module):
         # more than 16 rows (extend with B * T > 16): the "auto" route, as prefill
         return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual)
 
+    def _stream(self, x, w, bias=None, act="none", residual=None):
+        # 17 .. stream_rows rows: the wide weight-streaming kernel (kernels/gemm_stream_wide.hip), on either weight type
+        return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual, variant="stream")
+
+    @staticmethod
+    def _check_stream_rows(stream_rows) -> int:
+        lo, hi = ops.gemm.SKINNY_MAX_M, ops.gemm.STREAM_MAX_M
+        if isinstance(stream_rows, bool) or not isinstance(stream_rows, int) or not lo <= stream_rows <= hi:
+            raise ValueError(f"stream_rows: an int in {lo} .. {hi} expected, got {stream_rows!r}")
+        return stream_rows
+
+    def _route(self, rows: int, stream_rows: int):
+        """The linear a step of ``rows`` rows runs on (the rule of ``extend``)."""
+        if rows <= ops.gemm.SKINNY_MAX_M:
+            return self._skinny
+        return self._stream if rows <= stream_rows else self._auto
+
     def _fc1(self, lin, y, w, blk):
-        """The up-projection and its activation on the HIP kernels, ``lin`` being ``_skinny`` or ``_auto``. GELU: the
+        """The up-projection and its activation on the HIP kernels, ``lin`` being ``_skinny``, ``_stream`` or ``_auto``. GELU: the
         GEMM's epilogue on either route. SwiGLU: on the weight-streaming route the gated GEMM, one launch as GELU has
         (it won or tied the two-launch form at every measured M, weight format and d_ff: profiles/glu/README.md);
-        on the "auto" route (more than 16 rows, and every prefill) the GEMM to [rows, 2 d_ff], then the elementwise
+        the wide weight-streaming route (17 .. ``stream_rows`` rows) has the same gated launch;
+        on the "auto" route (more rows, and every prefill) the GEMM to [rows, 2 d_ff], then the elementwise
         gate kernel."""
         if not blk.swiglu:
             return lin(y, w, blk.fc1.bias, act=blk.fc1.act)
-        if lin == self._skinny:
+        if lin in (self._skinny, self._stream):
             return lin(y, w, blk.fc1.bias, act="swiglu")
         return ops.swiglu(lin(y, w, blk.fc1.bias))
 
@@ -754,7 +774,7 @@ class GPT(torch.nn.Module):
         bits per weight (``ops.quantize_weight(w, dtype="mxfp4")``); here a matrix stays bf16 when its inner dimension
         is no multiple of 32. Each format has its own memo: asking for one neither returns nor evicts the other's.
 
-        Which steps read them: those of up to 16 rows, see ``extend``; ``prefill`` never does."""
+        Which steps read them: those of up to max(16, ``stream_rows``) rows, see ``extend``; ``prefill`` never does."""
         mx4 = ops.gemm.is_mxfp4(dtype)
         if not mx4 and dtype != torch.float8_e4m3fn:
             raise ValueError(f'decode_weights: torch.float8_e4m3fn or "mxfp4" expected, got {dtype}')
@@ -782,31 +802,36 @@ class GPT(torch.nn.Module):
         self.__dict__[slot] = memo  # not a parameter, buffer or submodule
         return memo
 
-    def _weight_selector(self, weights, rows: int):
-        """(layer, name) -> the weight a step of ``rows`` rows reads in that linear: the 8-bit one when
-        ``weights`` is given and the step takes the weight-streaming route (rows <= 16), else the model's."""
+    def _weight_selector(self, weights, rows: int, stream_rows: int = 16):
+        """(layer, name) -> the weight a step of ``rows`` rows reads in that linear: the quantised one when
+        ``weights`` is given and the step takes a weight-streaming route (rows <= max(16, stream_rows)), else the
+        model's."""
         if weights is not None and not isinstance(weights, DecodeWeights):
             raise TypeError("weights: a DecodeWeights (GPT.decode_weights()) expected")
-        if weights is None or rows > ops.gemm.SKINNY_MAX_M:
+        if weights is None or rows > max(ops.gemm.SKINNY_MAX_M, stream_rows):
             return lambda li, name: getattr(self.blocks[li], name).weight
         if len(weights.blocks) != len(self.blocks):
             raise ValueError("weights do not match the model")
         return lambda li, name: weights.blocks[li][name]
 
-    def _head_weight(self, weights, rows: int):
-        return self.tok if weights is None or rows > ops.gemm.SKINNY_MAX_M else weights.head
+    def _head_weight(self, weights, rows: int, stream_rows: int = 16):
+        return self.tok if weights is None or rows > max(ops.gemm.SKINNY_MAX_M, stream_rows) else weights.head
 
     @torch.no_grad()
-    def decode_step(self, tok: torch.Tensor, cache, weights: "DecodeWeights | None" = None) -> torch.Tensor:
+    def decode_step(self, tok: torch.Tensor, cache, weights: "DecodeWeights | None" = None,
+                    stream_rows: int = 16) -> torch.Tensor:
         """One new token ``tok [B]`` per row against ``cache``; logits ``[B, vocab]``. Advances the cache.
-        ``weights`` (``decode_weights()``): a step of B <= 16 rows reads the 8-bit weights in every linear and
-        in the LM head; a wider batch reads the bf16 weights (the rule of ``extend``)."""
+        ``weights`` (``decode_weights()``) and ``stream_rows``: the rule of ``extend`` at B rows. A step of
+        B <= max(16, stream_rows) rows runs every linear and the LM head on a weight-streaming kernel and reads the
+        quantised weights when given; a wider batch runs the "auto" route on the bf16 weights."""
         B = tok.shape[0]
+        stream_rows = self._check_stream_rows(stream_rows)
         self._check_cache(cache, B, 1)
         native = self._native_decode(self.tok)
         h, hd = self.blocks[0].local_heads, self.cfg.head_dim
-        wsel = self._weight_selector(weights, B)
-        head_w = self._head_weight(weights, B)
+        wsel = self._weight_selector(weights, B, stream_rows)
+        head_w = self._head_weight(weights, B, stream_rows)
+        lin = self._route(B, stream_rows)
         x = F.embedding(tok, self.tok)  # [B, d_model]
         if self.pos is not None:
             x = x + F.embedding(cache.lens, self.pos)
@@ -821,13 +846,14 @@ class GPT(torch.nn.Module):
             ops.attention_decode(q, cache, li, out=a.view(B, h, hd), **att)
             return a
         for li, blk in enumerate(self.blocks):
-            x = self._cache_layer(blk, li, x, cache, native=native, lin=self._skinny, w=wsel, attend=attend)
+            x = self._cache_layer(blk, li, x, cache, native=native, lin=lin, w=wsel, attend=attend)
         cache.advance(1)
-        return self._lm_head(x, head_w, self._skinny, native)
+        return self._lm_head(x, head_w, lin, native)
 
     @torch.no_grad()
     def extend(self, idx: torch.Tensor, cache, last_only: bool = False,
-               weights: "DecodeWeights | None" = None, chunk: int | None = None) -> torch.Tensor:
+               weights: "DecodeWeights | None" = None, chunk: int | None = None,
+               stream_rows: int = 16) -> torch.Tensor:
         """Append ``idx [B, T]`` (T >= 1 tokens per row) to ``cache`` in any state, empty included; logits
         ``[B, T, vocab]`` of every new position (``[B, vocab]`` of the last one with ``last_only``).
         Advances the cache by T. On the GPU a step of up to 16 tokens runs the decode kernels with
@@ -843,6 +869,13 @@ class GPT(torch.nn.Module):
         are there). The rule looks at row counts only, on every device: the CPU / ``ops.torch_reference()``
         path applies it with the dequantised weights.
 
+        ``stream_rows`` (16 .. 128, default 16) moves the row count up to which a step streams its weights. The rule,
+        for a step of ``rows`` rows (B for ``decode_step``, B * T per chunk here; the LM head by its own row count):
+        ``rows <= 16``: the M <= 16 weight-streaming kernels, as ever. ``16 < rows <= stream_rows``: every linear on
+        ``ops.gemm_nt(variant="stream")`` (``kernels/gemm_stream_wide.hip``), SwiGLU as its gated launch, reading
+        ``weights`` (either format) when given. More rows: the "auto" route on the model's bf16 weights. With the
+        default nothing above 16 rows streams; the torch path selects its weights by the same rule.
+
         ``chunk=N`` (16 < N <= the cache's capacity): the input runs in steps of N tokens per row instead of 16,
         attention on ``ops.attention_chunk`` (MFMA query tiles over the cache, K / V read once per 128 new
         rows), the linears on the route the step's row count B * N picks (the bf16 weights above 16 rows,
@@ -853,6 +886,7 @@ class GPT(torch.nn.Module):
         described above, unchanged."""
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError(f"extend: idx [B, T >= 1] expected, got {tuple(idx.shape)}")
+        stream_rows = self._check_stream_rows(stream_rows)
         B, T = idx.shape
         if not cache.ring:
             self._check_cache(cache, B, T)
@@ -872,13 +906,14 @@ class GPT(torch.nn.Module):
             final = t0 + R >= T
             if last_only and not final:
                 self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none", weights=weights,
-                                   mfma=chunk is not None)
+                                   mfma=chunk is not None, stream_rows=stream_rows)
             else:
                 outs.append(self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="last" if last_only else "all",
-                                               weights=weights, mfma=chunk is not None))
+                                               weights=weights, mfma=chunk is not None, stream_rows=stream_rows))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
 
-    def _extend_chunk(self, idx, cache, native: bool, head: str, weights=None, mfma: bool = False):
+    def _extend_chunk(self, idx, cache, native: bool, head: str, weights=None, mfma: bool = False,
+                      stream_rows: int = 16):
         """One extend step of T tokens per row (T <= 16 on ``ops.attention_extend``; any T with ``mfma``, on
         ``ops.attention_chunk``); ``head``: LM head on "all" rows, the "last", or "none"."""
         B, T = idx.shape
@@ -891,8 +926,8 @@ class GPT(torch.nn.Module):
             x = x + F.embedding(pos, self.pos)
         # the step's attention sees the rows it appends: lens + T, computed on the device
         att = self._att(cache, T, c.window)
-        lin = self._skinny if B * T <= ops.gemm.SKINNY_MAX_M else self._auto
-        wsel = self._weight_selector(weights, B * T)
+        lin = self._route(B * T, stream_rows)
+        wsel = self._weight_selector(weights, B * T, stream_rows)
 
         def attend(li, qkv, native):
             q = qkv[..., :h * hd].view(B, T, h, hd)
@@ -912,8 +947,8 @@ class GPT(torch.nn.Module):
         if head == "last":
             x = x[:, -1].contiguous()  # [B, d_model]
         rows = x.numel() // c.d_model  # the head's own row count picks its weight and its route
-        head_w = self._head_weight(weights, rows)
-        head_lin = self._skinny if rows <= ops.gemm.SKINNY_MAX_M else self._auto
+        head_w = self._head_weight(weights, rows, stream_rows)
+        head_lin = self._route(rows, stream_rows)
         if not native:
             return self._lm_head(x, head_w, head_lin, False)
         return self._lm_head(x.reshape(rows, c.d_model), head_w, head_lin, True).view(*x.shape[:-1], c.vocab_size)
@@ -976,7 +1011,8 @@ class GPT(torch.nn.Module):
                  lookahead: int = 4, return_stats: bool = False, kv_dtype: torch.dtype | None = None,
                  weight_dtype: torch.dtype | None = None, top_p: float | None = None, stop_token: int | None = None,
                  sampler: str = "torch", prefill_chunk: int | None = None, ring: bool = False, paged: bool = False,
-                 num_samples: int | None = None, pool: "ops.PagePool | None" = None, return_cache: bool = False):
+                 num_samples: int | None = None, pool: "ops.PagePool | None" = None, return_cache: bool = False,
+                 stream_rows: int = 16):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -993,6 +1029,10 @@ class GPT(torch.nn.Module):
         own): every step of up to 16 rows reads 8-bit projection weights and LM head, half the bytes of a
         small-batch step; the prompt's ``prefill`` and steps of more rows read the bf16 weights. It combines
         freely with ``kv_dtype`` and ``graph``. Any other dtype raises.
+
+        ``stream_rows`` (16 .. 128): decode steps of up to that many rows (``B``, or ``B * num_samples``) stream their
+        weights, the quantised ones with ``weight_dtype`` (the rule of ``extend``); the default 16 leaves wider batches
+        on the "auto" route and the bf16 weights. The prompt is not a decode step and ignores it.
 
         ``sampler``: ``"torch"`` (the default) is the sampler described above; ``top_p`` / ``stop_token`` raise
         with it. ``"fused"`` samples every token with ``ops.sample`` (one HIP kernel on the GPU, the same rule
@@ -1033,6 +1073,7 @@ class GPT(torch.nn.Module):
         ``return_cache=True`` (paged only): returns ``(tokens, cache)`` and leaves the pages held, for a follow-up turn
         or a look at ``cache.pool``; call ``cache.release()`` when done. Not built (raises): ``paged`` / ``num_samples``
         with ``draft=``, with ``ring`` or a windowed model, or with a tensor-parallel group that issues collectives."""
+        stream_rows = self._check_stream_rows(stream_rows)
         if num_samples is not None:
             if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
                 raise ValueError(f"generate(num_samples=...): an int >= 1 expected, got {num_samples!r}")
@@ -1116,11 +1157,11 @@ class GPT(torch.nn.Module):
         weights = self.decode_weights(weight_dtype) if weight_dtype is not None else None
         if sampler == "fused":
             out = self._generate_fused(idx, logits, cache, weights, max_new_tokens, temperature, top_k, top_p,
-                                       stop_token, generator, graph)
+                                       stop_token, generator, graph, stream_rows)
         else:
-            step = lambda t: self.decode_step(t, cache, weights=weights)  # noqa: E731
+            step = lambda t: self.decode_step(t, cache, weights=weights, stream_rows=stream_rows)  # noqa: E731
             if graph and max_new_tokens > 1:
-                step = self.graphed_decode_step(cache, weights=weights)
+                step = self.graphed_decode_step(cache, weights=weights, stream_rows=stream_rows)
             out = [idx]
             for i in range(max_new_tokens):
                 nxt = _sample(logits, temperature, top_k, generator)
@@ -1136,7 +1177,7 @@ class GPT(torch.nn.Module):
 
 
     def _generate_fused(self, idx, logits, cache, weights, S: int, temperature, top_k, top_p, stop_token, generator,
-                        graph: bool):
+                        graph: bool, stream_rows: int = 16):
         """The token loop of ``generate(sampler="fused")`` after the prefill (``logits``: its output)."""
         B, dev = idx.shape[0], idx.device
         u = torch.rand(S, B, generator=generator, device=generator.device if generator is not None else "cpu").to(dev)
@@ -1149,20 +1190,21 @@ class GPT(torch.nn.Module):
         ops.sample(logits, u, **kw)  # the first token: from the prefill's logits, eagerly
         step.add_(1)
         if graph and S > 1:
-            g = self.graphed_generate_step(cache, weights, tok=tok, u=u, **{k: v for k, v in kw.items() if k != "out"})
+            g = self.graphed_generate_step(cache, weights, tok=tok, u=u, stream_rows=stream_rows,
+                                           **{k: v for k, v in kw.items() if k != "out"})
             for _ in range(S - 1):
                 g.replay()
         else:
             for _ in range(S - 1):
-                ops.sample(self.decode_step(tok, cache, weights=weights), u, **kw)
+                ops.sample(self.decode_step(tok, cache, weights=weights, stream_rows=stream_rows), u, **kw)
                 step.add_(1)
         return torch.cat([idx, seq], 1)
 
     def graphed_generate_step(self, cache, weights: "DecodeWeights | None" = None, *, tok: torch.Tensor,
                               u: torch.Tensor, step: torch.Tensor, temperature: float = 1.0, top_k: int | None = None,
                               top_p: float | None = None, seq: torch.Tensor | None = None,
-                              done: torch.Tensor | None = None,
-                              stop_token: int | None = None) -> "_GraphedGenerateStep":
+                              done: torch.Tensor | None = None, stop_token: int | None = None,
+                              stream_rows: int = 16) -> "_GraphedGenerateStep":
         """``decode_step(tok) -> ops.sample(..., out=tok) -> step += 1`` on ``cache`` captured once into a
         hipGraph, on a single stream: ``tok`` (int64 ``[B]``) is both the step's input and the sampler's
         output, so each ``replay()`` of the result turns the token of one position into the token of the next
@@ -1174,7 +1216,8 @@ class GPT(torch.nn.Module):
         the host-side capacity check is kept (a ``replay()`` with no free cache row raises like
         ``decode_step``). The cache needs one free row, and ``step`` one free row of ``u``, for the warm-up
         step, whose effects (``lens``, ``step``, ``tok``, ``seq``, ``done``) are undone here. The graph holds the
-        tensors' addresses: the returned object keeps them (and ``weights``) alive."""
+        tensors' addresses: the returned object keeps them (and ``weights``) alive. ``stream_rows``: as ``decode_step``."""
+        stream_rows = self._check_stream_rows(stream_rows)
         limit = self.cfg.max_seq if cache.ring else cache.capacity
         if cache._bound + 1 > limit:
             raise ValueError("graphed_generate_step needs a free cache row")
@@ -1189,7 +1232,8 @@ class GPT(torch.nn.Module):
             cache._bound = bound
             if hlen is not None:  # the warm-up took the step's page; the capture finds it and changes nothing
                 cache._hlen = list(hlen)
-            ops.sample(self.decode_step(t, cache, weights=weights), u, temperature=temperature, top_k=top_k,
+            ops.sample(self.decode_step(t, cache, weights=weights, stream_rows=stream_rows), u,
+                       temperature=temperature, top_k=top_k,
                        top_p=top_p, step=step, out=t, seq=seq, done=done, stop_token=stop_token)
             step.add_(1)
 
@@ -1202,13 +1246,15 @@ class GPT(torch.nn.Module):
             cache._hlen = list(hlen)
         return _GraphedGenerateStep(g, cache, (weights, u, step, tok, seq, done), limit)
 
-    def graphed_decode_step(self, cache, weights: "DecodeWeights | None" = None) -> "_GraphedDecodeStep":
+    def graphed_decode_step(self, cache, weights: "DecodeWeights | None" = None,
+                            stream_rows: int = 16) -> "_GraphedDecodeStep":
         """``decode_step`` on ``cache`` captured once into a hipGraph (its attention grid sized for the
         whole capacity); each call replays it on a new token ``[B]`` and returns the logits, valid until
         the next call. The position lives in the device-side ``cache.lens``, which the replay advances;
         the host-side bound follows, and a call with no free cache row raises like ``decode_step``. The
-        cache needs one free row for the warm-up step, whose effect on ``lens`` is undone here. ``weights``: as
-        ``decode_step``; the graph holds the quantised tensors' addresses, so keep the object alive."""
+        cache needs one free row for the warm-up step, whose effect on ``lens`` is undone here. ``weights`` and
+        ``stream_rows``: as ``decode_step``; the graph holds the quantised tensors' addresses, so keep the object alive."""
+        stream_rows = self._check_stream_rows(stream_rows)
         limit = self.cfg.max_seq if cache.ring else cache.capacity
         if cache._bound + 1 > limit:
             raise ValueError("graphed_decode_step needs a free cache row")
@@ -1221,7 +1267,7 @@ class GPT(torch.nn.Module):
             cache._bound = bound
             if hlen is not None:  # the warm-up took the step's page; the capture finds it and changes nothing
                 cache._hlen = list(hlen)
-            return self.decode_step(t, cache, weights=weights)
+            return self.decode_step(t, cache, weights=weights, stream_rows=stream_rows)
 
         g = ops.GraphedCallable(step, torch.zeros(cache.B, dtype=torch.long, device=cache.lens.device), warmup=1)
         torch.cuda.current_stream().synchronize()

@@ -238,6 +238,18 @@ _SIGNATURES = {
                                                   c_ll, c_ll, c_float, c_vp]),
     "kfamd_gemm_nt_skinny_mx4_glu_tiles": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                                    c_ll, c_ll, c_ll, c_ll, c_float, c_vp]),
+    "kfamd_gemm_nt_stream_bf16": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                          c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_stream_w8": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                        c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_stream_mx4": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                         c_ll, c_ll, c_float, c_int, c_vp]),
+    "kfamd_gemm_nt_stream_bf16_glu": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                              c_float, c_vp]),
+    "kfamd_gemm_nt_stream_w8_glu": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                            c_float, c_vp]),
+    "kfamd_gemm_nt_stream_mx4_glu": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                             c_ll, c_float, c_vp]),
     "kfamd_swiglu_fwd_bf16": (c_int, [c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_vp]),
     "kfamd_swiglu_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_ll, c_vp]),
     "kfamd_rmsnorm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp]),

@@ -19,6 +19,8 @@ VARIANTS = {"auto": 0, "fast": 1, "generic": 2, "pipe": 3, "pipe_sched": 4, "w4"
 # the M <= 16 weight-streaming kernel: "skinny" picks VALU / MFMA by M, the other two force one (bench)
 SKINNY_PATHS = {"skinny": 0, "skinny_valu": 1, "skinny_mfma": 2}
 SKINNY_MAX_M = 16
+# the wide weight-streaming kernel (kernels/gemm_stream_wide.hip), variant "stream": up to this many rows
+STREAM_MAX_M = 128
 FP8 = torch.float8_e4m3fn
 
 
@@ -326,6 +328,78 @@ def _gemm_nt_swiglu(a, w, bias, residual, alpha, out, variant, tiles: int = 0):
     return out
 
 
+def gemm_nt_stream(a, b, *, bias=None, residual=None, alpha: float = 1.0, act: str = "none", out=None,
+                   tiles: int = 0):
+    """``gemm_nt(..., variant="stream")``: the wide weight-streaming kernel (``kernels/gemm_stream_wide.hip``) for a
+    non-batched call of ``1 <= M <= STREAM_MAX_M`` rows (built for 17 .. 128) on a bf16 weight, a ``QuantizedWeight``
+    or an ``MXFP4Weight`` (K % 8 / 16 / 32 == 0), ``act="swiglu"`` (``ops/swiglu.py``'s rule, output ``[..., N / 2]``,
+    no residual) included. Outside the contract it raises ``ValueError``: no other kernel, no dequantised copy.
+    ``tiles`` (tests / bench): 0 lets the launcher choose, 1 / 2 / 4 force the 16-row weight tiles per workgroup."""
+    mx4, w8 = isinstance(b, MXFP4Weight), isinstance(b, QuantizedWeight)
+    glu = act == "swiglu"
+    if not glu and act not in ACTS:
+        raise ValueError(f'gemm_nt variant="stream": act in {sorted(ACTS)} or "swiglu" expected, got {act!r}')
+    if tiles not in (0, 1, 2, 4):
+        raise ValueError(f'gemm_nt variant="stream": tiles in (0, 1, 2, 4) expected, got {tiles!r}')
+    _check_operand(a, "a")
+    wt = b.codes if (mx4 or w8) else b
+    if not (mx4 or w8):
+        _check_operand(b, "b")
+    if len(b.shape) != 2:
+        raise ValueError(f'gemm_nt variant="stream": a non-batched weight [N, K] expected, got {tuple(b.shape)}')
+    if not wt.is_cuda or wt.device != a.device:
+        raise ValueError("gemm_nt: the weight must live on a's GPU")
+    N, K = b.shape
+    if a.shape[-1] != K:
+        raise ValueError(f"inner dims differ: a has K={a.shape[-1]}, the weight has K={K}")
+    scales = b.scales if mx4 else (b.scale if w8 else None)
+    if wt.stride(1) != 1 or (scales is not None and not scales.is_contiguous()):
+        raise ValueError("gemm_nt: a weight with a unit inner stride (and contiguous scales) expected")
+    a2 = a.reshape(-1, K) if a.dim() != 2 else a
+    M = a2.shape[0]
+    kq = 32 if mx4 else (16 if w8 else 8)
+    if not 1 <= M <= STREAM_MAX_M or K < kq or K % kq:
+        raise ValueError(f'gemm_nt variant="stream": 1 <= M <= {STREAM_MAX_M}, K >= {kq} and K % {kq} == 0 expected, '
+                         f"got M={M} K={K}")
+    if glu and (N % 2 or residual is not None):
+        raise ValueError('gemm_nt(act="swiglu"): an even number of weight rows (gate / up pairs) and no residual '
+                         f"expected, got N={N}")
+    if residual is not None and act != "none":
+        raise ValueError("gemm_nt: a residual goes with act='none'")
+    No = N // 2 if glu else N
+    out_shape = (*a.shape[:-1], No)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.bfloat16, device=a.device)
+    else:
+        _check_operand(out, "out")
+        if out.device != a.device or tuple(out.shape) != tuple(out_shape):
+            raise ValueError(f"out must be a bf16 {tuple(out_shape)} tensor on {a.device}, got {tuple(out.shape)} on "
+                             f"{out.device}")
+    c2 = out.view(M, No)
+    bp = None
+    if bias is not None:
+        _check_operand(bias, "bias")
+        if bias.numel() != N or not bias.is_contiguous():
+            raise ValueError("bias must be a contiguous [N] tensor")
+        bp = bias.data_ptr()
+    L, st = _lib.lib(), _stream_ptr(a)
+    head = (int(tiles), a2.data_ptr(), wt.data_ptr(), *((scales.data_ptr(),) if scales is not None else ()),
+            c2.data_ptr(), bp)
+    ldw = (a2.stride(0), wt.stride(0), *((scales.stride(0),) if mx4 else ()), c2.stride(0))
+    fmt = "mx4" if mx4 else ("w8" if w8 else "bf16")
+    if glu:
+        rc = getattr(L, f"kfamd_gemm_nt_stream_{fmt}_glu")(*head, M, N, K, *ldw, float(alpha), st)
+    else:
+        r_ptr, ldr = None, 0
+        if residual is not None:
+            _check_operand(residual, "residual")
+            r2 = residual.reshape(M, N)
+            r_ptr, ldr = r2.data_ptr(), r2.stride(0)
+        rc = getattr(L, f"kfamd_gemm_nt_stream_{fmt}")(*head, r_ptr, M, N, K, *ldw, ldr, float(alpha), ACTS[act], st)
+    _lib.check(rc, f"gemm_nt[stream {fmt}{' swiglu' if glu else ''} {M}x{N}x{K}]")
+    return out
+
+
 def _stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -419,7 +493,11 @@ def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight | MXFP4Weight", 
     (K % 32 == 0): the MXFP4 weight-streaming kernel (``kernels/gemm_skinny_mx4.hip``).
     ``act="swiglu"`` (the three skinny variants only; ``b``'s rows interleaved gate / up, ``ops/swiglu.py``): C =
     silu(z[..., 2j]) * z[..., 2j + 1] of z = alpha * a @ b^T + bias, shape ``[..., N / 2]``, in the GEMM's one launch;
-    a residual, an odd N or any other variant raises ``ValueError``."""
+    a residual, an odd N or any other variant raises ``ValueError``.
+    ``variant="stream"``: the wide weight-streaming kernel for a non-batched call of up to ``STREAM_MAX_M`` = 128 rows
+    on any of the three weight types, ``act="swiglu"`` included (``gemm_nt_stream``); outside its contract it raises."""
+    if variant == "stream":
+        return gemm_nt_stream(a, b, bias=bias, residual=residual, alpha=alpha, act=act, out=out)
     if act == "swiglu":
         return _gemm_nt_swiglu(a, b, bias, residual, alpha, out, variant)
     if isinstance(b, QuantizedWeight):

@@ -86,6 +86,12 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         interleaved in one process, medians of 7 blocks with min and max. Model: a graphed gpt-1b step (gpt-small
         with --quick) at position about 4000 with W = 1024, flat against ring, B in {1, 8}, 7 interleaved runs.
         nbytes: both caches for gpt-1b shapes at max_seq = 32768, W = 4096, B in {1, 16} (meta device, no timing).
+  stream (not in the default list) the wide weight-streaming GEMM. Kernel: gemm_nt(variant="stream") at M in {17, 32,
+        64, 128} on the gpt-1b shapes and the gated 16384 x 2048, bf16 / FP8 / MXFP4 weights rotated past the last-level
+        cache, every tiles value forced, against variant="auto" on bf16 at the same M and the M = 16 skinny call; 7
+        interleaved blocks: us, min - max, TB/s of weight bytes. Model: a graphed gpt-1b decode step (gpt-small with
+        --quick) at position about 2048, B in {32, 64, 128}: stream_rows=128 on the three weight formats against
+        stream_rows=16, bf16 and FP8 caches.
 """
 from __future__ import annotations
 
@@ -103,7 +109,7 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "mx4": 900, "sample": 420,
-                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600, "ring": 900}
+                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600, "ring": 900, "stream": 1100}
 WINDOW_WS = (256, 1024, 4095, 4096)
 GQA_GS = (1, 2, 4, 8, 16)
 GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
@@ -1542,7 +1548,98 @@ def step_window(quick: bool):
     return {"kernel": _window_kernel_rows(quick), "model": _window_model_rows(quick)}
 
 
-STEPS = {"ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8, "mx4": step_mx4}
+STREAM_MS = (17, 32, 64, 128)
+
+
+def _stream_kernel_rows(quick: bool):
+    """us per call of gemm_nt(variant="stream") on the gpt-1b shapes and the gated 16384 x 2048: three weight formats,
+    every tiles value forced and the launcher's choice, against variant="auto" on bf16 at the same M (the only route
+    before) and the M = 16 skinny call; TB/s of weight bytes."""
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    shapes = [(N, K, False) for N, K in GEMM_SHAPES] + [(16384, 2048, True)]
+    for N, K, glu in shapes[:2] + shapes[-1:] if quick else shapes:
+        ncopy = 2 if quick else max(2, -(-(1024 << 20) // (N * K)))
+        ws = [torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16) for _ in range(ncopy)]
+        fmts = {"bf16": ws, "fp8": [ops.quantize_weight(w) for w in ws],
+                "mx4": [ops.quantize_weight(w, dtype="mxfp4") for w in ws]}
+        nbytes = {"bf16": 2 * N * K, "fp8": fmts["fp8"][0].nbytes, "mx4": fmts["mx4"][0].nbytes}
+        bias = torch.randn(N, device="cuda").to(torch.bfloat16)
+        act = "swiglu" if glu else "none"
+        a16 = torch.randn(16, K, device="cuda").to(torch.bfloat16)
+        for M in STREAM_MS[1::2] if quick else STREAM_MS:
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            out = torch.empty(M, N // 2 if glu else N, device="cuda", dtype=torch.bfloat16)
+
+            def stream(f, tiles):
+                return lambda i: ops.gemm_nt_stream(a, fmts[f][i % ncopy], bias=bias, act=act, out=out, tiles=tiles)
+
+            fns = {f"{f}_t{t}": stream(f, t) for f in fmts for t in (0, 1, 2, 4)}
+            fns["skinny16_bf16"] = lambda i: ops.gemm_nt(a16, ws[i % ncopy], bias=bias, act=act, variant="skinny")
+            if glu:  # the route before: the GEMM to [M, 2F], then the gate kernel
+                fns["auto_bf16"] = lambda i: ops.swiglu(ops.gemm_nt(a, ws[i % ncopy], bias=bias))
+            else:
+                fns["auto_bf16"] = lambda i: ops.gemm_nt(a, ws[i % ncopy], bias=bias, out=out)
+            r = _time_blocks(fns, blocks=5 if quick else 7, iters=min(ncopy, 32))
+            row = {"M": M, "N": N, "K": K, "gated": glu, "weight_copies": ncopy, **r}
+            for f in fmts:
+                row[f"{f}_TBps"] = nbytes[f] / r[f"{f}_t0"]["median_us"] / 1e6
+                row[f"auto_over_{f}"] = r["auto_bf16"]["median_us"] / r[f"{f}_t0"]["median_us"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del ws, fmts
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _stream_model_rows(model, name: str, B: int, quick: bool):
+    """A graphed decode step at position about 2048 (zero K / V: the kernels' time does not depend on the values):
+    stream_rows=128 on bf16 / FP8 / MXFP4 weights against stream_rows=16 (the "auto" route on the bf16 weights whatever
+    ``weights`` is), bf16 and FP8 caches; ms per step, interleaved blocks."""
+    import torch
+    pos, cap, iters = 2000, 2048, 4
+    weights = {"bf16": None, "fp8": model.decode_weights(), "mx4": model.decode_weights("mxfp4")}
+    toks = torch.randint(0, model.cfg.vocab_size, (B,), device="cuda")
+    row = {"model": name, "B": B, "position": pos}
+    for kv, kv_dtype in (("kvbf16", None), ("kvfp8", torch.float8_e4m3fn)):
+        cache = model.new_cache(B, cap, kv_dtype=kv_dtype)
+        graphs = {}
+        for key, w, sr in [("auto16", None, 16)] + [(f"stream128_{k}", w, 128) for k, w in weights.items()]:
+            cache.set_lens([pos] * B)
+            graphs[key] = model.graphed_decode_step(cache, weights=w, stream_rows=sr)
+        times = {k: [] for k in graphs}
+        for b in range(-1, 3 if quick else 7):  # block -1: warm-up, not recorded
+            for k, g in graphs.items():
+                cache.set_lens([pos] * B)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    g(toks)
+                e1.record()
+                e1.synchronize()
+                if b >= 0:
+                    times[k].append(e0.elapsed_time(e1) / iters)
+        for k, v in times.items():
+            row[f"{kv}_{k}"] = {"ms_per_step": statistics.median(v), "min": min(v), "max": max(v)}
+        del graphs, cache
+        torch.cuda.empty_cache()
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def step_stream(quick: bool):
+    import torch
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    result = {"kernel": _stream_kernel_rows(quick), "model": []}
+    name = "gpt-small" if quick else "gpt-1b"
+    model = GPT(CONFIGS[name], device="cuda").eval()
+    for B in (32,) if quick else (32, 64, 128):
+        result["model"].append(_stream_model_rows(model, name, B, quick))
+    return result
+
+
+STEPS = {"stream": step_stream, "ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8, "mx4": step_mx4}
 
 
 def main() -> int:
