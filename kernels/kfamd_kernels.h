@@ -648,6 +648,24 @@ int kfamd_gemm_nt_stream_w8_glu(int tiles, const void* A, const void* codes, con
 int kfamd_gemm_nt_stream_mx4_glu(int tiles, const void* A, const void* codes, const void* scales, void* C,
                                  const void* bias, int M, int N, int K, long long lda, long long ldw_bytes,
                                  long long lds, long long ldc, float alpha, void* stream);
+
+// Dense W8A8 FP8 NT GEMM (gemm_fp8.hip; the rule: ops/gemm.py's docstring), for prefill and chunk steps:
+//   C[m][n] = act(alpha * a_scale[m] * w_scale[n] * sum_k a_codes[m][k] * w_codes[n][k] + bias[n]) (+ R[m][n])
+// Both operands OCP e4m3fn codes, K contiguous (row strides lda / ldw in bytes, multiples of 16, 16-B aligned bases),
+// one fp32 scale per row; bias, R, C bf16, any ldc / ldr; fp32 accumulation on v_mfma_f32_32x32x64_f8f6f4, one RNE
+// rounding. Any M, N >= 1; K >= 16, K % 16 == 0; (rows - 1) * ld + K below 2^31 for both operands. Nothing at or
+// past row M / N or byte K of a row is read as data. plan: 0 = kfamd_gemm_nt_fp8_plan(M, N) (2 at every shape,
+// as measured), 1 = the 256 x 256 tile, 2 = the 128 x 128 tile. KFAMD_EINVAL / KFAMD_EALIGN before any launch. No atomics: a captured launch
+// replays its bits.
+int kfamd_gemm_nt_fp8_plan(int M, int N);
+int kfamd_gemm_nt_fp8(int plan, const void* a_codes, const float* a_scale, const void* w_codes, const float* w_scale,
+                      void* C, const void* bias, const void* R, int M, int N, int K, long long lda, long long ldw,
+                      long long ldc, long long ldr, float alpha, int act, void* stream);
+// bf16 rows x [M][K] (row stride ldx elements, % 8, 16-B aligned base; K % 8 == 0) -> e4m3fn codes [M][K] (row stride
+// ldq bytes, % 8, 8-B aligned base) and scale [M] fp32, bit for bit ops.decode.quantize_rows: scale = amax / 448 (1
+// for a zero row), code = RNE_e4m3(clamp(x / scale, -448, 448)). One wave per row.
+int kfamd_quantize_rows_bf16(const void* x, void* codes, float* scale, int M, int K, long long ldx, long long ldq,
+                             void* stream);
 // The gate as its own pass (swiglu_bf16.hip), any row count: z [rows][2F] (row stride ldz >= 2F) -> h [rows][F]
 // (ldh >= F); backward dh [rows][F] (lddh), z -> dz [rows][2F] (lddz): dz[2j] = dh u s (1 + g (1 - s)),
 // dz[2j + 1] = dh silu(g), s = 1 / (1 + exp(-g)). 16-B loads and stores when F % 8 == 0, every stride % 8 == 0

@@ -84,7 +84,7 @@ TU_FLAGS = {"attention_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 # budget (attn_chunk_split<Fp8Rows, 128, true>: 255 of 256), and a spill there costs time without failing any
 # test. The compiler's resource remarks are read at build time; a kernel with scratch fails the build.
 NO_SCRATCH_TUS = ("attn_kv.hip", "attn_kv_mfma.hip", "rope_bf16.hip", "gemm_skinny_mx4.hip", "attention_bf16.hip",
-                  "gemm_stream_wide.hip")
+                  "gemm_stream_wide.hip", "gemm_fp8.hip")
 
 
 def check_no_scratch(src: Path, remarks: str) -> None:
@@ -148,7 +148,7 @@ def build_kernels(force: bool = False, jobs: int = 8) -> Path:
 # gfx950 code object). A host compile that drops a template's kernel stubs still links and still
 # exits 0, leaving a library whose launches fail at run time: refuse to install it.
 REQUIRED_KERNELS = ("gemm_w4", "gemm_nt_256p", "gemm_nt_128", "norm_fwd_wave", "ln_bwd_dx_wave",
-                    "allreduce_oneshot")
+                    "allreduce_oneshot", "gemm_fp8_nt", "quantize_rows_bf16")
 
 
 def kernel_descriptors(lib: Path) -> set[str]:

@@ -627,7 +627,7 @@ class GPT(torch.nn.Module):
         goes with them (none on a ring: its grid does not come from it) and the window."""
         return {"lens": cache.lens_after(T), "t_bound": None if cache.ring else cache.bound_after(T), "window": window}
 
-    def _cache_layer(self, blk, li: int, x, cache, *, native: bool, lin, w, attend):
+    def _cache_layer(self, blk, li: int, x, cache, *, native: bool, lin, w, attend, w8a8: bool = False):
         """One layer against ``cache``, the body ``prefill``, ``decode_step`` and ``_extend_chunk`` share. They vary
         ``lin`` (``self._skinny`` or ``self._auto``), ``w(li, name)`` (the weight of "qkv" / "proj" / "fc1" / "fc2":
         ``_weight_selector``) and ``attend(li, qkv, native)``, the attention over the QKV linear's output as the linear
@@ -640,6 +640,13 @@ class GPT(torch.nn.Module):
             ops.kv_append(qkv.view(cache.B, -1, qkv.shape[-1]), cache, li, q_heads=h, rope=rope)
             x = lin(attend(li, qkv, True), w(li, "proj"), blk.proj.bias, residual=x)
             y = self._fc1(lin, blk.ln2.fwd(x), w(li, "fc1"), blk)
+            return lin(y, w(li, "fc2"), blk.fc2.bias, residual=x)
+        if w8a8:  # (the caller routed to _w8a8) the W8A8 rule in torch, with the kernel's epilogues and one rounding
+            lin = self._w8a8_nd
+            qkv = lin(blk.ln1(x), w(li, "qkv"), blk.qkv.bias)
+            ops.kv_append(qkv.view(cache.B, -1, qkv.shape[-1]), cache, li, q_heads=h, rope=rope)
+            x = lin(attend(li, qkv, False), w(li, "proj"), blk.proj.bias, residual=x)
+            y = self._fc1(lin, blk.ln2(x), w(li, "fc1"), blk)
             return lin(y, w(li, "fc2"), blk.fc2.bias, residual=x)
         qkv = _flinear(blk.ln1(x), w(li, "qkv"), blk.qkv.bias)
         ops.kv_append(qkv.view(cache.B, -1, qkv.shape[-1]), cache, li, q_heads=h, rope=rope)
@@ -655,7 +662,8 @@ class GPT(torch.nn.Module):
         return _flinear(self.ln_f(x), w)
 
     @torch.no_grad()
-    def prefill(self, idx: torch.Tensor, cache) -> torch.Tensor:
+    def prefill(self, idx: torch.Tensor, cache, weights: "DecodeWeights | None" = None,
+                w8a8: bool = False) -> torch.Tensor:
         """Run the prompt ``idx [B, T0]`` into an empty ``cache``; logits ``[B, vocab]`` of the last position.
         The prompt's own attention runs on the unquantised QKV activation (the flash kernel on the GPU) and
         never reads the cache: with an FP8 cache only what is STORED is quantised, and the logits are those
@@ -665,8 +673,15 @@ class GPT(torch.nn.Module):
         window: the prompt then runs over the cache as ONE ``extend`` step of T0 rows on ``ops.attention_chunk``
         (``generate(prefill_chunk=N)`` runs it in steps of N instead). With an FP8 cache the prompt then attends the
         QUANTISED rows, as ``prefill_chunk`` does, and the logits are no longer those of a bf16 cache. On the torch
-        path (CPU, ``ops.torch_reference()``) the prompt's attention stays on the activation, under the windowed mask."""
+        path (CPU, ``ops.torch_reference()``) the prompt's attention stays on the activation, under the windowed mask.
+
+        ``w8a8=True`` with FP8 ``weights`` (``decode_weights()``): a prompt of more than 16 rows runs its block linears
+        on the dense FP8 GEMM and reads the FP8 copies (the rule of ``extend``); the LM head, and a prompt of up to 16
+        rows, stay on the "auto" route and the bf16 weights. ``w8a8=False`` is the prefill as it was; ``weights`` alone
+        changes nothing."""
         B, T = idx.shape
+        self._check_w8a8(weights, w8a8)
+        fp8 = w8a8 and B * T > ops.gemm.SKINNY_MAX_M
         if cache.ring and self.cfg.window is not None and self.cfg.window + T - 1 > cache.capacity:
             raise ValueError(f"prefill: a prompt of {T} tokens with window {self.cfg.window} needs a ring of capacity >= "
                              f"{self.cfg.window + T - 1}, got {cache.capacity}: run it in steps with extend(chunk=N)")
@@ -676,7 +691,9 @@ class GPT(torch.nn.Module):
         native = self._native_decode(self.tok)
         c = self.cfg
         if native and c.window is not None:  # the windowed MFMA kernel over the cache: one step of T rows
-            return self._extend_chunk(idx, cache, True, head="last", mfma=True)
+            # as ever by _route on the model's weights; with w8a8 its block linears on the FP8 copies, the head as ever
+            return self._extend_chunk(idx, cache, True, head="last", mfma=True, weights=weights if fp8 else None,
+                                      w8a8=fp8, head_weights=None)
         h, hkv, hd = self.blocks[0].local_heads, self.blocks[0].local_kv_heads, c.head_dim
         kv = {} if hkv == h else {"kv_heads": hkv}  # grouped K / V heads, read in place by the flash kernel
         mask = {"is_causal": True} if c.window is None else {"attn_mask": _window_mask(T, c.window, idx.device)}
@@ -691,9 +708,11 @@ class GPT(torch.nn.Module):
             x = x + self.pos[:T]
         if native:
             x = x.reshape(B * T, c.d_model)
-        w = self._weight_selector(None, B * T)  # the model's own weights, on the "auto" route, whatever B * T is
+        # the model's own weights, on the "auto" route, whatever B * T is; with w8a8 the FP8 copies above 16 rows
+        w = self._weight_selector(weights if fp8 else None, B * T, w8a8=fp8)
+        lin = self._w8a8 if fp8 else self._auto
         for li, blk in enumerate(self.blocks):
-            x = self._cache_layer(blk, li, x, cache, native=native, lin=self._auto, w=w, attend=attend)
+            x = self._cache_layer(blk, li, x, cache, native=native, lin=lin, w=w, attend=attend, w8a8=fp8)
         cache.advance(T)
         last = x.view(B, T, c.d_model)[:, -1]  # the LM head of the last position only
         # M = B rows: auto routes it as the parent commit did
@@ -723,6 +742,34 @@ class GPT(torch.nn.Module):
         # 17 .. stream_rows rows: the wide weight-streaming kernel (kernels/gemm_stream_wide.hip), on either weight type
         return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual, variant="stream")
 
+    def _w8a8(self, x, w, bias=None, act="none", residual=None):
+        # more rows than any weight-streaming route takes, with w8a8=True: the dense FP8 GEMM (kernels/gemm_fp8.hip) on
+        # the FP8 copy, x [rows, K] quantised per row by the op; on CPU tensors the op computes the same rule in torch
+        if isinstance(w, ops.QuantizedWeight):
+            return ops.gemm_nt(x, w, bias=bias, act=act, residual=residual, variant="w8a8")
+        # a matrix decode_weights() left in bf16 (inner dimension off the 16 grid): the route it has without w8a8
+        if x.is_cuda and ops.native_enabled():
+            return self._auto(x, w, bias, act, residual)
+        y = ops.gemm._act_reference(F.linear(x, w, bias).float(), act)
+        return (y if residual is None else y + residual.float()).to(x.dtype)
+
+    def _w8a8_nd(self, x, w, bias=None, act="none", residual=None):
+        """``_w8a8`` over ``x [..., K]`` (the torch path keeps the batch dimensions)."""
+        r2 = None if residual is None else residual.reshape(-1, residual.shape[-1])
+        return self._w8a8(x.reshape(-1, x.shape[-1]), w, bias, act, r2).view(*x.shape[:-1], -1)
+
+    def _check_w8a8(self, weights, w8a8: bool) -> None:
+        if not w8a8:
+            return
+        if not isinstance(weights, DecodeWeights):
+            raise ValueError("w8a8=True needs weights=GPT.decode_weights() (FP8)")
+        if any(isinstance(m, ops.MXFP4Weight) for m in weights.matrices()):
+            raise ValueError("w8a8=True needs FP8 decode weights, not MXFP4")
+        if self.blocks[0].tp_group is not None:
+            raise ValueError("w8a8=True with a tensor-parallel group is not built")
+        if self.cfg.dtype != torch.bfloat16:
+            raise ValueError(f"w8a8=True: a bf16 model expected, got {self.cfg.dtype}")
+
     @staticmethod
     def _check_stream_rows(stream_rows) -> int:
         lo, hi = ops.gemm.SKINNY_MAX_M, ops.gemm.STREAM_MAX_M
@@ -730,11 +777,13 @@ class GPT(torch.nn.Module):
             raise ValueError(f"stream_rows: an int in {lo} .. {hi} expected, got {stream_rows!r}")
         return stream_rows
 
-    def _route(self, rows: int, stream_rows: int):
+    def _route(self, rows: int, stream_rows: int, w8a8: bool = False):
         """The linear a step of ``rows`` rows runs on (the rule of ``extend``)."""
         if rows <= ops.gemm.SKINNY_MAX_M:
             return self._skinny
-        return self._stream if rows <= stream_rows else self._auto
+        if rows <= stream_rows:
+            return self._stream
+        return self._w8a8 if w8a8 else self._auto
 
     def _fc1(self, lin, y, w, blk):
         """The up-projection and its activation on the HIP kernels, ``lin`` being ``_skinny``, ``_stream`` or ``_auto``. GELU: the
@@ -774,7 +823,8 @@ class GPT(torch.nn.Module):
         bits per weight (``ops.quantize_weight(w, dtype="mxfp4")``); here a matrix stays bf16 when its inner dimension
         is no multiple of 32. Each format has its own memo: asking for one neither returns nor evicts the other's.
 
-        Which steps read them: those of up to max(16, ``stream_rows``) rows, see ``extend``; ``prefill`` never does."""
+        Which steps read them: those of up to max(16, ``stream_rows``) rows, see ``extend``; ``prefill`` and wider
+        steps only with ``w8a8=True``."""
         mx4 = ops.gemm.is_mxfp4(dtype)
         if not mx4 and dtype != torch.float8_e4m3fn:
             raise ValueError(f'decode_weights: torch.float8_e4m3fn or "mxfp4" expected, got {dtype}')
@@ -802,13 +852,13 @@ class GPT(torch.nn.Module):
         self.__dict__[slot] = memo  # not a parameter, buffer or submodule
         return memo
 
-    def _weight_selector(self, weights, rows: int, stream_rows: int = 16):
+    def _weight_selector(self, weights, rows: int, stream_rows: int = 16, w8a8: bool = False):
         """(layer, name) -> the weight a step of ``rows`` rows reads in that linear: the quantised one when
-        ``weights`` is given and the step takes a weight-streaming route (rows <= max(16, stream_rows)), else the
-        model's."""
+        ``weights`` is given and the step takes a weight-streaming route (rows <= max(16, stream_rows)) or, with
+        ``w8a8``, the dense FP8 route (more rows), else the model's."""
         if weights is not None and not isinstance(weights, DecodeWeights):
             raise TypeError("weights: a DecodeWeights (GPT.decode_weights()) expected")
-        if weights is None or rows > max(ops.gemm.SKINNY_MAX_M, stream_rows):
+        if weights is None or (rows > max(ops.gemm.SKINNY_MAX_M, stream_rows) and not w8a8):
             return lambda li, name: getattr(self.blocks[li], name).weight
         if len(weights.blocks) != len(self.blocks):
             raise ValueError("weights do not match the model")
@@ -853,7 +903,7 @@ class GPT(torch.nn.Module):
     @torch.no_grad()
     def extend(self, idx: torch.Tensor, cache, last_only: bool = False,
                weights: "DecodeWeights | None" = None, chunk: int | None = None,
-               stream_rows: int = 16) -> torch.Tensor:
+               stream_rows: int = 16, w8a8: bool = False) -> torch.Tensor:
         """Append ``idx [B, T]`` (T >= 1 tokens per row) to ``cache`` in any state, empty included; logits
         ``[B, T, vocab]`` of every new position (``[B, vocab]`` of the last one with ``last_only``).
         Advances the cache by T. On the GPU a step of up to 16 tokens runs the decode kernels with
@@ -876,6 +926,14 @@ class GPT(torch.nn.Module):
         ``weights`` (either format) when given. More rows: the "auto" route on the model's bf16 weights. With the
         default nothing above 16 rows streams; the torch path selects its weights by the same rule.
 
+        ``w8a8=True`` (FP8 ``weights`` required; ``ValueError`` with ``weights=None``, MXFP4 weights or a
+        tensor-parallel group): a step of ``rows > max(16, stream_rows)`` runs qkv, proj, fc1 and fc2 on
+        ``ops.gemm_nt(variant="w8a8")`` (``kernels/gemm_fp8.hip``; the rule in ``ops/gemm.py``'s docstring) and reads
+        the FP8 copies: each linear's input is quantised per row once (one launch), a SwiGLU model runs the GEMM to
+        ``[rows, 2 d_ff]`` and then ``ops.swiglu``, as the "auto" route does. The LM head and steps of fewer rows keep
+        the routes above. The torch path computes the same rule. ``w8a8=False`` (the default) is everything above,
+        unchanged.
+
         ``chunk=N`` (16 < N <= the cache's capacity): the input runs in steps of N tokens per row instead of 16,
         attention on ``ops.attention_chunk`` (MFMA query tiles over the cache, K / V read once per 128 new
         rows), the linears on the route the step's row count B * N picks (the bf16 weights above 16 rows,
@@ -887,6 +945,7 @@ class GPT(torch.nn.Module):
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError(f"extend: idx [B, T >= 1] expected, got {tuple(idx.shape)}")
         stream_rows = self._check_stream_rows(stream_rows)
+        self._check_w8a8(weights, w8a8)
         B, T = idx.shape
         if not cache.ring:
             self._check_cache(cache, B, T)
@@ -906,17 +965,21 @@ class GPT(torch.nn.Module):
             final = t0 + R >= T
             if last_only and not final:
                 self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="none", weights=weights,
-                                   mfma=chunk is not None, stream_rows=stream_rows)
+                                   mfma=chunk is not None, stream_rows=stream_rows, w8a8=w8a8)
             else:
                 outs.append(self._extend_chunk(idx[:, t0:t0 + R], cache, native, head="last" if last_only else "all",
-                                               weights=weights, mfma=chunk is not None, stream_rows=stream_rows))
+                                               weights=weights, mfma=chunk is not None, stream_rows=stream_rows,
+                                               w8a8=w8a8))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
 
     def _extend_chunk(self, idx, cache, native: bool, head: str, weights=None, mfma: bool = False,
-                      stream_rows: int = 16):
+                      stream_rows: int = 16, w8a8: bool = False, head_weights="weights"):
         """One extend step of T tokens per row (T <= 16 on ``ops.attention_extend``; any T with ``mfma``, on
-        ``ops.attention_chunk``); ``head``: LM head on "all" rows, the "last", or "none"."""
+        ``ops.attention_chunk``); ``head``: LM head on "all" rows, the "last", or "none". ``head_weights``: what the
+        LM head's rule selects from, ``weights`` unless given (``prefill``'s head never reads the quantised copy)."""
         B, T = idx.shape
+        if isinstance(head_weights, str):
+            head_weights = weights
         attention = ops.attention_chunk if mfma else ops.attention_extend
         c = self.cfg
         h, hd = self.blocks[0].local_heads, c.head_dim
@@ -926,8 +989,9 @@ class GPT(torch.nn.Module):
             x = x + F.embedding(pos, self.pos)
         # the step's attention sees the rows it appends: lens + T, computed on the device
         att = self._att(cache, T, c.window)
-        lin = self._route(B * T, stream_rows)
-        wsel = self._weight_selector(weights, B * T, stream_rows)
+        lin = self._route(B * T, stream_rows, w8a8)
+        fp8 = w8a8 and B * T > max(ops.gemm.SKINNY_MAX_M, stream_rows)  # the route is _w8a8
+        wsel = self._weight_selector(weights, B * T, stream_rows, w8a8)
 
         def attend(li, qkv, native):
             q = qkv[..., :h * hd].view(B, T, h, hd)
@@ -939,7 +1003,7 @@ class GPT(torch.nn.Module):
         if native:
             x = x.reshape(B * T, c.d_model)
         for li, blk in enumerate(self.blocks):
-            x = self._cache_layer(blk, li, x, cache, native=native, lin=lin, w=wsel, attend=attend)
+            x = self._cache_layer(blk, li, x, cache, native=native, lin=lin, w=wsel, attend=attend, w8a8=fp8)
         cache.advance(T)
         if head == "none":
             return None
@@ -947,7 +1011,7 @@ class GPT(torch.nn.Module):
         if head == "last":
             x = x[:, -1].contiguous()  # [B, d_model]
         rows = x.numel() // c.d_model  # the head's own row count picks its weight and its route
-        head_w = self._head_weight(weights, rows, stream_rows)
+        head_w = self._head_weight(head_weights, rows, stream_rows)
         head_lin = self._route(rows, stream_rows)
         if not native:
             return self._lm_head(x, head_w, head_lin, False)
@@ -1012,7 +1076,7 @@ class GPT(torch.nn.Module):
                  weight_dtype: torch.dtype | None = None, top_p: float | None = None, stop_token: int | None = None,
                  sampler: str = "torch", prefill_chunk: int | None = None, ring: bool = False, paged: bool = False,
                  num_samples: int | None = None, pool: "ops.PagePool | None" = None, return_cache: bool = False,
-                 stream_rows: int = 16):
+                 stream_rows: int = 16, w8a8: bool = False):
         """Sample ``max_new_tokens`` after the prompt ``idx [B, T0]`` -> ``[B, T0 + max_new_tokens]``.
         ``temperature == 0``: greedy; otherwise softmax sampling (optionally over the ``top_k`` largest
         logits) with ``torch.multinomial`` under ``generator``. ``graph=True`` (GPU): decode_step is
@@ -1033,6 +1097,10 @@ class GPT(torch.nn.Module):
         ``stream_rows`` (16 .. 128): decode steps of up to that many rows (``B``, or ``B * num_samples``) stream their
         weights, the quantised ones with ``weight_dtype`` (the rule of ``extend``); the default 16 leaves wider batches
         on the "auto" route and the bf16 weights. The prompt is not a decode step and ignores it.
+
+        ``w8a8=True`` (with ``weight_dtype=torch.float8_e4m3fn``; ``ValueError`` without it, with ``"mxfp4"``, with a
+        tensor-parallel group or with ``draft=``): the prompt steps, ``prefill`` or ``prefill_chunk``'s ``extend``, get
+        the FP8 weights and run their linears of more than 16 rows on the dense FP8 GEMM (the rule of ``extend``).
 
         ``sampler``: ``"torch"`` (the default) is the sampler described above; ``top_p`` / ``stop_token`` raise
         with it. ``"fused"`` samples every token with ``ops.sample`` (one HIP kernel on the GPU, the same rule
@@ -1074,6 +1142,10 @@ class GPT(torch.nn.Module):
         or a look at ``cache.pool``; call ``cache.release()`` when done. Not built (raises): ``paged`` / ``num_samples``
         with ``draft=``, with ``ring`` or a windowed model, or with a tensor-parallel group that issues collectives."""
         stream_rows = self._check_stream_rows(stream_rows)
+        if w8a8:
+            if weight_dtype != torch.float8_e4m3fn or draft is not None:
+                raise ValueError("generate(w8a8=True) needs weight_dtype=torch.float8_e4m3fn and no draft")
+            self._check_w8a8(self.decode_weights(weight_dtype), True)
         if num_samples is not None:
             if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
                 raise ValueError(f"generate(num_samples=...): an int >= 1 expected, got {num_samples!r}")
@@ -1145,7 +1217,11 @@ class GPT(torch.nn.Module):
                                    n_pages=None if pool is not None else n_pages)
         else:
             cache = self.new_cache(B, total, device=idx.device, kv_dtype=kv_dtype)
-        if prefill_chunk is None:
+        if w8a8:  # the prompt's wide steps on the FP8 weights
+            pw = self.decode_weights(weight_dtype)
+            logits = (self.prefill(idx, cache, weights=pw, w8a8=True) if prefill_chunk is None else
+                      self.extend(idx, cache, last_only=True, chunk=prefill_chunk, weights=pw, w8a8=True))
+        elif prefill_chunk is None:
             logits = self.prefill(idx, cache)
         else:  # the bf16 weights, as prefill: a prompt is not a decode step
             logits = self.extend(idx, cache, last_only=True, chunk=prefill_chunk)

@@ -1,7 +1,7 @@
 """Torch-facing wrappers of the hand-written gfx950 kernels (no silent eager fallback)."""
 from ._lib import NativeLibraryError, available, build_info, lib  # noqa: F401
-from .gemm import MXFP4Weight, QuantizedWeight, quantize_weight  # noqa: F401
-from .gemm import act_grad, dgrad_act, flops, gemm_nt, gemm_nt_preact, gemm_nt_stream, linear, matmul, mlp, mm, wgrad_pair  # noqa: F401
+from .gemm import MXFP4Weight, QuantizedWeight, quantize_act, quantize_weight  # noqa: F401
+from .gemm import act_grad, dgrad_act, flops, gemm_nt, gemm_nt_preact, gemm_nt_stream, gemm_nt_w8a8, linear, matmul, mlp, mm, wgrad_pair  # noqa: F401
 from .layernorm import layer_norm, layer_norm_fwd, layer_norm_residual, rms_norm, rms_norm_fwd, rms_norm_residual  # noqa: F401
 from .xent import cross_entropy  # noqa: F401
 from .attention import attention_qkv, attn_block, doc_bounds, doc_mask, flash_attention, split_heads  # noqa: F401

@@ -250,6 +250,10 @@ _SIGNATURES = {
                                             c_float, c_vp]),
     "kfamd_gemm_nt_stream_mx4_glu": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
                                              c_ll, c_float, c_vp]),
+    "kfamd_gemm_nt_fp8_plan": (c_int, [c_int, c_int]),
+    "kfamd_gemm_nt_fp8": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                  c_ll, c_float, c_int, c_vp]),
+    "kfamd_quantize_rows_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_ll, c_vp]),
     "kfamd_swiglu_fwd_bf16": (c_int, [c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_vp]),
     "kfamd_swiglu_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_ll, c_vp]),
     "kfamd_rmsnorm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp]),

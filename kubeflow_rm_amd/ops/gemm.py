@@ -4,6 +4,25 @@
 weight layout), optionally batched, with a fused epilogue: ``alpha``, bias, activation
 (relu / gelu_tanh / silu) or residual add. ``linear`` is the autograd-aware ``F.linear``
 replacement used by :mod:`kubeflow_rm_amd.models` and the TP layers.
+
+The W8A8 rule (``variant="w8a8"``, ``kernels/gemm_fp8.hip``; stated here once). ``gemm_nt(a, b, variant="w8a8")`` with
+``b`` a ``QuantizedWeight [N, K]`` computes
+
+    ``C[m, n] = act(alpha * sa[m] * sb[n] * sum_k ca[m, k] * cb[n, k] + bias[n]) + residual[m, n]``
+
+with fp32 accumulation and ONE RNE rounding to bf16. ``(ca, sa)`` are the activation's FP8 rows in the format of
+``ops.decode.quantize_rows`` (e4m3fn codes, one fp32 scale per row: amax / 448, 1 for an all-zero row): ``a`` is a bf16
+``[M, K]`` tensor, which ``quantize_act`` quantises first (one kernel launch), or an already quantised
+``QuantizedWeight [M, K]`` (the class is "FP8 rows + one fp32 scale per row"). ``act`` is any of ``ACTS``; ``bias``,
+``residual``, ``alpha`` and ``out=`` (any row stride) as in the other variants. ``ValueError`` before any launch: an
+``MXFP4Weight``, a batched call (``a`` not 2-D), ``act="swiglu"``, a non-unit inner stride, ``K < 16`` or
+``K % 16 != 0``. CPU tensors and ``ops.torch_reference()`` run the same rule in torch: ``quantize_rows`` on ``a``, then
+an fp32 matmul of the dequantised operands. No silent fallback.
+
+The kernels' divisions are IEEE, so ``quantize_act`` on the GPU is bit for bit ``quantize_rows`` of the CPU copy of the
+input, as the FP8 KV cache's append is. ``quantize_rows`` run by torch on a CUDA tensor, which is what
+``ops.torch_reference()`` does there, divides by multiplying with a reciprocal: its scales, and rarely a code, can
+differ from the kernel's in the last bit.
 """
 from __future__ import annotations
 
@@ -400,6 +419,102 @@ def gemm_nt_stream(a, b, *, bias=None, residual=None, alpha: float = 1.0, act: s
     return out
 
 
+W8A8_PLANS = {"auto": 0, "large": 1, "small": 2}  # the 256 x 256 / 128 x 128 tile of kernels/gemm_fp8.hip
+
+
+def quantize_act(x: torch.Tensor) -> QuantizedWeight:
+    """A bf16 activation ``[M, K]`` (any row stride) as FP8 rows: bit for bit ``ops.decode.quantize_rows`` with IEEE
+    divisions (the module docstring's note), codes and scales, in one kernel launch (``quantize_rows_bf16`` of
+    ``kernels/gemm_fp8.hip``; K % 8 == 0). On CPU tensors and under ``ops.torch_reference()``: ``quantize_rows``."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.shape[0] < 1:
+        raise ValueError(f"quantize_act: a bf16 [M >= 1, K] tensor expected, got {tuple(x.shape)} {x.dtype}")
+    from . import native_enabled
+    if not x.is_cuda or not native_enabled():
+        codes, scale = quantize_rows(x)
+        return QuantizedWeight(codes.contiguous(), scale.contiguous())
+    M, K = x.shape
+    if K < 8 or K % 8:
+        raise ValueError(f"quantize_act: K >= 8 and K % 8 == 0 expected, got K={K}")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.contiguous_format)  # (contiguous() returns a one-row view as it is)
+    codes = torch.empty(M, K, dtype=FP8, device=x.device)
+    scale = torch.empty(M, dtype=torch.float32, device=x.device)
+    rc = _lib.lib().kfamd_quantize_rows_bf16(x.data_ptr(), codes.data_ptr(), scale.data_ptr(), M, K, x.stride(0), K,
+                                             _stream_ptr(x))
+    _lib.check(rc, f"quantize_act[{M}x{K}]")
+    return QuantizedWeight(codes, scale)
+
+
+def _act_reference(c: torch.Tensor, act: str) -> torch.Tensor:
+    if act == "relu":
+        return torch.relu(c)
+    if act in ("gelu", "gelu_tanh"):
+        return torch.nn.functional.gelu(c, approximate="tanh")
+    return torch.nn.functional.silu(c) if act == "silu" else c
+
+
+def gemm_nt_w8a8(a, b, *, bias=None, residual=None, alpha: float = 1.0, act: str = "none", out=None,
+                 plan: str = "auto"):
+    """``gemm_nt(..., variant="w8a8")``: the dense FP8 GEMM of the module docstring's W8A8 rule. ``plan`` (tests /
+    bench): "auto" lets the launcher choose its tile, "large" / "small" force the 256 x 256 / 128 x 128 one."""
+    if isinstance(b, MXFP4Weight) or isinstance(a, MXFP4Weight):
+        raise ValueError('gemm_nt variant="w8a8": an MXFP4Weight is not an FP8 operand')
+    if not isinstance(b, QuantizedWeight):
+        raise ValueError(f'gemm_nt variant="w8a8": b must be a QuantizedWeight [N, K], got {type(b).__name__}')
+    if act == "swiglu" or act not in ACTS:
+        raise ValueError(f'gemm_nt variant="w8a8": act in {sorted(ACTS)} expected (the gate: ops.swiglu on the '
+                         f"result), got {act!r}")
+    if plan not in W8A8_PLANS:
+        raise ValueError(f'gemm_nt variant="w8a8": plan in {sorted(W8A8_PLANS)} expected, got {plan!r}')
+    quant = isinstance(a, QuantizedWeight)
+    at = a.codes if quant else a
+    if at.dim() != 2:
+        raise ValueError(f'gemm_nt variant="w8a8": a non-batched a [M, K] expected, got {tuple(at.shape)}')
+    if not quant and at.dtype != torch.bfloat16:
+        raise TypeError(f"a must be bfloat16 or a QuantizedWeight, got {at.dtype}")
+    M, K = at.shape
+    N = b.shape[0]
+    if b.shape[1] != K:
+        raise ValueError(f"inner dims differ: a has K={K}, the weight has K={b.shape[1]}")
+    if at.stride(1) != 1 or b.codes.stride(1) != 1:
+        raise ValueError('gemm_nt variant="w8a8": operands with a unit inner stride expected')
+    if M < 1 or K < 16 or K % 16:
+        raise ValueError(f'gemm_nt variant="w8a8": M >= 1, K >= 16 and K % 16 == 0 expected, got M={M} K={K}')
+    if b.device != at.device:
+        raise ValueError("gemm_nt: the weight must live on a's device")
+    for t, name, shape in ((bias, "bias", (N,)), (residual, "residual", (M, N)), (out, "out", (M, N))):
+        if t is not None and (t.dtype != torch.bfloat16 or tuple(t.shape) != shape or t.device != at.device
+                              or t.stride(-1) != 1):
+            raise ValueError(f"{name} must be a bf16 {shape} tensor on {at.device} with a unit inner stride")
+    from . import native_enabled
+    if not at.is_cuda or not native_enabled():
+        qa = a if quant else quantize_act(a)
+        c = float(alpha) * (qa.dequantize() @ b.dequantize().t())
+        if bias is not None:
+            c = c + bias.float()
+        c = _act_reference(c, act)
+        if residual is not None:
+            c = c + residual.float()
+        c = c.to(torch.bfloat16)
+        return c if out is None else out.copy_(c)
+    qa = a if quant else quantize_act(a)
+
+    def aligned(t):  # the kernel's 16-byte rows; codes off that grid are copied (K % 16 == 0 keeps a copy on it)
+        ok = t.stride(0) % 16 == 0 and t.data_ptr() % 16 == 0
+        return t if ok else t.clone(memory_format=torch.contiguous_format)
+    ca, cb = aligned(qa.codes), aligned(b.codes)
+    sa, sb = qa.scale.contiguous(), b.scale.contiguous()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=at.device)
+    rc = _lib.lib().kfamd_gemm_nt_fp8(
+        W8A8_PLANS[plan], ca.data_ptr(), sa.data_ptr(), cb.data_ptr(), sb.data_ptr(), out.data_ptr(),
+        bias.data_ptr() if bias is not None else None, residual.data_ptr() if residual is not None else None,
+        M, N, K, ca.stride(0), cb.stride(0), out.stride(0), residual.stride(0) if residual is not None else 0,
+        float(alpha), ACTS[act], _stream_ptr(at))
+    _lib.check(rc, f"gemm_nt[w8a8 {M}x{N}x{K}]")
+    return out
+
+
 def _stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -495,7 +610,11 @@ def gemm_nt(a: torch.Tensor, b: "torch.Tensor | QuantizedWeight | MXFP4Weight", 
     silu(z[..., 2j]) * z[..., 2j + 1] of z = alpha * a @ b^T + bias, shape ``[..., N / 2]``, in the GEMM's one launch;
     a residual, an odd N or any other variant raises ``ValueError``.
     ``variant="stream"``: the wide weight-streaming kernel for a non-batched call of up to ``STREAM_MAX_M`` = 128 rows
-    on any of the three weight types, ``act="swiglu"`` included (``gemm_nt_stream``); outside its contract it raises."""
+    on any of the three weight types, ``act="swiglu"`` included (``gemm_nt_stream``); outside its contract it raises.
+    ``variant="w8a8"``: the dense FP8 GEMM on a ``QuantizedWeight`` for any M (``gemm_nt_w8a8``; the module docstring
+    states its rule); ``a`` is bf16 (quantised per row first) or a ``QuantizedWeight``."""
+    if variant == "w8a8":
+        return gemm_nt_w8a8(a, b, bias=bias, residual=residual, alpha=alpha, act=act, out=out)
     if variant == "stream":
         return gemm_nt_stream(a, b, bias=bias, residual=residual, alpha=alpha, act=act, out=out)
     if act == "swiglu":

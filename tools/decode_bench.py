@@ -92,6 +92,11 @@ limit, and a step that fails or times out ends the run (nothing more is started 
         interleaved blocks: us, min - max, TB/s of weight bytes. Model: a graphed gpt-1b decode step (gpt-small with
         --quick) at position about 2048, B in {32, 64, 128}: stream_rows=128 on the three weight formats against
         stream_rows=16, bf16 and FP8 caches.
+  w8a8  (not in the default list) the dense FP8 GEMM. Kernel: gemm_nt(variant="w8a8") at the gpt-1b projection shapes,
+        M in {128, 512, 2048, 8192}: the quantise launch, the GEMM on quantised rows (launcher's plan and both forced)
+        and their sum, against variant="auto" on bf16 operands, 7 interleaved blocks: us, min - max, TFLOP/s. Model: a
+        512-token extend(chunk=512) turn over 1536 cached tokens and a 2048-token prefill of gpt-1b (gpt-small with
+        --quick), with and without w8a8, and the max-abs logit shift against the bf16 weights.
 """
 from __future__ import annotations
 
@@ -109,7 +114,7 @@ if str(ROOT) not in sys.path:
 
 ROOF = 6.29e12
 STEP_LIMIT_S = {"gemm": 300, "attn": 150, "e2e": 420, "extend": 600, "kv8": 420, "w8": 900, "mx4": 900, "sample": 420,
-                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600, "ring": 900, "stream": 1100}
+                "chunk": 900, "gqa": 1000, "rope": 600, "glu": 600, "window": 600, "ring": 900, "stream": 1100, "w8a8": 900}
 WINDOW_WS = (256, 1024, 4095, 4096)
 GQA_GS = (1, 2, 4, 8, 16)
 GQA_FORMS = ((8, 1), (4, 2), (2, 4), (16, 1), (8, 2), (4, 4), (2, 8))  # (G, T) with T * G in {8, 16}
@@ -1639,7 +1644,90 @@ def step_stream(quick: bool):
     return result
 
 
-STEPS = {"stream": step_stream, "ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8, "mx4": step_mx4}
+W8A8_MS = (128, 512, 2048, 8192)
+
+
+def _w8a8_kernel_rows(quick: bool):
+    """us per call at the gpt-1b projection shapes: "auto" on bf16 operands (the yardstick), the activation quantiser,
+    the FP8 GEMM on already quantised rows (plan by the launcher, and both forced) and the op on a bf16 activation
+    (quantise + GEMM); TFLOP/s of 2 M N K."""
+    import torch
+    from kubeflow_rm_amd import ops
+    rows = []
+    for N, K in GEMM_SHAPES[:2] if quick else GEMM_SHAPES[:4]:
+        w = torch.randn(N, K, device="cuda").mul_(0.02).to(torch.bfloat16)
+        qw = ops.quantize_weight(w)
+        bias = torch.randn(N, device="cuda").to(torch.bfloat16)
+        for M in W8A8_MS[:2] if quick else W8A8_MS:
+            a = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            qa = ops.quantize_act(a)
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            fns = {"auto_bf16": lambda i: ops.gemm_nt(a, w, bias=bias, out=out),
+                   "quantize": lambda i: ops.quantize_act(a),
+                   "w8a8_sum": lambda i: ops.gemm_nt(a, qw, bias=bias, out=out, variant="w8a8")}
+            for plan in ("auto", "large", "small"):
+                fns[f"gemm_{plan}"] = (lambda p: lambda i: ops.gemm_nt_w8a8(qa, qw, bias=bias, out=out, plan=p))(plan)
+            r = _time_blocks(fns, blocks=3 if quick else 7, iters=max(4, min(64, (1 << 36) // (M * N * K))))
+            row = {"M": M, "N": N, "K": K, **r, "plan": ["auto", "large", "small"][
+                ops.lib().kfamd_gemm_nt_fp8_plan(M, N)]}
+            for k in ("auto_bf16", "gemm_auto", "w8a8_sum"):
+                row[f"{k}_TFLOPs"] = 2.0 * M * N * K / r[k]["median_us"] / 1e6
+            row["auto_over_w8a8_sum"] = r["auto_bf16"]["median_us"] / r["w8a8_sum"]["median_us"]
+            row["separated"] = _sep(*({"min": r[k]["min_us"], "max": r[k]["max_us"]}
+                                      for k in ("auto_bf16", "w8a8_sum")))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def _w8a8_model_rows(model, name: str, quick: bool):
+    """ms per call, B = 1: a 512-token extend(chunk=512) turn over 1536 cached tokens and a 2048-token prefill, bf16
+    route against w8a8=True; the max-abs shift of the last position's logits."""
+    import torch
+    W = model.decode_weights()
+    T0, T1 = (256, 128) if quick else (2048, 512)
+    idx = torch.randint(0, model.cfg.vocab_size, (1, T0), device="cuda")
+    cache = model.new_cache(1, T0)
+    runs = {}
+    for key, kw in (("bf16", {}), ("w8a8", {"weights": W, "w8a8": True})):
+        def prefill(kw=kw):
+            cache.reset()
+            return model.prefill(idx, cache, **kw)
+
+        def turn(kw=kw):
+            cache.set_lens([T0 - T1])
+            return model.extend(idx[:, -T1:], cache, last_only=True, chunk=T1, **kw)
+        runs[f"prefill{T0}_{key}"], runs[f"chunk{T1}_{key}"] = prefill, turn
+    row = {"model": name, "B": 1}
+    logits = {k: f().float() for k, f in runs.items()}  # also the warm-up
+    for what in (f"prefill{T0}", f"chunk{T1}"):
+        row[f"{what}_logit_shift_max_abs"] = (logits[f"{what}_w8a8"] - logits[f"{what}_bf16"]).abs().max().item()
+        row[f"{what}_logit_max_abs"] = logits[f"{what}_bf16"].abs().max().item()
+    times = {k: [] for k in runs}
+    for b in range(3 if quick else 7):
+        for k, f in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / 4)
+    for k, v in times.items():
+        row[k] = {"median_ms": statistics.median(v), "min": min(v), "max": max(v)}
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def step_w8a8(quick: bool):
+    from kubeflow_rm_amd.models import CONFIGS, GPT
+    result = {"kernel": _w8a8_kernel_rows(quick)}
+    name = "gpt-small" if quick else "gpt-1b"
+    result["model"] = [_w8a8_model_rows(GPT(CONFIGS[name], device="cuda").eval(), name, quick)]
+    return result
+
+
+STEPS = {"w8a8": step_w8a8, "stream": step_stream, "ring": step_ring, "window": step_window, "glu": step_glu, "rope": step_rope, "gqa": step_gqa,"chunk": step_chunk, "sample": step_sample, "gemm": step_gemm, "attn": step_attn, "e2e": step_e2e, "extend": step_extend, "kv8": step_kv8, "w8": step_w8, "mx4": step_mx4}
 
 
 def main() -> int:
